@@ -14,7 +14,7 @@ iteration (HIP events recorded by the solver, rsba_get_phase_times).  At N = 1 t
 ("cpu_baseline": evaluation at 1 and at the best of all / half / quarter of the host's threads, and its LM iteration) and
 the rows next to the path add bounded wall-clock figures under "next_rows".
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -248,6 +248,47 @@ def shard_eval(full, world: int, device, capi, steps: int = 20):
                     "what each rank's timed region is made of); predicted_value_from_kernel_time uses the HIP-event kernel time alone and is the upper bound"}
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # under the 64 MB the dump may take, .npy headers included
+DUMP_SEED = 0x5BA
+
+
+def dump_outputs(dp, prob, outdir, rank, world):
+    """--dump-outputs: what the timed loop's LAST step left in HBM, read through rsba_get_device_view (no further evaluation) and
+    returned in the caller's observation order, as rsba_evaluate would: residuals [n, 2] and raw Jacobian blocks [n, 2, K], float64.
+    When a rank's share of the budget cannot hold every observation, a fixed sample (DUMP_SEED) is taken, sorted, and its
+    caller-side indices are written beside it as observation_index.npy.  On several ranks each writes its own shard, suffixed _rank<r>."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from rsba_amd.distributed import _DevicePtr
+    n = prob.num_observations
+    v = dp.device_view()
+    k, tile = v.jacobian_cols, v.tile
+    span = -(-n // tile) * tile                                   # the buffers hold whole tiles; the last one's tail is not an observation
+    order = np.ctypeslib.as_array(C.cast(v.order_host, C.POINTER(C.c_int64)), shape=(n,)) if n else np.zeros(0, np.int64)
+    internal_of = np.empty(n, np.int64)
+    internal_of[order] = np.arange(n)                             # caller's index -> internal (tiled) position
+    cap = DUMP_BUDGET_BYTES // world // ((3 + 2 * k) * 8)         # residuals + Jacobians + the index, per observation
+    pick = np.arange(n) if n <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+    i = internal_of[pick]
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def gather(ptr, ncomp):   # component c of internal observation i: base[(i / tile) * ncomp * tile + c * tile + i % tile]
+        flat = torch.as_tensor(_DevicePtr(int(ptr), span * ncomp), device=dev)
+        at = ((i // tile) * ncomp * tile + i % tile)[:, None] + np.arange(ncomp)[None, :] * tile
+        return flat[torch.from_numpy(at).to(dev)].cpu().numpy()
+
+    if n:
+        res, jac = gather(v.residuals, 2), gather(v.jacobians, 2 * k).reshape(-1, 2, k)
+    else:     # a rank that owns no observation
+        res, jac = np.zeros((0, 2)), np.zeros((0, 2, k))
+    out = {"residuals": res, "jacobians": jac, "observation_index": pick.astype(np.float64)}
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def next_rows(prob, dp, device):
     """Wall-clock figures of the rows next to the hot path, on rank 0 at N = 1 only: bounded (about a second
     in total) and never fatal — they ride in the JSON line under "next_rows", they are not the metric."""
@@ -371,7 +412,10 @@ def main():
     ap.add_argument("--no-lm", action="store_true")
     ap.add_argument("--lm-iters", type=int, default=12)
     ap.add_argument("--no-next-rows", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64, under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -463,6 +507,8 @@ def main():
         dp.evaluate_device(True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:   # outside the timed region, before anything else runs on the handle
+        dump_outputs(dp, prob, args.dump_outputs, rank, world)
     barrier()
     cdev = "cpu" if one_gpu else "cuda"
     n_obs = torch.tensor([float(prob.num_observations)], device=cdev, dtype=torch.float64)

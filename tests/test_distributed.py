@@ -126,10 +126,10 @@ def run_bench(nproc, config, extra_env=None, lm_iters=6, timeout=1200):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,config", [(2, "C2"), (5, "C4"), (8, "C4")])
+@pytest.mark.parametrize("world,config", [(2, "C2"), (3, "C4"), (4, "C4")])   # (at most four ranks: with this process and the launcher, six processes have the shared GPU open)
 def test_bench_takes_its_native_rccl_branch_with_several_ranks(world, config):
     """The branch of bench.py the driver's multi-GPU command takes — attach_rccl -> rsba_rccl_comm_create -> rsba_set_exchange_rccl, the warm
-    handle of the LM leg on the SAME communicator, the LM solve on the watchdog thread with comm set — run here with 2 and 8 ranks on one
+    handle of the LM leg on the SAME communicator, the LM solve on the watchdog thread with comm set — run here with 2 to 4 ranks on one
     GPU: RSBA_BENCH_NATIVE=1 + RSBA_RCCL_LIB = the stream-ordered stand-in for librccl (tools/mock_rccl.hip; RCCL itself refuses two
     ranks on one device).  Every rank must report the communicator as the library sees it, the sharded plan, and the one-GPU cost."""
     one = run_bench(1, config)
@@ -309,25 +309,25 @@ def test_sharded_factorisation_two_ranks_c2(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_sharded_factorisation_at_c4_size(tmp_path, world):
-    """The headline configuration (1000 frames, 100k points, 2.04 M observations) on 2, 4 and 8 ranks sharing one GPU: the sharded
+    """The headline configuration (1000 frames, 100k points, 2.04 M observations) on 2, 3 and 4 ranks sharing one GPU: the sharded
     factorisation reproduces the single-GPU LM trajectory to 1e-9, and exchange (2) carries the separators only."""
     res = run_two_ranks("nd:C4:4", tmp_path, world)
     a = check_nd(res, world)
     full = a["ref_plan"]["exchange_doubles"]                 # the replicated factorisation's payload: every non-zero tile of S | rhs
-    assert a["plan"]["exchange_doubles"] <= {2: 0.12, 4: 0.25, 8: 0.6}[world] * full
+    assert a["plan"]["exchange_doubles"] <= {2: 0.12, 3: 0.18, 4: 0.25}[world] * full   # (7, 12, 19 separator tile columns)
     assert a["plan"]["separator_tiles"] == a["top_tile_columns"]
 
 
 @pytest.mark.gpu
 def test_sharded_factorisation_at_c5_size(tmp_path):
     """BASELINE config 5 as it is quoted — 4000 frames, 500k points, 10.3 M observations, Huber loss, the shared intrinsics block as a
-    parameter block — on EIGHT ranks (sharing one GPU; gloo callback transport): every rank factors its own part of the reduced system,
+    parameter block — on FOUR ranks (sharing one GPU; gloo callback transport): every rank factors its own part of the reduced system,
     the 9-wide intrinsics border is one more separator all ranks share, and the LM trajectory is the single-GPU one to 1e-9 (which
     tests/test_gpu_fullsize.py holds against the oracle's)."""
-    res = run_two_ranks("nd:C5:3", tmp_path, 8, timeout=2400)
-    a = check_nd(res, 8)
+    res = run_two_ranks("nd:C5:3", tmp_path, 4, timeout=2400)
+    a = check_nd(res, 4)
     full = a["ref_plan"]["exchange_doubles"]
     assert a["plan"]["exchange_doubles"] <= 0.15 * full       # (12.2 MB of separators against 156 MB of tiles, DESIGN.md §5)
     assert a["plan"]["separator_tiles"] >= a["top_tile_columns"]   # (+ the intrinsics pseudo tile)
@@ -445,7 +445,7 @@ def test_a_rank_without_observations(tmp_path):
 # the host polls a pinned stamp while kernels and collectives of the iteration are in flight.
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 4, 5, 8])   # (5 and 8: round 6 — the stand-in's waits used to spin in every workgroup of its kernels, and with five or eight ranks on one GPU they starved each other's publish kernels until the bounded waits gave up: tools/mock_rccl.hip, gate_kernel)
+@pytest.mark.parametrize("world", [2, 3, 4])   # (at most four ranks: with this process and the launcher, six processes have the shared GPU open.  Round 6: the stand-in's waits used to spin in every workgroup of its kernels, and with five or eight ranks on one GPU they starved each other's publish kernels until the bounded waits gave up — tools/mock_rccl.hip, gate_kernel)
 def test_sharded_factorisation_at_c4_size_over_a_stream_ordered_transport(tmp_path, world):
     assert os.path.exists(MOCK_RCCL), "tools/libmock_rccl.so is built by __graft_entry__.build()"
     res = run_two_ranks("nd:C4:4:mock", tmp_path, world, env_extra={"RSBA_RCCL_LIB": MOCK_RCCL})

@@ -1,6 +1,6 @@
 """The reference's own known-answer tests (src/rsba/test/mat_test.cc) re-expressed against the CPU
 oracle: same input tables, same tolerances.  This is what pins the oracle's geometry helpers
-(SURVEY §4 / §8c).  Line numbers refer to /root/reference/src/rsba/test/mat_test.cc."""
+(SURVEY §4 / §8c).  Line numbers refer to the reference's src/rsba/test/mat_test.cc."""
 import math
 
 import numpy as np

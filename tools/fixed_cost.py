@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rsba_amd import capi
 from rsba_amd.scene import make_config
 prob = make_config("C4").problem
