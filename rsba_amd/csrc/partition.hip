@@ -12,7 +12,10 @@
 
 using namespace rsba;
 
-extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t world, int32_t* owner, int32_t* num_top_tiles) {
+namespace {
+
+// the cut (part_of: per tile column, -1 = a separator) and the owners of the points
+int32_t partition(const rsba_problem_desc* d, int32_t world, int32_t* owner, int32_t* num_top_tiles, std::vector<int32_t>& part_of) {
   if (!d || !owner || world < 1) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad partition arguments");
   const int P = d->poses_per_frame;
   if (P != 1 && P != 2) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "poses_per_frame must be 1 or 2");
@@ -21,7 +24,7 @@ extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t wor
   const int F = FR + NIB * NPF, nt = (F + FT - 1) / FT;
   const int64_t N = d->num_observations;
   if (num_top_tiles) *num_top_tiles = 0;
-  if (world == 1 || N == 0) { std::fill(owner, owner + M, 0); return RSBA_OK; }
+  if (world == 1 || N == 0) { std::fill(owner, owner + M, 0); part_of.assign(nt, 0); return RSBA_OK; }
   for (int64_t i = 0; i < N; ++i)
     if (d->obs_frame[i] < 0 || d->obs_frame[i] >= FR || d->obs_point[i] < 0 || d->obs_point[i] >= M) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "observation index out of range");
   auto intr_of = [&](int f) { return (NIB > 1 && d->frame_intrinsics) ? d->frame_intrinsics[f] : 0; };
@@ -35,13 +38,16 @@ extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t wor
   std::vector<double> weight(nt, 0.0);
   for (int64_t i = 0; i < N; ++i) weight[d->obs_frame[i] / FT] += 1.0;
   std::vector<int32_t> tiles;
-  for (int j = 0; j < M; ++j) {
+  auto tiles_of = [&](int j) {
     tiles.clear();
     for (int64_t x = ptr[j]; x < ptr[j + 1]; ++x) {
       tiles.push_back(fr[x] / FT);
       for (int v = 0; v < NPF; ++v) tiles.push_back((FR + intr_of(fr[x]) * NPF + v) / FT);
     }
     std::sort(tiles.begin(), tiles.end()); tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
+  };
+  for (int j = 0; j < M; ++j) {
+    tiles_of(j);
     for (size_t a = 0; a < tiles.size(); ++a) for (size_t b = 0; b < a; ++b) pair[(size_t)tiles[a] * nt + tiles[b]] = 1;
   }
   for (int f = 0; f < FR && NIB > 0; ++f) for (int v = 0; v < NPF; ++v) { const int a = (FR + intr_of(f) * NPF + v) / FT, b = f / FT; if (a != b) pair[(size_t)std::max(a, b) * nt + std::min(a, b)] = 1; }
@@ -54,13 +60,16 @@ extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t wor
   int ntop = 0;
   for (int t = 0; t < nt; ++t) ntop += ord.part_of[t] < 0;
   if (num_top_tiles) *num_top_tiles = ntop;
-  // a point belongs to the part of any of its tiles that has one; points seen in separator tiles only touch the tiles every rank
-  // shares, so any rank may own them: they go, in point order, to whoever holds the fewest observations so far
+  // a point belongs to the part of any of its tiles — real frames' and the pseudo frames' of the blocks it is seen through — that has
+  // one (its tiles are a clique of the graph cut above, so at most one part is among them); points whose tiles are all separator
+  // tiles touch only what every rank shares, so any rank may own them: they go, in point order, to whoever holds the fewest
+  // observations so far.  (A point seen in separator frames only may still be seen through a block whose pseudo tile is in a part.)
   std::vector<int64_t> load(world, 0);
   for (int j = 0; j < M; ++j) {
     int own = -1;
-    for (int64_t x = ptr[j]; x < ptr[j + 1]; ++x) {
-      const int p = ord.part_of[fr[x] / FT];
+    tiles_of(j);
+    for (int32_t t : tiles) {
+      const int p = ord.part_of[t];
       if (p < 0) continue;
       if (own >= 0 && own != p) return rsba_set_error(RSBA_ERR_HIP, "internal: a point is seen on both sides of a separator");
       own = p;
@@ -72,5 +81,31 @@ extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t wor
     const int own = (int)(std::min_element(load.begin(), load.end()) - load.begin());
     owner[j] = own; load[own] += ptr[j + 1] - ptr[j];
   }
+  part_of = ord.part_of;
   return RSBA_OK;
 }
+
+}  // namespace
+
+extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t world, int32_t* owner, int32_t* num_top_tiles) {
+  std::vector<int32_t> part_of;
+  return partition(d, world, owner, num_top_tiles, part_of);
+}
+
+#ifdef RSBA_TEST_HOOKS
+// instrumented build only (not part of include/rsba_amd.h): the part of every tile column (-1 = a separator) of the cut
+// rsba_partition_points computes — real frames' tiles first, then the intrinsics blocks' pseudo frames'.  part_of == NULL: only
+// *num_tiles; otherwise part_of holds *num_tiles entries (the tile count of the problem; the caller asks for it first).
+extern "C" int32_t rsba_debug_partition_tiles(const rsba_problem_desc* d, int32_t world, int32_t* part_of, int32_t* num_tiles) {
+  if (!d || !num_tiles || d->num_points < 0 || (d->poses_per_frame != 1 && d->poses_per_frame != 2)) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad partition arguments");
+  const int CD = 6 * d->poses_per_frame, FT = kTile / CD;
+  const int NIB = d->calibrated ? 0 : d->num_intrinsics, NPF = d->calibrated ? 0 : (9 + CD - 1) / CD;
+  const int nt = (d->num_frames + NIB * NPF + FT - 1) / FT;
+  if (!part_of) { *num_tiles = nt; return RSBA_OK; }
+  if (*num_tiles != nt) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "num_tiles is not the problem's tile count");
+  std::vector<int32_t> owner((size_t)std::max(d->num_points, 1)), parts;
+  if (const int32_t rc = partition(d, world, owner.data(), nullptr, parts)) return rc;
+  std::copy(parts.begin(), parts.end(), part_of);
+  return RSBA_OK;
+}
+#endif

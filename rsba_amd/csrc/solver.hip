@@ -751,14 +751,21 @@ int32_t build_solver_impl(rsba_handle* h) {
   // part holds the pose, a free interFrameRatio has its column's forward solve run part by part — and SEVERAL intrinsics blocks (a 9-block
   // per frame, CeresHandler.h:256-264,273-280; round 6) need nothing of their own: a block's pseudo frames sit in a tile that is adjacent to the
   // tiles of exactly the frames seen through it, so the dissection puts it in those frames' part or in a separator, every point seen through
-  // the block is owned by that part's rank (rsba_partition_points builds the same graph), and the tile's replicated terms — damping, identity
-  // padding, the gradient after exchange (1) — follow frame_lead like any frame tile's.
+  // the block is owned by that part's rank (rsba_partition_points builds the same graph and follows the pseudo tiles too: the vote below
+  // checks both), and the tile's replicated terms — damping, identity padding, the gradient after exchange (1) — follow frame_lead like
+  // any frame tile's.
   std::vector<int32_t> cpart(nt, -1);
   bool sharded = want_parts && tord.parts_ok;
   if (const char* e = std::getenv("RSBA_SHARDED")) sharded = sharded && e[0] != '0';   // A/B switch
   if (want_parts) {
     double bad = sharded ? 0.0 : 1.0;
-    for (int64_t i = 0; i < N && bad == 0.0; ++i) { const int p = tord.part_of[of[i] / FT]; if (p >= 0 && p != h->rank) bad = 1.0; }
+    // an observation adds to its frame's tile and to the pseudo frames' tiles of the block its frame is seen through: every one of them
+    // must be this rank's or a separator (a point seen in separator frames only may still reach a block whose pseudo tile is in a part)
+    auto foreign = [&](int t) { const int p = tord.part_of[t]; return p >= 0 && p != h->rank; };
+    for (int64_t i = 0; i < N && bad == 0.0; ++i) {
+      if (foreign(of[i] / FT)) bad = 1.0;
+      for (int v = 0; v < NPF && NIB > 0; ++v) if (foreign((FR + intr_of(of[i]) * NPF + v) / FT)) bad = 1.0;
+    }
     if (local_fail) bad = 2.0;   // this rank cannot build its plan at all: every rank gives up together
     // every rank must take the same form: one all-reduce (max) of the verdicts — through the handle's cost slot (allocated with the
     // handle, rewritten by every evaluation): no allocation here that could fail on one rank and leave the others waiting

@@ -31,10 +31,11 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
     from rsba_amd.scene import make_config
     _, cfg, iters = mode.split(":")[:3]
     flags = mode.split(":")[3:]
-    if cfg.startswith("S"):   # "S<frames>": a scene of that many rolling-shutter frames, 70 points per frame
+    if cfg.startswith("S"):   # "S<frames>": a scene of that many rolling-shutter frames, 70 points per frame ("seed<k>": drawn with seed k, else 3)
         from rsba_amd.problem import apply_gauge_masks
         from rsba_amd.scene import make_scene
-        full = make_scene(int(cfg[1:]), 70 * int(cfg[1:]), seed=3).problem
+        seed = next((int(f[4:]) for f in flags if f.startswith("seed")), 3)
+        full = make_scene(int(cfg[1:]), 70 * int(cfg[1:]), seed=seed).problem
         apply_gauge_masks(full, fix_first_n_cameras=1)
         full.pose_fixed_mask[-1, -1] |= 0b111000
     else:
@@ -51,6 +52,10 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
             own = np.arange(full.num_frames) % 3 == 1
             full.frame_intrinsics = np.where(own, np.cumsum(own), 0).astype(np.int32)
             full.intrinsics = np.ascontiguousarray(full.intrinsics[: int(own.sum()) + 1])
+        run = next((int(f[7:]) for f in flags if f.startswith("runintr")), 0)
+        if run:                    # ... or "runintr<k>": one block for each run of k consecutive frames (a block's pseudo tile next to several frames' tiles)
+            full.frame_intrinsics = (np.arange(full.num_frames) // run).astype(np.int32)
+            full.intrinsics = np.ascontiguousarray(full.intrinsics[: int(full.frame_intrinsics.max()) + 1])
     if "priors" in flags:    # a motion prior between every two consecutive frames (CeresHandler.h:147-185), known interFrameRatio: each rank contributes the priors of its part
         full.prior_kind, full.prior_scale, full.inter_frame_ratio = 2, 25.0, 1.2
         full.prior_frames = np.arange(1, full.num_frames, dtype=np.int32)
@@ -68,8 +73,15 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
         os.environ["RSBA_DEVICE_LM_OFF_ON_THIS_RANK"] = "1"
     if "corrupt" in flags:   # the first persistent-driver solve loses an entry of its result (test hook of the library): every rank must notice through exchange (3)
         os.environ["RSBA_CHOL_TEST_CORRUPT"] = "1"
+    off_cut = None
     if "emptyrank" in flags:   # the last rank owns no point at all (a host that has fewer pieces of work than ranks): its kernels have nothing to do, its exchanges still pair up
         owner, ntop = capi.partition_points(full, world - 1)
+    elif "realowners" in flags:   # the caller's own owners, which follow the cut's real-frame tiles only (instrumented library: the cut from rsba_debug_partition_tiles) — some points
+        from helpers import owners_from_real_tiles, partition_tiles, points_off_the_cut   # reach a pseudo tile of another rank's part: the plan-time vote must send every rank to the replicated factorisation
+        part_of = partition_tiles(full, world)
+        ntop = int((part_of < 0).sum())
+        owner = owners_from_real_tiles(full, world, part_of)
+        off_cut = {"any": int(points_off_the_cut(full, owner, part_of).size), "pseudo": int(points_off_the_cut(full, owner, part_of, pseudo_only=True).size)}
     else:
         owner, ntop = capi.partition_points(full, world)
     shard = full.shard(rank, world, owner)
@@ -90,7 +102,7 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
     dp.close()
     if comm is not None:
         capi.rccl_comm_destroy(comm)
-    out = {"rank": rank, "transport": transport, "collective_calls": {k: v["calls"] for k, v in xs["collectives"].items()}, "world": world, "n_full": int(full.num_observations), "n_shard": int(shard.num_observations), "top_tile_columns": ntop,
+    out = {"rank": rank, "transport": transport, "collective_calls": {k: v["calls"] for k, v in xs["collectives"].items()}, "world": world, "n_full": int(full.num_observations), "n_shard": int(shard.num_observations), "top_tile_columns": ntop, "off_cut": off_cut,
            "final_cost": s.final_cost, "initial_cost": s.initial_cost, "iters": s.num_iterations, "dag_fallbacks": s.num_dag_fallbacks,
            "reduced": s.num_residual_blocks_reduced, "params": s.num_parameters_reduced, "costs": [t.cost for t in tr], "plan": st,
            "poses_sum": float(np.abs(shard.poses).sum()), "points_sum": float(np.abs(shard.points).sum()), "ratio": float(shard.inter_frame_ratio),

@@ -90,3 +90,71 @@ def read_result_file(path, prob):
     rest = raw[6 + npose + prob.points.size:]
     return dict(initial_cost=head[0], final_cost=head[1], iterations=int(head[2]), reduced=int(head[3]), termination=int(head[4]),
                 usable=bool(head[5]), poses=poses, points=points, covariance=rest[:108].reshape(3, 6, 6) if rest.size >= 108 else None)
+
+
+# ---- the cut of a sharded solve (rsba_partition_points) restated on the host ----
+
+HOOKS_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rsba_amd", "_lib", "librsba_amd_hooks.so")
+
+
+def partition_tiles(prob: BAProblem, world: int) -> np.ndarray:
+    """part_of[tile column] of the cut rsba_partition_points computes (-1 = a separator): rsba_debug_partition_tiles, which only the
+    instrumented library (-DRSBA_TEST_HOOKS) exports.  Host only."""
+    import ctypes as C
+
+    from rsba_amd import capi
+    L = C.CDLL(HOOKS_LIB)
+    d = capi.make_desc(prob)
+    nt = C.c_int32(0)
+    assert L.rsba_debug_partition_tiles(C.byref(d), C.c_int32(world), None, C.byref(nt)) == 0
+    part_of = np.full(nt.value, -2, dtype=np.int32)
+    rc = L.rsba_debug_partition_tiles(C.byref(d), C.c_int32(world), part_of.ctypes.data_as(C.c_void_p), C.byref(nt))
+    if rc != 0:
+        L.rsba_last_error.restype = C.c_char_p
+        raise capi.RsbaError(rc, L.rsba_last_error().decode())
+    return part_of
+
+
+def observation_tiles(prob: BAProblem):
+    """Per observation, the tile columns of the reduced camera system it adds to: its frame's tile (real, [N]) and the tiles of the
+    pseudo frames of the intrinsics block its frame is seen through (pseudo, [N, NPF]; NPF = 0 when calibrated).  A tile holds 48
+    unknowns: 4 two-pose frames or 8 one-pose frames; a 9-block of intrinsics takes ceil(9 / unknowns per frame) pseudo frames,
+    numbered behind the real frames block by block."""
+    CD = 6 * prob.poses_per_frame
+    FT, FR = 48 // CD, prob.num_frames
+    NIB = 0 if prob.calibrated else prob.num_intrinsics
+    NPF = 0 if prob.calibrated else (9 + CD - 1) // CD
+    fi = prob.frame_intrinsics if (NIB > 1 and prob.frame_intrinsics is not None) else np.zeros(FR, dtype=np.int32)
+    real = prob.obs_frame.astype(np.int64) // FT
+    pseudo = (FR + fi[prob.obs_frame].astype(np.int64)[:, None] * NPF + np.arange(NPF)[None, :]) // FT
+    nt = (FR + NIB * NPF + FT - 1) // FT
+    return real, pseudo, nt
+
+
+def points_off_the_cut(prob: BAProblem, owner: np.ndarray, part_of: np.ndarray, pseudo_only: bool = False) -> np.ndarray:
+    """The points that reach a tile of a part other than their owner's (separator tiles, -1, are everyone's) — through a real frame's
+    tile or an intrinsics block's pseudo tile (pseudo_only: through the pseudo tiles alone)."""
+    real, pseudo, _ = observation_tiles(prob)
+    own = np.asarray(owner)[prob.obs_point][:, None]
+    tiles = pseudo if pseudo_only else np.concatenate([real[:, None], pseudo], axis=1)
+    p = part_of[tiles]
+    off = ((p >= 0) & (p != own)).any(axis=1)
+    return np.unique(prob.obs_point[off])
+
+
+def owners_from_real_tiles(prob: BAProblem, world: int, part_of: np.ndarray) -> np.ndarray:
+    """An owner rule that looks at the real frames' tiles only (what rsba_partition_points did before it followed the pseudo tiles
+    too): a point goes to the part of its frames' tiles, points seen in separator frames only to whichever rank holds the fewest
+    observations so far, in point order."""
+    real, _, _ = observation_tiles(prob)
+    M = prob.num_points
+    p = part_of[real]
+    owner = np.full(M, -1, dtype=np.int32)
+    inpart = p >= 0
+    owner[prob.obs_point[inpart]] = p[inpart]
+    nobs = np.bincount(prob.obs_point, minlength=M)
+    load = np.bincount(owner[owner >= 0], weights=nobs[owner >= 0], minlength=world).astype(np.int64)
+    for j in np.flatnonzero(owner < 0):
+        r = int(np.argmin(load))
+        owner[j] = r; load[r] += nobs[j]
+    return owner

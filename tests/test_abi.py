@@ -37,6 +37,7 @@ def test_the_instrumented_library_is_the_same_abi_plus_its_counters(built_lib):
     for n in declared_functions():
         assert hasattr(hooks, n), n
     assert hasattr(hooks, "rsba_debug_chol_coherent") and not hasattr(built_lib, "rsba_debug_chol_coherent")
+    assert hasattr(hooks, "rsba_debug_partition_tiles") and not hasattr(built_lib, "rsba_debug_partition_tiles")
 
 
 def test_python_binding_lists_the_same_symbols():

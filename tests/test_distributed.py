@@ -10,6 +10,7 @@ import sys
 
 import numpy as np
 import pytest
+from helpers import owners_from_real_tiles, observation_tiles, partition_tiles, points_off_the_cut
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,8 +23,8 @@ def run_two_ranks(mode, outdir, world=2, timeout=900, env_extra=None):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
-    if any(flag in mode.split(":") for flag in ("hostrank", "corrupt")) or mode.startswith("planfail:"):
-        env["RSBA_AMD_LIB"] = HOOKS_LIB   # modes that inject a fault run on the instrumented library
+    if any(flag in mode.split(":") for flag in ("hostrank", "corrupt", "realowners")) or mode.startswith("planfail:"):
+        env["RSBA_AMD_LIB"] = HOOKS_LIB   # modes that inject a fault (or read the cut through its debug entry point) run on the instrumented library
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "tests", "dist_worker.py"), mode, str(outdir)],
                        capture_output=True, text=True, env=env, timeout=timeout)
@@ -254,26 +255,135 @@ def test_partition_points_on_graphs_that_are_not_a_plain_band(kind):
             assert ntop == base[world][1]
 
 
+def intrinsics_layout(p, kind):
+    """Intrinsics blocks of a scene: "calibrated" (none), "shared" (one block, a dense border), "perframe" (a 9-block per frame, CeresHandler.h:256-264,273-280),
+    "shuffled" (a block per frame, numbered in random order), "mixedintr" (every third frame its own block, the rest share block 0 — tests/dist_worker.py),
+    "run<k>" (a block shared by each run of k consecutive frames)."""
+    FR = p.num_frames
+    if kind == "calibrated":
+        return p
+    p.calibrated = False
+    if kind == "shared":
+        return p
+    if kind == "perframe":
+        fi = np.arange(FR)
+    elif kind == "shuffled":
+        fi = np.random.default_rng(1).permutation(FR)
+    elif kind == "mixedintr":
+        own = np.arange(FR) % 3 == 1
+        fi = np.where(own, np.cumsum(own), 0)
+    else:
+        assert kind.startswith("run")
+        fi = np.arange(FR) // int(kind[3:])
+    p.frame_intrinsics = fi.astype(np.int32)
+    p.intrinsics = np.tile(p.intrinsics[:1], (int(fi.max()) + 1, 1))
+    return p
+
+
+def check_cut(p, world, owner, ntop, balance=1.25, max_separator=None):
+    """The invariant a sharded factorisation rests on: every tile column of the reduced camera system a point adds to — its frames' tiles
+    and the pseudo tiles of the intrinsics blocks it is seen through — is a separator tile or a tile of its owner's part.  Then every
+    column of a part is complete on its rank and only the separators' tiles need to travel."""
+    part_of = partition_tiles(p, world)
+    _, _, nt = observation_tiles(p)
+    assert part_of.shape == (nt,) and part_of.min() >= -1 and part_of.max() == world - 1
+    assert set(part_of[part_of >= 0].tolist()) == set(range(world))              # every rank has a part
+    assert ntop == int((part_of < 0).sum())
+    assert ntop <= (max_separator or min(0.8, 0.1 + 0.12 * world)) * nt
+    assert owner.shape == (p.num_points,) and owner.min() >= 0 and owner.max() <= world - 1
+    off = points_off_the_cut(p, owner, part_of)
+    assert off.size == 0, f"{off.size} points reach a tile of another rank's part (first: {off[:5].tolist()})"
+    load = np.bincount(owner[p.obs_point], minlength=world)
+    assert load.min() > 0 and load.max() <= balance * load.mean()
+    return part_of
+
+
 def test_partition_points_with_an_intrinsics_block_per_frame():
     """A 9-block of intrinsics per frame (CeresHandler.h:256-264,273-280) adds pseudo frames to the reduced system — one per block behind the
     real frames, in tiles of their own: the cut takes them along (a block's tile is adjacent to the tiles of the frames seen through it, so it
-    lands in their part or in a separator) — every tile, real or pseudo, that more than one rank's points reach is a separator tile."""
+    lands in their part or in a separator), and every point follows the parts of ALL its tiles, real and pseudo."""
     from rsba_amd import capi
     from rsba_amd.scene import make_scene
-    p = make_scene(300, 21000, seed=3).problem
-    p.calibrated = False
-    p.intrinsics = np.tile(p.intrinsics[:1], (p.num_frames, 1))
-    p.frame_intrinsics = np.arange(p.num_frames, dtype=np.int32)
+    p = intrinsics_layout(make_scene(300, 21000, seed=3).problem, "perframe")
     FT, FR = 4, p.num_frames
     nt = (2 * FR + FT - 1) // FT          # two-pose frames: 12 unknowns per frame, one pseudo frame per intrinsics block
+    assert observation_tiles(p)[2] == nt
     for world in (2, 4):
         owner, ntop = capi.partition_points(p, world)
-        load = np.bincount(owner[p.obs_point], minlength=world)
+        part_of = check_cut(p, world, owner, ntop, max_separator=0.4)
         touched = np.zeros((world, nt), dtype=bool)
         touched[owner[p.obs_point], p.obs_frame // FT] = True
         touched[owner[p.obs_point], (FR + p.frame_intrinsics[p.obs_frame]) // FT] = True
-        assert load.min() > 0 and load.max() <= 1.25 * load.mean()
-        assert 0 < int((touched.sum(0) > 1).sum()) <= ntop <= 0.4 * nt
+        assert np.all(part_of[touched.sum(0) > 1] == -1) and (touched.sum(0) > 1).any()   # the columns several ranks add to are separators
+
+
+@pytest.mark.parametrize("rolling,kind,seeds,worlds", [
+    (True, "mixedintr", (3, 7, 8, 12), (2, 3, 4, 5, 8)),
+    (True, "perframe", (3, 8), (2, 3, 4, 5, 8)),
+    (True, "shuffled", (3, 8), (2, 3, 4)),
+    (True, "run2", (3, 8), (2, 3, 4, 5, 8)),
+    (True, "run5", (3, 8), (2, 3, 4, 5, 8)),
+    (True, "run8", (3, 8), (2, 3, 4, 5, 8)),
+    (True, "shared", (3,), (2, 3, 4, 5, 8)),
+    (True, "calibrated", (3,), (2, 3, 4, 5, 8)),
+    (False, "mixedintr", (3, 8), (2, 3, 4, 5, 8)),
+    (False, "perframe", (3, 8), (2, 3, 4, 5)),
+    (False, "run5", (3, 8), (2, 3, 4, 5)),
+    (False, "shared", (3,), (2, 3, 4, 5, 8)),
+])
+def test_partition_points_follows_the_pseudo_tiles_of_the_intrinsics_blocks(rolling, kind, seeds, worlds):
+    """Several intrinsics blocks: a point seen in separator frames only may be seen through a block whose pseudo tile lies inside a part.
+    Its owner must be that part's rank — otherwise its terms in the (pseudo, pseudo) and (pseudo, separator) tiles and the pseudo rows of the
+    rhs are added on a rank that never sends them, and the sharded reduced system is silently wrong.  The exact invariant over layouts that
+    place the blocks' pseudo tiles in every way: in frame order, shuffled, shared by runs of frames, mixed with a session block; one-pose
+    frames (8 to a tile, a block spans two pseudo frames: with an odd frame count those straddle tile boundaries)."""
+    from rsba_amd import capi
+    from rsba_amd.scene import make_scene
+    for seed in seeds:
+        p = intrinsics_layout(make_scene(300 if rolling else 301, 21000, seed=seed, rolling=rolling).problem, kind)
+        real, pseudo, nt = observation_tiles(p)
+        if not rolling and kind != "shared":
+            assert pseudo.shape[1] == 2 and (pseudo[:, 0] != pseudo[:, 1]).any()    # blocks whose two pseudo frames sit in two tiles
+        for world in worlds:
+            owner, ntop = capi.partition_points(p, world)
+            part_of = check_cut(p, world, owner, ntop, balance=1.6 if kind == "shuffled" else 1.25, max_separator=0.85 if kind == "shuffled" else None)
+            # (a rule that follows the real frames' tiles only gets those right: what it breaks, it breaks through a pseudo tile)
+            pre = owners_from_real_tiles(p, world, part_of)
+            assert np.array_equal(points_off_the_cut(p, pre, part_of), points_off_the_cut(p, pre, part_of, pseudo_only=True))
+
+
+def test_an_owner_rule_on_real_frames_only_breaks_the_cut_on_the_suites_scenes():
+    """The case above is not hypothetical: on the scene the GPU tests shard ("mixedintr", 300 frames), an owner rule that looks at the real
+    frames' tiles only hands points to a rank whose part does not hold the pseudo tile they reach (seed 3 on 5 ranks, seed 8 on 2, 3, 4
+    ranks) — the owners the GPU test of the plan-time vote passes.  rsba_partition_points's own owners never do."""
+    from rsba_amd import capi
+    from rsba_amd.scene import make_scene
+    for seed, worlds in ((3, (5,)), (8, (2, 3, 4))):
+        p = intrinsics_layout(make_scene(300, 21000, seed=seed).problem, "mixedintr")
+        for world in worlds:
+            part_of = partition_tiles(p, world)
+            pre = owners_from_real_tiles(p, world, part_of)
+            assert points_off_the_cut(p, pre, part_of).size >= 50
+            assert points_off_the_cut(p, capi.partition_points(p, world)[0], part_of).size == 0
+
+
+def test_debug_partition_tiles_checks_its_arguments():
+    """rsba_debug_partition_tiles (instrumented library only): the tile count first, then the parts — a buffer of another size is refused."""
+    import ctypes as C
+
+    from helpers import HOOKS_LIB
+    from rsba_amd import capi
+    from rsba_amd.scene import make_scene
+    p = intrinsics_layout(make_scene(40, 2000, seed=3).problem, "perframe")
+    L = C.CDLL(HOOKS_LIB)
+    d = capi.make_desc(p)
+    nt = C.c_int32(0)
+    assert L.rsba_debug_partition_tiles(C.byref(d), 2, None, C.byref(nt)) == 0 and nt.value == 20
+    buf = np.zeros(nt.value + 1, dtype=np.int32)
+    small = C.c_int32(nt.value - 1)
+    assert L.rsba_debug_partition_tiles(C.byref(d), 2, buf.ctypes.data_as(C.c_void_p), C.byref(small)) == 1   # RSBA_ERR_INVALID_ARGUMENT
+    assert not buf.any()
+    assert np.array_equal(partition_tiles(p, 1), np.zeros(20, dtype=np.int32))
 
 
 def test_partition_points_refuses_what_cannot_be_cut():
@@ -408,6 +518,31 @@ def test_per_frame_intrinsics_blocks_on_several_ranks(tmp_path, mode, world):
     a = check_nd(res, world)
     assert a["plan"]["exchange_doubles"] < a["ref_plan"]["exchange_doubles"]
     assert all(o["plan"]["device_loop_solves"] >= 1 for o in res)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,world", [("nd:S300:5:perframe:mixedintr:seed8", 2), ("nd:S300:5:perframe:mixedintr:seed8", 3), ("nd:S300:5:perframe:mixedintr:seed8", 4),
+                                        ("nd:S300:5:perframe:mixedintr:seed8:priors:freeratio", 3), ("nd:S300:5:perframe:runintr5", 3)])
+def test_points_seen_in_separator_frames_only_follow_the_pseudo_tiles_of_their_blocks(tmp_path, mode, world):
+    """Scenes where points seen in separator frames only are seen through a block whose pseudo tile lies inside a part (seed 8 of the mixed
+    layout: 153, 110, 172 such points on 2, 3, 4 ranks; blocks shared by runs of five frames): rsba_partition_points gives them to that part's
+    rank, so the sharded factorisation is still the single-GPU trajectory to 1e-9 — with owners that looked at the real frames only, the
+    (pseudo, pseudo) and (pseudo, separator) tiles lost those points' terms and the trajectory left the single-GPU one with no error."""
+    res = run_two_ranks(mode, tmp_path, world)
+    a = check_nd(res, world)
+    assert a["plan"]["exchange_doubles"] < a["ref_plan"]["exchange_doubles"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world", [2, 4])
+def test_owners_that_break_the_cut_through_a_pseudo_tile_send_every_rank_to_the_replicated_factorisation(tmp_path, world):
+    """A caller's own owners that follow the cut's real-frame tiles but not the pseudo tiles (tests/helpers.py: owners_from_real_tiles): some
+    points reach a pseudo tile of another rank's part and nothing else is wrong.  The plan-time vote checks the pseudo tiles of every
+    observation's block too: every rank takes the replicated factorisation, and the trajectory is the single-GPU one."""
+    res = run_two_ranks("nd:S300:5:perframe:mixedintr:seed8:realowners", tmp_path, world)
+    off = res[0]["off_cut"]
+    assert off["any"] > 0 and off["pseudo"] == off["any"]          # the owners break the cut through pseudo tiles only
+    check_nd(res, world, sharded=False)
 
 
 @pytest.mark.gpu
