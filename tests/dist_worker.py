@@ -1,6 +1,7 @@
 """Worker for tests/test_distributed.py, launched by torch.distributed.run with 2 ranks.
    python -m torch.distributed.run --nproc-per-node 2 ... tests/dist_worker.py <mode> <outdir>
 mode "cpu": host-side exchange logic over gloo, partial blocks from the oracle (no GPU needed)
+mode "step:...": one iteration of the sharded solve, the solved parameters written for a comparison with a host reference
 mode "gpu": the sharded on-device LM solve, both ranks on GPU 0, exchange staged through gloo ("gpu_priors": with motion priors,
 "gpu_free_ratio": with a free interFrameRatio, "gpu_pose_priors": with GoodPosePrior blocks)"""
 import json
@@ -23,14 +24,9 @@ def scene():
     return p
 
 
-def nd_mode(mode, outdir, rank, world, dist, torch):
-    """"nd:<config>:<iterations>[:huber]": a BASELINE configuration sharded along the top separators of the reduced system's elimination tree
-    (rsba_partition_points) — every rank factors its own part, the separators' tiles are what travels — against the single-GPU solve."""
-    from rsba_amd import capi
-    from rsba_amd.distributed import attach
+def nd_problem(cfg, flags):
+    """The whole problem of an "nd:" or "step:" mode (also built by the parent test, which compares with a host reference)."""
     from rsba_amd.scene import make_config
-    _, cfg, iters = mode.split(":")[:3]
-    flags = mode.split(":")[3:]
     if cfg.startswith("S"):   # "S<frames>": a scene of that many rolling-shutter frames, 70 points per frame ("seed<k>": drawn with seed k, else 3)
         from rsba_amd.problem import apply_gauge_masks
         from rsba_amd.scene import make_scene
@@ -69,6 +65,17 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
     if "spherical" in flags:   # the SphericalPrior of a session that starts at the origin (CeresHandler.h:36-50,127-130): ONE 2-residual block on the first pose of frame 1 — its terms go to the rank whose part holds that pose
         full.poses[0] = 0.0; full.poses[1] = 0.0; full.poses[1, :, 3:] += 1e-4
         full.spherical_pose_block = 2
+    return full
+
+
+def nd_mode(mode, outdir, rank, world, dist, torch):
+    """"nd:<config>:<iterations>[:huber]": a BASELINE configuration sharded along the top separators of the reduced system's elimination tree
+    (rsba_partition_points) — every rank factors its own part, the separators' tiles are what travels — against the single-GPU solve."""
+    from rsba_amd import capi
+    from rsba_amd.distributed import attach
+    _, cfg, iters = mode.split(":")[:3]
+    flags = mode.split(":")[3:]
+    full = nd_problem(cfg, flags)
     if "hostrank" in flags and rank == 1:   # ONE rank cannot run the loop without the host (test hook of the library; in the field: a rank without observations, or with phase timers on): ALL ranks must then take the host form — their collectives pair up or the solve hangs
         os.environ["RSBA_DEVICE_LM_OFF_ON_THIS_RANK"] = "1"
     if "corrupt" in flags:   # the first persistent-driver solve loses an entry of its result (test hook of the library): every rank must notice through exchange (3)
@@ -119,6 +126,33 @@ def nd_mode(mode, outdir, rank, world, dist, torch):
                    traj_err=float(max(abs(a.cost - b.cost) / b.cost for a, b in zip(tr, tr1))), ref_plan=st1, ref_ratio=float(ref.inter_frame_ratio),
                    prior_err=None if ref.pose_prior_values is None else float(np.abs(ref.pose_prior_values - shard.pose_prior_values).max()),
                    decisions_equal=bool(all(a.step_is_successful == b.step_is_successful for a, b in zip(tr, tr1))))
+    with open(os.path.join(outdir, f"rank{rank}.json"), "w") as f:
+        json.dump(out, f)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def step_mode(mode, outdir, rank, world, dist, torch):
+    """"step:<config>[:flags]": ONE iteration of the sharded solve (the problem of nd_problem, cut by rsba_partition_points); every rank
+    writes its solved parameters and the trace, so that the parent test can compare the step with the host reference."""
+    from lm_step_cases import ONE_STEP
+    from rsba_amd import capi
+    from rsba_amd.distributed import attach
+    cfg, flags = mode.split(":")[1], mode.split(":")[2:]
+    full = nd_problem(cfg, flags)
+    owner, _ = capi.partition_points(full, world)
+    shard = full.shard(rank, world, owner)
+    torch.cuda.set_device(0)
+    dp = capi.DeviceProblem(shard, device=0)
+    attach(dp)
+    s, tr = dp.solve(capi.default_options(**ONE_STEP))
+    st = dp.plan_stats()
+    dp.close()
+    np.savez(os.path.join(outdir, f"rank{rank}.npz"), poses=shard.poses, points=shard.points, intrinsics=shard.intrinsics,
+             owned=np.asarray(owner) == rank)
+    out = {"rank": rank, "iters": s.num_iterations, "sharded": st["sharded_factorisation"], "n_shard": int(shard.num_observations),
+           "trace": [dict(step_is_successful=t.step_is_successful, model_cost_change=t.model_cost_change, step_norm=t.step_norm,
+                          gradient_max_norm=t.gradient_max_norm) for t in tr]}
     with open(os.path.join(outdir, f"rank{rank}.json"), "w") as f:
         json.dump(out, f)
     dist.barrier()
@@ -214,6 +248,8 @@ def main():
     rank, world = dist.get_rank(), dist.get_world_size()
     if mode.startswith("nd:"):
         return nd_mode(mode, outdir, rank, world, dist, torch)
+    if mode.startswith("step:"):
+        return step_mode(mode, outdir, rank, world, dist, torch)
     if mode == "mock_timeout":
         return mock_timeout_mode(outdir, rank, world, dist, torch)
     if mode.startswith("planfail:"):

@@ -616,3 +616,40 @@ def test_a_rank_that_never_arrives_is_reported_not_waited_for_forever(tmp_path):
     assert a["sum_ok"] and b["sum_ok"] and a["max_ok"] and b["max_ok"]
     assert a["enqueue_s"] < 0.25 and 0.4 <= a["gave_up_after_s"] < 10.0
     assert a["destroy"] == 2 and b["destroy"] == 0      # ncclSystemError on the rank that waited; nothing to report on the one that never called
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,world", [("step:S300:perframe:mixedintr:seed8", 2), ("step:S300:perframe:mixedintr:seed8", 4),
+                                        ("step:S300:perframe:runintr5", 2), ("step:S300:perframe:runintr5", 4), ("step:C2:intr", 2), ("step:C2:intr", 4)])
+def test_sharded_step_matches_the_host_reference(tmp_path, oracle, mode, world):
+    """One iteration of the sharded solve against the host reference of the whole problem (tests/lm_step_reference.py), per parameter
+    block with the tolerance of tests/test_gpu_lm_step.py: points seen in separator frames only (seed 8 of the mixed layout), blocks
+    shared by runs of five frames whose pseudo tiles sit next to a separator, shared intrinsics with Huber.  A point owned by the wrong
+    rank leaves the sharded system without its terms: its own step and its frames' steps leave the reference."""
+    import lm_step_reference as R
+    from dist_worker import nd_problem
+    from test_lm_step_reference import C_TOL
+    res = run_two_ranks(mode, tmp_path, world)
+    full = nd_problem(mode.split(":")[1], mode.split(":")[2:])
+    r, J, ok = oracle.evaluate_blocks(full)
+    assert ok.all()
+    ref = R.lm_step(full, r, J)
+    assert ref.kappa <= 1e9
+    a = res[0]
+    assert a["sharded"] == 1 and len(a["trace"]) == 2 and a["trace"][1]["step_is_successful"] == 1
+    for o in res[1:]:
+        assert o["trace"] == a["trace"]                                 # every rank took the same step
+    got = np.load(os.path.join(tmp_path, "rank0.npz"))
+    ratio, where = R.step_ratio(full, ref, got["poses"], got["points"], got["intrinsics"])
+    print(f"{mode} on {world} ranks: step ratio {ratio:.3f} at {where}, kappa {ref.kappa:.2e}")
+    assert ratio <= C_TOL, (ratio, where)
+    for k in range(1, world):                                           # the other ranks hold the same cameras and their own points
+        other = np.load(os.path.join(tmp_path, f"rank{k}.npz"))
+        assert np.array_equal(other["poses"], got["poses"]) and np.array_equal(other["intrinsics"], got["intrinsics"])
+        own = other["owned"]
+        assert np.array_equal(other["points"][own], got["points"][own])
+    t = a["trace"]
+    assert abs(t[1]["model_cost_change"] - ref.model_cost_change) <= 1e-12 * ref.model_cost_change
+    nrm, allowed = R.step_norm_bound(full, ref, C_TOL)
+    assert abs(t[1]["step_norm"] - nrm) <= allowed
+    assert abs(t[0]["gradient_max_norm"] - ref.gradient_max_norm) <= 1e-12 * ref.gradient_max_norm
