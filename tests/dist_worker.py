@@ -149,7 +149,8 @@ def step_mode(mode, outdir, rank, world, dist, torch):
     st = dp.plan_stats()
     dp.close()
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), poses=shard.poses, points=shard.points, intrinsics=shard.intrinsics,
-             owned=np.asarray(owner) == rank)
+             owned=np.asarray(owner) == rank, ratio=np.array([shard.inter_frame_ratio]),
+             pose_priors=np.zeros((0, 6)) if shard.pose_prior_values is None else shard.pose_prior_values)
     out = {"rank": rank, "iters": s.num_iterations, "sharded": st["sharded_factorisation"], "n_shard": int(shard.num_observations),
            "trace": [dict(step_is_successful=t.step_is_successful, model_cost_change=t.model_cost_change, step_norm=t.step_norm,
                           gradient_max_norm=t.gradient_max_norm) for t in tr]}

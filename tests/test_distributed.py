@@ -620,12 +620,17 @@ def test_a_rank_that_never_arrives_is_reported_not_waited_for_forever(tmp_path):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,world", [("step:S300:perframe:mixedintr:seed8", 2), ("step:S300:perframe:mixedintr:seed8", 4),
-                                        ("step:S300:perframe:runintr5", 2), ("step:S300:perframe:runintr5", 4), ("step:C2:intr", 2), ("step:C2:intr", 4)])
+                                        ("step:S300:perframe:runintr5", 2), ("step:S300:perframe:runintr5", 4), ("step:C2:intr", 2), ("step:C2:intr", 4),
+                                        ("step:S300:priors", 2), ("step:S300:priors", 4), ("step:S300:priors:freeratio", 2), ("step:S300:priors:freeratio", 4),
+                                        ("step:S300:posepriors", 2), ("step:S300:posepriors", 4), ("step:S300:spherical", 2), ("step:S300:spherical", 4),
+                                        ("step:S300:perframe:mixedintr:seed8:priors", 2), ("step:S300:perframe:mixedintr:seed8:priors", 4)])
 def test_sharded_step_matches_the_host_reference(tmp_path, oracle, mode, world):
     """One iteration of the sharded solve against the host reference of the whole problem (tests/lm_step_reference.py), per parameter
     block with the tolerance of tests/test_gpu_lm_step.py: points seen in separator frames only (seed 8 of the mixed layout), blocks
-    shared by runs of five frames whose pseudo tiles sit next to a separator, shared intrinsics with Huber.  A point owned by the wrong
-    rank leaves the sharded system without its terms: its own step and its frames' steps leave the reference."""
+    shared by runs of five frames whose pseudo tiles sit next to a separator, shared intrinsics with Huber; motion priors whose
+    (f, f - 1) blocks cross separators (also next to pseudo tiles), a free ratio whose border column is solved part by part,
+    GoodPosePrior blocks, the SphericalPrior.  A point owned by the wrong rank leaves the sharded system without its terms: its own
+    step and its frames' steps leave the reference."""
     import lm_step_reference as R
     from dist_worker import nd_problem
     from test_lm_step_reference import C_TOL
@@ -640,12 +645,14 @@ def test_sharded_step_matches_the_host_reference(tmp_path, oracle, mode, world):
     for o in res[1:]:
         assert o["trace"] == a["trace"]                                 # every rank took the same step
     got = np.load(os.path.join(tmp_path, "rank0.npz"))
-    ratio, where = R.step_ratio(full, ref, got["poses"], got["points"], got["intrinsics"])
+    ratio, where = R.step_ratio(full, ref, got["poses"], got["points"], got["intrinsics"], float(got["ratio"][0]),
+                                None if full.pose_prior_values is None else got["pose_priors"])
     print(f"{mode} on {world} ranks: step ratio {ratio:.3f} at {where}, kappa {ref.kappa:.2e}")
     assert ratio <= C_TOL, (ratio, where)
     for k in range(1, world):                                           # the other ranks hold the same cameras and their own points
         other = np.load(os.path.join(tmp_path, f"rank{k}.npz"))
         assert np.array_equal(other["poses"], got["poses"]) and np.array_equal(other["intrinsics"], got["intrinsics"])
+        assert np.array_equal(other["ratio"], got["ratio"]) and np.array_equal(other["pose_priors"], got["pose_priors"])
         own = other["owned"]
         assert np.array_equal(other["points"][own], got["points"][own])
     t = a["trace"]

@@ -10,6 +10,15 @@ Largest error / (kappa eps |delta_ref|_inf) measured on an MI355X, per family: f
 oracle reaches 18 on the same scenes; C_TOL = 64 covers both, and tests/test_lm_step_reference.py shows that a 1e-9 error in one
 48 x 48 tile still exceeds it.
 
+With prior blocks (lm_step_cases.PRIOR_CASES, kappa 5e2 - 1.1e5), per family: motion priors at a constant ratio (both kinds, the
+velocity prior's ratio <= eps branch) 0.26, free ratio 0.023 (projected onto its bound: 0.004), Huber on the priors 0.15, priors
+on some frames / next to constant frames 0.065, (f, f - 1) blocks across tile edges 0.47, GoodPosePrior blocks 0.17, the
+SphericalPrior 3.5 (rs_spherical; with other priors 1.04), one-pose frames in a two-pose session 0.086, intrinsics blocks with
+priors 0.54; every knob on the two prior shapes 2.1 (RSBA_FACTORED=0, rs_spherical_pp).  Sharded on 2 and 4 ranks: motion
+priors 0.041, free ratio 0.051, GoodPosePriors 0.084, SphericalPrior 0.18, priors beside per-frame / shared intrinsics 1.01.
+tests/test_lm_step_reference.py shows that a missing (f, f - 1) prior coupling (5e7x), a 1e-9 error in the ratio's border column
+(2x - 290x) and a priorPoses elimination without its LM diagonal (480x - 4300x) exceed the tolerance.
+
 C4's first step is not here: the host reference of its 312 000 unknowns (the reduced system assembled with scipy.sparse, factored
 densely, refined against the whole system) took 162 s on a development host, over a budget of about two minutes."""
 import numpy as np
@@ -39,7 +48,7 @@ def check_step(capi, oracle, p, opts, *, solver="lu"):
     with capi.DeviceProblem(q) as dp:
         s, tr = dp.solve(capi.default_options(**opts))
     assert len(tr) == 2 and tr[1].step_is_valid == 1 and tr[1].step_is_successful == 1   # a precondition of the case: the step was applied
-    ratio, where = R.step_ratio(p, ref, q.poses, q.points, q.intrinsics)
+    ratio, where = R.step_ratio(p, ref, *R.solved_blocks(q))
     assert ratio <= C_TOL, (ratio, where, ref.kappa)
     assert abs(tr[1].model_cost_change - ref.model_cost_change) <= 1e-12 * ref.model_cost_change, (tr[1].model_cost_change, ref.model_cost_change)
     nrm, allowed = R.step_norm_bound(p, ref, C_TOL)
@@ -49,7 +58,7 @@ def check_step(capi, oracle, p, opts, *, solver="lu"):
     return ratio
 
 
-@pytest.mark.parametrize("name", LC.CASES)
+@pytest.mark.parametrize("name", LC.CASES + LC.PRIOR_CASES)
 def test_device_step_matches_the_reference(capi, oracle, name):
     p, opts = LC.case(name)
     check_step(capi, oracle, p, opts)
@@ -64,11 +73,12 @@ def _knob_id(k):
     return "+".join(k) if "=" in k[0] else f"{k[0]}={k[1]}"
 
 
-@pytest.mark.parametrize("name", ["rs_far_pair", "gs_intr_run3", "rs_nt25"])
+@pytest.mark.parametrize("name", ["rs_far_pair", "gs_intr_run3", "rs_nt25", "rs_free_huber", "rs_spherical_pp"])
 @pytest.mark.parametrize("knob", KNOBS, ids=_knob_id)
 def test_plan_and_kernel_knobs_keep_the_step(capi, oracle, monkeypatch, knob, name):
-    """Every plan / kernel knob on three shapes: five tiles with a far pair, per-run intrinsics blocks (pseudo tiles) beside a
-    partial last tile, and 25 tiles (more than a leaf)."""
+    """Every plan / kernel knob on five shapes: five tiles with a far pair, per-run intrinsics blocks (pseudo tiles) beside a
+    partial last tile, 25 tiles (more than a leaf), motion priors with a free ratio and Huber, GoodPosePriors with the
+    SphericalPrior."""
     for kv in (knob if "=" in knob[0] else ["=".join(knob)]):
         k, v = kv.split("=")
         monkeypatch.setenv(k, v)

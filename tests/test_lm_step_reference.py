@@ -4,9 +4,16 @@ tests/test_gpu_lm_step.py puts on the device step would see a one-tile error of 
 The oracle solves by Schur elimination and an envelope Cholesky of the reduced system; the reference by a dense (or sparse LU)
 factorisation of the whole damped system refined in long double.  They share no code, so agreement to a few kappa * eps on every
 scene shape of tests/lm_step_cases.py checks both.  Measured here: error / (kappa eps |delta|_inf) <= 18 (the intrinsics scenes;
-below 3 elsewhere), the model cost change to <= 1e-13 relative."""
+below 3 elsewhere), the model cost change to <= 1e-13 relative.  With prior blocks (lm_step_cases.PRIOR_CASES): <= 7.7 (motion
+priors beside shared intrinsics), below 1.6 elsewhere; the sharded modes' problems (tests/test_distributed.py) <= 15.
+
+The prior blocks' closed forms are checked against mpmath (50 digits, central differences), and three errors a device could make
+in them are shown to exceed the device tolerance: one prior's (f, f - 1) coupling missing from the reduced system, a 1e-9 error in
+the free ratio's border column, and the priorPoses elimination without the block's LM diagonal."""
 import numpy as np
 import pytest
+
+import mpmath
 
 import lm_step_cases as LC
 import lm_step_reference as R
@@ -29,7 +36,7 @@ def test_huber_rho_matches_the_goldens():
         assert np.allclose([v[0] for v in rho], c["rho"], rtol=1e-15, atol=0.0), c
 
 
-@pytest.mark.parametrize("name", LC.CASES)
+@pytest.mark.parametrize("name", LC.CASES + LC.PRIOR_CASES)
 def test_reference_step_matches_the_oracles_first_step(oracle, name):
     p, opts, ref = reference(oracle, name)
     assert ref.kappa <= 1e9, ref.kappa
@@ -37,7 +44,8 @@ def test_reference_step_matches_the_oracles_first_step(oracle, name):
     q = p.copy()
     s, tr = oracle.solve(q, oracle.default_options(**opts))
     assert len(tr) == 2 and tr[1].step_is_successful == 1         # a precondition of the case: the step is applied
-    ratio, where = R.step_ratio(p, ref, q.poses, q.points, q.intrinsics)
+    ratio, where = R.step_ratio(p, ref, *R.solved_blocks(q))
+    print(f"{name}: step ratio {ratio:.3f} at {where}, kappa {ref.kappa:.2e}")
     assert ratio <= C_TOL, (ratio, where, ref.kappa)
     assert abs(tr[1].model_cost_change - ref.model_cost_change) <= 1e-12 * ref.model_cost_change
     nrm, allowed = R.step_norm_bound(p, ref, C_TOL)
@@ -98,3 +106,195 @@ def test_the_tolerance_sees_a_one_tile_error(oracle, name):
     dS[np.ix_(a, b)] = smallest          # S = U - sum_j W_j V_j^-1 W_j^T: dropping point j's term adds it back
     dS[np.ix_(b, a)] = smallest.T
     assert moved(dS) > 10 * tol, (moved(dS), tol)
+
+
+def test_the_bound_case_projects_the_ratio(oracle):
+    """rs_vel_free_bound: the model step takes the ratio below 0; the candidate sits on the bound, step_norm counts the projected
+    move, model_cost_change the model step."""
+    p, _, ref = reference(oracle, "rs_vel_free_bound")
+    x0 = p.inter_frame_ratio
+    assert x0 + ref.ratio[0] < 0.0 and ref.apply(p)["ratio"][0] == 0.0
+    d = ref.delta()
+    d[R.layout(p)["iratio"]] = -x0                                        # the projected move of the ratio
+    assert abs(ref.step_norm - np.linalg.norm(d)) <= 1e-14 * ref.step_norm
+    assert abs(ref.step_norm - np.linalg.norm(ref.delta())) > 1e-3 * ref.step_norm
+
+
+def test_one_pose_frames_keep_their_second_slot_out_of_the_system():
+    """frame_global: the second slot of a one-pose frame is data — no Jacobian entry refers to it and it is not an unknown."""
+    p, _ = LC.case("rs_scanline_priors")
+    gcol, ncam, nparam, fixed = R.columns(p)
+    glob = np.flatnonzero(p.frame_global)
+    slot2 = (glob[:, None] * 12 + 6 + np.arange(6)[None, :]).reshape(-1)
+    assert len(glob) == 3 and fixed[slot2].all()
+    assert not np.isin(gcol, slot2).any()
+    for _, _, g, _ in R.prior_blocks(p):
+        assert not np.isin(g, slot2).any()
+    q = p.copy(); q.pose_fixed_mask[glob, 1] = 0                        # even without the caller's mask
+    assert R.columns(q)[3][slot2].all()
+
+
+# ---- the prior blocks' closed forms against mpmath ------------------------------------------------------------------------------
+
+mp = mpmath.mp
+
+
+def _mp_motion(kind, scale, t, a, b, c, d):
+    """The motion priors from their meaning, in mpmath: the frame's first pose against the previous frame's last pose moved on
+    over the gap (gap = ratio x exposure), the frame's last pose against its first pose moved on over the exposure — at the previous
+    velocity (kind 1; its second half at the previous frame's velocity when ratio <= eps) or at the mean of the previous and the
+    current one (kind 2); rotation rows x 0.01, all x scale."""
+    out = []
+    for half in (0, 1):
+        for i in range(6):
+            if kind == 1 and half == 0:
+                v = a[i] - (d[i] + t * (d[i] - c[i]))
+            elif kind == 1:
+                v = b[i] - (a[i] + ((a[i] - d[i]) / t if t > R.DBL_EPSILON else (d[i] - c[i])))
+            elif half == 0:
+                prev, now = t * (d[i] - c[i]), a[i] - d[i]
+                v = a[i] - (d[i] + prev + (now - prev) / 2)
+            else:
+                prev, now = (a[i] - d[i]) / t, b[i] - a[i]
+                v = b[i] - (a[i] + prev + (now - prev) / 2)
+            out.append(v * scale * (mpmath.mpf("0.01") if i < 3 else 1))
+    return out
+
+
+def _mp_jacobian(fun, x, h=mpmath.mpf("1e-25")):
+    cols = []
+    for k in range(len(x)):
+        xp, xm = list(x), list(x)
+        xp[k] += h; xm[k] -= h
+        cols.append([(u - v) / (2 * h) for u, v in zip(fun(xp), fun(xm))])
+    return [[cols[k][i] for k in range(len(x))] for i in range(len(cols[0]))]
+
+
+def _close(got, want, rtol):
+    got = np.asarray(got, dtype=np.longdouble).astype(np.float64)
+    want = np.array([[float(v) for v in row] for row in want]) if isinstance(want[0], list) else np.array([float(v) for v in want])
+    scale = max(float(np.max(np.abs(want))), 1e-300)
+    assert np.max(np.abs(got - want)) <= rtol * scale, (np.max(np.abs(got - want)) / scale)
+
+
+@pytest.mark.parametrize("kind,t", [(1, 0.8), (1, 2.5), (1, 0.0), (1, 1e-17), (1, 3e-16), (2, 0.8), (2, 1.25), (2, 1e-3)])
+def test_motion_prior_jacobians_against_mpmath(kind, t):
+    rng = np.random.default_rng(7)
+    a, b, c, d = rng.normal(size=(4, 6))
+    scale = 7.0
+    with mp.workdps(50):
+        x = [mpmath.mpf(float(v)) for v in np.concatenate([a, b, c, d, [t]])]
+        fun = lambda x: _mp_motion(kind, scale, x[24], x[0:6], x[6:12], x[12:18], x[18:24])   # noqa: E731
+        r_mp, J_mp = fun(x), _mp_jacobian(fun, x)
+    r, J = R.motion_prior_jacobian(kind, scale, t, a, b, c, d)
+    _close(r[0], r_mp, 1e-17)
+    _close(J[0], J_mp, 1e-17)
+    if kind == 1 and t <= R.DBL_EPSILON:                       # the second half does not depend on the ratio there
+        assert np.all(J[0, 6:, 24] == 0)
+
+
+def test_pose_prior_jacobians_against_mpmath():
+    rng = np.random.default_rng(8)
+    prior, pose = rng.normal(size=(2, 6)) * 0.1
+    with mp.workdps(50):
+        x = [mpmath.mpf(float(v)) for v in np.concatenate([prior, pose])]
+        W = [3, 3, 3, 5, 5, 5]
+        fun = lambda x: [W[i] * (x[i] - x[6 + i]) for i in range(6)]   # noqa: E731
+        r_mp, J_mp = fun(x), _mp_jacobian(fun, x)
+    r, J = R.good_pose_prior(3.0, 5.0, prior, pose)
+    _close(r[0], r_mp, 1e-17)
+    _close(J[0], J_mp, 1e-17)
+
+
+@pytest.mark.parametrize("signs", [(1, 1, 1), (-1, 1, -1), (1, -1, -1)])
+def test_spherical_prior_jacobians_against_mpmath(signs):
+    pose = np.array([0.1, -0.2, 0.05, 1e-4, 2e-4, 3e-4]) * np.array([1, 1, 1, *signs])
+    with mp.workdps(60):
+        x = [mpmath.mpf(float(v)) for v in pose]
+        fun = lambda x: [x[0] ** 2 + x[1] ** 2 + x[2] ** 2, mpmath.mpf(10) ** 20 * (1 - abs(x[3]) - abs(x[4]) - abs(x[5]))]   # noqa: E731
+        r_mp, J_mp = fun(x), _mp_jacobian(fun, x, h=mpmath.mpf("1e-30"))
+    r, J = R.spherical_prior(pose)
+    _close(r[0], r_mp, 1e-17)
+    _close(J[0][0], J_mp[0], 1e-17)
+    _close(J[0][1], J_mp[1], 1e-17)
+
+
+# ---- sensitivity: errors in the prior terms that the device tolerance must see ----------------------------------------------------
+
+def _moved(oracle, p, opts, ref, edit):
+    """|delta' - delta|_inf when the reference's scaled, damped matrix is edited, and the device tolerance."""
+    r, J, ok = oracle.evaluate_blocks(p)
+    other = R.lm_step(p, r, J, want_kappa=False, edit=edit, **{k: opts[k] for k in ("initial_trust_region_radius",) if k in opts})
+    tol = C_TOL * ref.kappa * R.EPS * R.delta_inf(ref)
+    return float(np.max(np.abs(other.delta() - ref.delta()))), tol
+
+
+@pytest.mark.parametrize("name,f", [("rs_acc_r1.25", 4), ("rs_acc_r1.25", 5), ("rs_free_huber", 8)])
+def test_the_tolerance_sees_a_missing_prior_coupling(oracle, name, f):
+    """Prior f's share of the (f, f - 1) block of the reduced system left out (f = FT: the block crosses a tile edge)."""
+    p, opts, ref = reference(oracle, name)
+    k = int(np.flatnonzero(p.prior_frames == f)[0])
+    rp, Jp, g, _ = R.prior_blocks(p)[0]
+    _, Jc = R.corrected(float(p.huber_a), rp.astype(np.float64)[k:k + 1], Jp.astype(np.float64)[k:k + 1])
+
+    def edit(H, free, scale):
+        pos = {int(c): i for i, c in enumerate(free)}
+        H = H.tolil()
+        for a in range(12):                       # columns of frame f
+            for b in range(12, 24):               # columns of frame f - 1
+                ia, ib = pos.get(int(g[k, a])), pos.get(int(g[k, b]))
+                if ia is None or ib is None:
+                    continue
+                v = np.longdouble(scale[ia] * scale[ib] * float(Jc[0, :, a] @ Jc[0, :, b]))
+                H[ia, ib] -= v
+                H[ib, ia] -= v
+        return H.tocsr()
+    moved, tol = _moved(oracle, p, opts, ref, edit)
+    print(f"{name} prior {f}: moved {moved:.3e}, tolerance {tol:.3e}, ratio {moved / tol:.3g}")
+    assert moved > 10 * tol, (moved, tol)
+
+
+@pytest.mark.parametrize("name", ["rs_vel_free", "rs_acc_free", "rs_free_huber"])
+def test_the_tolerance_sees_a_ratio_border_error(oracle, name):
+    """A 1e-9 relative error in the free ratio's border column of the system (every off-diagonal entry).  (Measured: 2x - 290x the
+    tolerance.  It is the least sharp of these checks: on the 7-tile rs_prior_nt the same error moves delta by 0.9x the tolerance.)"""
+    p, opts, ref = reference(oracle, name)
+    ir = int(np.flatnonzero(ref.free == R.layout(p)["iratio"])[0])
+
+    def edit(H, free, scale):
+        H = H.tolil()
+        row = H.getrow(ir)
+        for j, v in zip(row.indices, row.data):
+            if j != ir:
+                H[ir, j] = v * np.longdouble(1 + 1e-9)
+                H[j, ir] = H[ir, j]
+        return H.tocsr()
+    moved, tol = _moved(oracle, p, opts, ref, edit)
+    print(f"{name} ratio border: moved {moved:.3e}, tolerance {tol:.3e}, ratio {moved / tol:.3g}")
+    assert moved > tol, (moved, tol)
+
+
+@pytest.mark.parametrize("name", ["rs_pp_all", "gs_pp_some", "rs_spherical_all"])
+def test_the_tolerance_sees_a_prior_pose_elimination_without_its_diagonal(oracle, name):
+    """The device eliminates each priorPoses coordinate in closed form: S_xx -= c^2 / V0' with V0' = V0 + D0 its damped diagonal.
+    With c^2 / V0 instead (no LM diagonal), S_xx changes by c^2 / V0' - c^2 / V0: that changed S, the same back-substitution."""
+    p, opts, ref = reference(oracle, name)
+    L = R.layout(p)
+    radius = opts.get("initial_trust_region_radius", 1e4)
+
+    def edit(H, free, scale):
+        H = H.tolil()
+        for i in np.flatnonzero((free >= L["ipp"]) & (free < L["ipp"] + 6 * len(p.pose_prior_block))):
+            row = H.getrow(i)
+            tied = [j for j in row.indices if j != i]               # the pose coordinate it is tied to (W is diagonal), if that is free
+            if not tied:
+                continue
+            (x,) = tied
+            Vd = H[i, i]
+            V0 = Vd / (1 + np.longdouble(1.0) / np.longdouble(radius))   # (V0 is inside [1e-6, 1e32]: D0 = V0 / radius)
+            c = H[i, x]
+            H[x, x] += c * c / Vd - c * c / V0
+        return H.tocsr()
+    moved, tol = _moved(oracle, p, opts, ref, edit)
+    print(f"{name} priorPoses without D0: moved {moved:.3e}, tolerance {tol:.3e}, ratio {moved / tol:.3g}")
+    assert moved > 10 * tol, (moved, tol)
