@@ -6,7 +6,8 @@
 // Not built (out-of-scope costs): the structure-less ray costs — reaching them throws std::runtime_error.  The per-pose priors
 // (SphericalPrior :127-130, GoodPosePrior :188-204) and the motion priors (:147-186) are built, the latter with a known
 // opt.ceres.interFrameRatio (!= 1: constant block) and with the free, lower-bounded ratio of the default.  opt.debug.calcCovariances (VideoSfMHandler.cc:599-621) is built.  revalidateReprojections (:239-243) runs as one
-// batched device validation per frame (video_sfm.hpp).
+// batched device validation per frame (video_sfm.hpp).  BA / fullBA / windowedBA(..., reproject) run createTracks after the
+// solve (create_tracks.hpp).
 #pragma once
 #include <cmath>
 #include <iomanip>
@@ -15,6 +16,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "create_tracks.hpp"
 #include "motion_priors.hpp"
 #include "pose_priors.hpp"
 #include "reprojection_costs.hpp"
@@ -212,9 +214,12 @@ class CeresHandler {
 
 // VideoSfMHandler::BA (VideoSfMHandler.cc:574-631) without the service bookkeeping: options as :579-583,
 // Add frames [startFrame, endFrame], solve, print the report and the "average reprojection error"
-// sqrt(final_cost / num_residual_blocks_reduced) (:627-628), return IsSolutionUsable() (:630).
+// sqrt(final_cost / num_residual_blocks_reduced) (:627-628), return IsSolutionUsable() (:630).  With `reproject`, createTracks
+// runs on every frame of the window after the solve (:600), as one batched call (create_tracks.hpp; neither it nor the
+// covariances read what the other writes, so running it after them changes nothing).
 inline bool BA(Session& sess, const int32_t startFrame, const int32_t endFrame, const SfmOptions& opt, const int32_t maxIter,
-               ceres::Solver::Summary* out = nullptr, bool progress = true, std::vector<std::vector<double>>* covariances = nullptr) {
+               ceres::Solver::Summary* out = nullptr, bool progress = true, std::vector<std::vector<double>>* covariances = nullptr,
+               bool reproject = false) {
   ceres::Solver::Options cOpt;
   cOpt.linear_solver_type = ceres::SPARSE_SCHUR;
   cOpt.minimizer_progress_to_stdout = progress;
@@ -251,6 +256,7 @@ inline bool BA(Session& sess, const int32_t startFrame, const int32_t endFrame, 
       }
     }
   }
+  if (reproject && startFrame <= endFrame) createTracks(sess, (size_t)startFrame, (size_t)endFrame, opt);
   if (progress)
     std::cout << "average reprojection error: " << std::sqrt(summary.final_cost / summary.num_residual_blocks_reduced) << std::endl;
   if (out) *out = summary;
@@ -270,24 +276,25 @@ inline void relax_valid_matches_rule(const Session& sess, SfmOptions& opt) {
 }  // namespace detail
 
 // VideoSfMHandler::fullBA (VideoSfMHandler.cc:153-180) without the RPC arguments and the PLY dump: every frame of the session, the
-// options as configured except for the valid-matches rule above.  (`reproject` — createTracks after the solve — is the caller's.)
+// options as configured except for the valid-matches rule above.  `reproject`: createTracks on every frame after the solve.
 inline bool fullBA(Session& sess, const SfmOptions& options, const int32_t maxIter, ceres::Solver::Summary* out = nullptr, bool progress = true,
-                   std::vector<std::vector<double>>* covariances = nullptr) {
+                   std::vector<std::vector<double>>* covariances = nullptr, bool reproject = false) {
   SfmOptions opt = options;
   detail::relax_valid_matches_rule(sess, opt);
-  return BA(sess, 0, (int32_t)sess.frames.size() - 1, opt, maxIter, out, progress, covariances);
+  return BA(sess, 0, (int32_t)sess.frames.size() - 1, opt, maxIter, out, progress, covariances, reproject);
 }
 
 // VideoSfMHandler::windowedBA (VideoSfMHandler.cc:185-214): frames [startFrame, endFrame], the poses before the window stay as they
 // are; fixScale is switched off (:195 — the window is anchored by the frozen tracks) and the valid-matches rule counts the tracks of
 // the whole session, as the reference does (:199 "TODO check tracks within window?").
 inline bool windowedBA(Session& sess, const SfmOptions& options, const int32_t startFrame, const int32_t endFrame, const int32_t maxIter,
-                       ceres::Solver::Summary* out = nullptr, bool progress = true, std::vector<std::vector<double>>* covariances = nullptr) {
+                       ceres::Solver::Summary* out = nullptr, bool progress = true, std::vector<std::vector<double>>* covariances = nullptr,
+                       bool reproject = false) {
   if (endFrame >= (int32_t)sess.frames.size()) throw std::out_of_range("windowedBA: endFrame");   // CHECK_LT (:192)
   SfmOptions opt = options;
   opt.ceres.fixScale = false;
   detail::relax_valid_matches_rule(sess, opt);
-  return BA(sess, startFrame, endFrame, opt, maxIter, out, progress, covariances);
+  return BA(sess, startFrame, endFrame, opt, maxIter, out, progress, covariances, reproject);
 }
 
 }  // namespace rsba_amd

@@ -1,7 +1,7 @@
 // Host data model of one SfM session, field-for-field what rsba's Thrift IDL generates
 // (/root/reference/src/rsba/sfm.thrift:13-74, gen-cpp/sfm_types.h:51-66,133-146,259-272,332-348) minus
 // the RPC / serialisation machinery, plus the option fields the bundle-adjustment path reads
-// (/root/reference/src/rsba/SfmOptions.h:23-27,42,46,63-87).  Parameter blocks are the std::vector<double>
+// (/root/reference/src/rsba/SfmOptions.h:23-27,40-46,63-87).  Parameter blocks are the std::vector<double>
 // storage inside Frame::poses[i] / Track::pt / Session::cam — block identity is the address, exactly as in
 // the reference.
 #pragma once
@@ -65,7 +65,10 @@ struct SfmOptions {
     bool constVelocity = false;
   } model;
   struct Tracks {
+    bool synthetic = false;           // SfmOptions.h:40; createTracks runs evalTracks instead (VideoSfMHandler.cc:285-288)
     double sqrdThreshold = 16.0;
+    unsigned minReprojections = 3;
+    unsigned maxReprojections = 10;   // 0 = no limit (VideoSfMHandler.cc:248)
     unsigned minDistanceToCamera = 0;
   } tracks;
   struct Ceres {

@@ -250,6 +250,29 @@ int32_t rsba_validate_frame(int32_t device, const double* cam, const double* pos
 int32_t rsba_reproject_frame(int32_t device, const double* cam, const double* poses, int32_t num_poses, int32_t shutter, const int32_t* scanlines,
                              int32_t interpolate_rotation, const double* points, int64_t n, double* xy_out, uint8_t* ok_out);
 
+/* == the geometric predicates of VideoSfMHandler::createTracks / reprojectMatches (VideoSfMHandler.cc:231-372) for a batch of
+ * candidates, without a handle.  A candidate is a pair (o = cand_a[c], o2 = cand_b[c]) of indices into the observations; its
+ * request[c] holds RSBA_TRACK_* bits:
+ *   RSBA_TRACK_TRIANGULATE: tri_ok[c] = 1 iff getPose(o) and getPose(o2) differ bitwise (memcmp, :321), both directions exist
+ *     (undistortion converged, mat/cam.h:154-176), det(A) >= DBL_EPSILON in triangulate (mat/cam.h:188-231; the reference aborts
+ *     there), neither camera centre is nearer than min_distance to the point, and vision::validate holds on both sides
+ *     (:326-337).  tri_pt[c][3] is the triangulated point whenever the 3x3 solve ran, else 0.
+ *   RSBA_TRACK_REPROJECT: reproj_ok[c] = vision::sfm::validate(sess, frame of o, opt, track_pt[c], o) (struct/VideoSfM.cc:159-169):
+ *     the distance gate and the reprojection check of reprojectMatches (:250-262), both at getPose(o).
+ * Frames: cams [num_cams][9] with frame_cam [F] (NULL when num_cams == 1); poses [pose_offset[F]][6] with pose_offset [F + 1]
+ * (pose_offset[0] = 0, non-decreasing): a frame's 1 pose, 2 (interpolate_rs at the observation's scan line) or more (one per
+ * scan line, struct/VideoSfM.cc:118-132).  Observations: obs_frame [num_obs] in [0, F), each of a frame with poses; obs_xy
+ * [num_obs][2].  Outputs in the caller's candidate order; an output may be NULL only when no candidate asks for it
+ * (track_pt likewise); a bit not asked for gives 0.  All host arrays.  The ray pass (getPose, undistortion, rotation) runs once
+ * per observation and only when some candidate asks for a triangulation.  Each host thread keeps one device arena, pinned
+ * staging buffer and stream between calls, as for rsba_validate_frame; there is no CPU fallback. */
+enum { RSBA_TRACK_TRIANGULATE = 1, RSBA_TRACK_REPROJECT = 2 };
+int32_t rsba_track_candidates(int32_t device, const double* cams, int32_t num_cams, const int32_t* frame_cam, int32_t num_frames,
+                              const double* poses, const int64_t* pose_offset, int32_t shutter, const int32_t* scanlines, int32_t interpolate_rotation,
+                              const int32_t* obs_frame, const double* obs_xy, int64_t num_obs, const int32_t* cand_a, const int32_t* cand_b,
+                              const uint8_t* request, const double* track_pt, int64_t num_cand, double sq_threshold, double min_distance,
+                              uint8_t* tri_ok, double* tri_pt, uint8_t* reproj_ok);
+
 /* == the covariance blocks VideoSfMHandler::BA prints with opt.debug.calcCovariances (VideoSfMHandler.cc:602-621:
  * ceres::Covariance::Compute on (p0,p0), (p0,p1), (p1,p1) of a frame): cov [CD][CD] row-major,
  * CD = 6 * poses_per_frame, = the (frame, frame) block of (J^T J)^-1 at the current parameters, loss function applied,

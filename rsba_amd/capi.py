@@ -25,7 +25,7 @@ EXPORTS = [
     "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
-    "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe",
+    "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
 ]
 NUM_EXCHANGES = 6
 NUM_PHASES = 13
@@ -420,6 +420,34 @@ def reproject_frame(cam, poses, shutter, scanlines, points, interpolate_rotation
     _check(lib().rsba_reproject_frame(C.c_int32(device), _ptr(cam), _ptr(ps), C.c_int32(len(ps)), C.c_int32(int(shutter)), _ptr(sl), C.c_int32(int(interpolate_rotation)),
                                       _ptr(X), C.c_int64(len(X)), _ptr(xy), _ptr(ok)))
     return xy, ok.astype(bool)
+
+
+TRACK_TRIANGULATE, TRACK_REPROJECT = 1, 2   # rsba_amd.h: RSBA_TRACK_* request bits
+
+
+def track_candidates(cams, frame_cam, frame_poses, shutter, scanlines, obs_frame, obs_xy, cand_a, cand_b, request, track_pt=None,
+                     sq_threshold=16.0, min_distance=0.0, interpolate_rotation=True, device=0):
+    """The geometric predicates of createTracks / reprojectMatches for a batch of candidates, no handle (rsba_amd.h:
+    rsba_track_candidates).  frame_poses: one [np, 6] array per frame (np may differ between frames).
+    -> tri_ok [n] bool, tri_pt [n, 3], reproj_ok [n] bool"""
+    cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 9)
+    fc = None if frame_cam is None else np.ascontiguousarray(frame_cam, dtype=np.int32)
+    ps = [np.asarray(p, dtype=np.float64).reshape(-1, 6) for p in frame_poses]
+    off = np.zeros(len(ps) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(p) for p in ps])
+    poses = np.ascontiguousarray(np.concatenate(ps) if off[-1] else np.zeros((1, 6)))
+    sl = np.ascontiguousarray(scanlines, dtype=np.int32)
+    of = np.ascontiguousarray(obs_frame, dtype=np.int32); xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+    ca = np.ascontiguousarray(cand_a, dtype=np.int32); cb = np.ascontiguousarray(cand_b, dtype=np.int32)
+    rq = np.ascontiguousarray(request, dtype=np.uint8)
+    n = len(ca)
+    tp = np.zeros((n, 3)) if track_pt is None else np.ascontiguousarray(track_pt, dtype=np.float64).reshape(-1, 3)
+    tri_ok = np.zeros(n, dtype=np.uint8); tri_pt = np.zeros((n, 3)); rep = np.zeros(n, dtype=np.uint8)
+    _check(lib().rsba_track_candidates(C.c_int32(device), _ptr(cams), C.c_int32(len(cams)), _ptr(fc), C.c_int32(len(ps)), _ptr(poses), _ptr(off),
+                                       C.c_int32(int(shutter)), _ptr(sl), C.c_int32(int(interpolate_rotation)), _ptr(of), _ptr(xy), C.c_int64(len(of)),
+                                       _ptr(ca), _ptr(cb), _ptr(rq), _ptr(tp), C.c_int64(n), C.c_double(sq_threshold), C.c_double(min_distance),
+                                       _ptr(tri_ok), _ptr(tri_pt), _ptr(rep)))
+    return tri_ok.astype(bool), tri_pt, rep.astype(bool)
 
 
 def rccl_unique_id() -> bytes:
