@@ -9,6 +9,7 @@
 #include "handle.hpp"
 #include "solver_state.hpp"
 #include "tile_order.hpp"
+#include "chol_plan.hpp"
 
 using namespace rsba;
 
@@ -19,9 +20,8 @@ int32_t partition(const rsba_problem_desc* d, int32_t world, int32_t* owner, int
   if (!d || !owner || world < 1) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad partition arguments");
   const int P = d->poses_per_frame;
   if (P != 1 && P != 2) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "poses_per_frame must be 1 or 2");
-  const int FR = d->num_frames, M = d->num_points, CD = 6 * P, FT = kTile / CD;
-  const int NIB = d->calibrated ? 0 : d->num_intrinsics, NPF = d->calibrated ? 0 : (9 + CD - 1) / CD;
-  const int F = FR + NIB * NPF, nt = (F + FT - 1) / FT;
+  const TileLayout lay(P, d->num_frames, d->calibrated != 0, d->num_intrinsics);
+  const int FR = lay.FR, M = d->num_points, NIB = lay.NIB, NPF = lay.NPF, nt = lay.nt;
   const int64_t N = d->num_observations;
   if (num_top_tiles) *num_top_tiles = 0;
   if (world == 1 || N == 0) { std::fill(owner, owner + M, 0); part_of.assign(nt, 0); return RSBA_OK; }
@@ -36,13 +36,13 @@ int32_t partition(const rsba_problem_desc* d, int32_t world, int32_t* owner, int
   { std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1); for (int64_t i = 0; i < N; ++i) fr[fill[d->obs_point[i]]++] = d->obs_frame[i]; }
   std::vector<uint8_t> pair((size_t)nt * nt, 0);
   std::vector<double> weight(nt, 0.0);
-  for (int64_t i = 0; i < N; ++i) weight[d->obs_frame[i] / FT] += 1.0;
+  for (int64_t i = 0; i < N; ++i) weight[lay.frame_tile(d->obs_frame[i])] += 1.0;
   std::vector<int32_t> tiles;
   auto tiles_of = [&](int j) {
     tiles.clear();
     for (int64_t x = ptr[j]; x < ptr[j + 1]; ++x) {
-      tiles.push_back(fr[x] / FT);
-      for (int v = 0; v < NPF; ++v) tiles.push_back((FR + intr_of(fr[x]) * NPF + v) / FT);
+      tiles.push_back(lay.frame_tile(fr[x]));
+      for (int v = 0; v < NPF; ++v) tiles.push_back(lay.pseudo_tile(intr_of(fr[x]), v));
     }
     std::sort(tiles.begin(), tiles.end()); tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
   };
@@ -50,8 +50,8 @@ int32_t partition(const rsba_problem_desc* d, int32_t world, int32_t* owner, int
     tiles_of(j);
     for (size_t a = 0; a < tiles.size(); ++a) for (size_t b = 0; b < a; ++b) pair[(size_t)tiles[a] * nt + tiles[b]] = 1;
   }
-  for (int f = 0; f < FR && NIB > 0; ++f) for (int v = 0; v < NPF; ++v) { const int a = (FR + intr_of(f) * NPF + v) / FT, b = f / FT; if (a != b) pair[(size_t)std::max(a, b) * nt + std::min(a, b)] = 1; }
-  for (int c = 0; c < NIB; ++c) for (int v = 0; v < NPF; ++v) for (int w = 0; w < v; ++w) { const int a = (FR + c * NPF + v) / FT, b = (FR + c * NPF + w) / FT; if (a != b) pair[(size_t)std::max(a, b) * nt + std::min(a, b)] = 1; }
+  for (int f = 0; f < FR && NIB > 0; ++f) for (int v = 0; v < NPF; ++v) { const int a = lay.pseudo_tile(intr_of(f), v), b = lay.frame_tile(f); if (a != b) pair[(size_t)std::max(a, b) * nt + std::min(a, b)] = 1; }
+  for (int c = 0; c < NIB; ++c) for (int v = 0; v < NPF; ++v) for (int w = 0; w < v; ++w) { const int a = lay.pseudo_tile(c, v), b = lay.pseudo_tile(c, w); if (a != b) pair[(size_t)std::max(a, b) * nt + std::min(a, b)] = 1; }
   std::vector<std::vector<int32_t>> adj(nt);
   for (int a = 0; a < nt; ++a) for (int b = 0; b < a; ++b) if (pair[(size_t)a * nt + b]) { adj[a].push_back(b); adj[b].push_back(a); }
   for (auto& l : adj) std::sort(l.begin(), l.end());
@@ -98,14 +98,53 @@ extern "C" int32_t rsba_partition_points(const rsba_problem_desc* d, int32_t wor
 // *num_tiles; otherwise part_of holds *num_tiles entries (the tile count of the problem; the caller asks for it first).
 extern "C" int32_t rsba_debug_partition_tiles(const rsba_problem_desc* d, int32_t world, int32_t* part_of, int32_t* num_tiles) {
   if (!d || !num_tiles || d->num_points < 0 || (d->poses_per_frame != 1 && d->poses_per_frame != 2)) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad partition arguments");
-  const int CD = 6 * d->poses_per_frame, FT = kTile / CD;
-  const int NIB = d->calibrated ? 0 : d->num_intrinsics, NPF = d->calibrated ? 0 : (9 + CD - 1) / CD;
-  const int nt = (d->num_frames + NIB * NPF + FT - 1) / FT;
+  const int nt = TileLayout(d->poses_per_frame, d->num_frames, d->calibrated != 0, d->num_intrinsics).nt;
   if (!part_of) { *num_tiles = nt; return RSBA_OK; }
   if (*num_tiles != nt) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "num_tiles is not the problem's tile count");
   std::vector<int32_t> owner((size_t)std::max(d->num_points, 1)), parts;
   if (const int32_t rc = partition(d, world, owner.data(), nullptr, parts)) return rc;
   std::copy(parts.begin(), parts.end(), part_of);
+  return RSBA_OK;
+}
+
+// ... and the Cholesky plan (chol_plan.hpp) of a tile graph given as nt tiles and num_edges pairs {a, b}, as rank `rank` of `world`
+// ranks would build it: ordered as the solver orders it (the leaf size from RSBA_CHOL_LEAF), sharded when the graph can be cut into
+// `world` parts, every tile pair of the graph a tile pair of S.  emit(ctx, name, data, count) is called once per list — and once
+// with "meta" = {sharded, levels, partial tiles, packed slots}; the data does not outlive the call.
+extern "C" int32_t rsba_debug_chol_plan(int32_t nt, int32_t num_edges, const int32_t* edges, int32_t world, int32_t rank, int32_t two_rhs, int32_t chunk, int32_t tail,
+                                        int32_t fuse_last, void (*emit)(void* ctx, const char* name, const int32_t* data, int64_t count), void* ctx) {
+  if (nt < 1 || num_edges < 0 || (num_edges && !edges) || world < 1 || rank < 0 || rank >= world || tail < 1 || chunk < tail || !emit) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad plan arguments");
+  std::vector<std::vector<int32_t>> adj(nt);
+  std::vector<int32_t> pair_I, pair_J;
+  for (int t = 0; t < nt; ++t) { pair_I.push_back(t); pair_J.push_back(t); }
+  for (int e = 0; e < num_edges; ++e) {
+    const int a = edges[2 * e], b = edges[2 * e + 1];
+    if (a < 0 || a >= nt || b < 0 || b >= nt || a == b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad edge");
+    adj[a].push_back(b); adj[b].push_back(a);
+  }
+  for (int t = 0; t < nt; ++t) {
+    std::sort(adj[t].begin(), adj[t].end()); adj[t].erase(std::unique(adj[t].begin(), adj[t].end()), adj[t].end());
+    for (int32_t u : adj[t]) if (u < t) { pair_I.push_back(t); pair_J.push_back(u); }
+  }
+  const TileOrder ord = nested_dissection(nt, adj, plan_leaf_size(world, nt), world);
+  CholHostPlan hp;
+  chol_symbolic(nt, adj, ord, &hp);
+  CholTaskInput in;
+  in.order = &ord; in.sharded = world > 1 && ord.parts_ok; in.rank = rank; in.two_rhs = two_rhs != 0; in.pair_I = &pair_I; in.pair_J = &pair_J;
+  in.opt.chunk = chunk; in.opt.tail = tail; in.opt.fuse_last = fuse_last != 0;
+  chol_tasks(in, &hp);
+  const std::vector<int32_t> meta{hp.sharded, hp.nlev, hp.nparts, hp.nslots};
+  emit(ctx, "meta", meta.data(), (int64_t)meta.size());
+  auto bytes = [&](const char* name, const std::vector<uint8_t>& v) { const std::vector<int32_t> w(v.begin(), v.end()); emit(ctx, name, w.data(), (int64_t)w.size()); };
+#define RSBA_EMIT(x) emit(ctx, #x, hp.x.data(), (int64_t)hp.x.size())
+  RSBA_EMIT(perm); RSBA_EMIT(slot_tiles); RSBA_EMIT(level); RSBA_EMIT(cpart); RSBA_EMIT(lev_diag_ptr); RSBA_EMIT(lev_sub_ptr); RSBA_EMIT(lev_upd_ptr);
+  RSBA_EMIT(upd); RSBA_EMIT(upd_owner); RSBA_EMIT(diag_info); RSBA_EMIT(diag_ptr); RSBA_EMIT(diag_list); RSBA_EMIT(diag_own); RSBA_EMIT(diag_fuse);
+  RSBA_EMIT(sub_info); RSBA_EMIT(sub_ptr); RSBA_EMIT(sub_list); RSBA_EMIT(sub_own); RSBA_EMIT(sub_col); RSBA_EMIT(sub_pub);
+  RSBA_EMIT(back_info); RSBA_EMIT(back_ptr); RSBA_EMIT(back_list); RSBA_EMIT(tasks); RSBA_EMIT(fwd_full); RSBA_EMIT(diag_toprow);
+  RSBA_EMIT(tasks_a); RSBA_EMIT(tasks_b); RSBA_EMIT(fwd_a); RSBA_EMIT(fwd_b); RSBA_EMIT(diag_info_sh); RSBA_EMIT(sub_info_sh);
+  RSBA_EMIT(top_slots); RSBA_EMIT(top_info); RSBA_EMIT(asm_ptr); RSBA_EMIT(asm_list); RSBA_EMIT(top_tiles); RSBA_EMIT(top_fill);
+#undef RSBA_EMIT
+  bytes("row_mine", hp.row_mine); bytes("row_check", hp.row_check); bytes("row_sep", hp.row_sep);
   return RSBA_OK;
 }
 #endif

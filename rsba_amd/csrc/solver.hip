@@ -26,6 +26,7 @@
 #include "devmem.hpp"
 #include "solver_state.hpp"
 #include "tile_order.hpp"
+#include "chol_plan.hpp"
 #include "plan_device.hpp"
 #include "test_hooks.hpp"
 
@@ -50,28 +51,37 @@ struct PhaseTimer {
   ~PhaseTimer() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
 };
 
+// The lists of the Cholesky plan (chol_plan.hpp) that a CholPlan names — one row per list: the host vector, the field its device copy
+// goes to, and which plans take it (a sharded factorisation runs launch A and launch B on plans of their own, which differ from the
+// replicated one in these rows only).  build_solver walks the table once to upload and once to fill the plans.
+enum : unsigned { kPlanRep = 1, kPlanA = 2, kPlanB = 4, kPlanAll = 7 };
+struct PlanListRow { std::vector<int32_t> CholHostPlan::*host; const int32_t* CholPlan::*field; unsigned plans; };
+const PlanListRow kPlanLists[] = {
+  {&CholHostPlan::upd, &CholPlan::upd, kPlanAll},
+  {&CholHostPlan::diag_info, &CholPlan::diag_info, kPlanRep | kPlanA}, {&CholHostPlan::diag_info_sh, &CholPlan::diag_info, kPlanB},   // (B: the parts' partial tiles have been summed in by the exchange)
+  {&CholHostPlan::diag_ptr, &CholPlan::diag_ptr, kPlanAll}, {&CholHostPlan::diag_list, &CholPlan::diag_list, kPlanAll},
+  {&CholHostPlan::diag_own, &CholPlan::diag_own, kPlanAll}, {&CholHostPlan::diag_fuse, &CholPlan::diag_fuse, kPlanAll},
+  {&CholHostPlan::sub_info, &CholPlan::sub_info, kPlanRep | kPlanA}, {&CholHostPlan::sub_info_sh, &CholPlan::sub_info, kPlanB},
+  {&CholHostPlan::sub_ptr, &CholPlan::sub_ptr, kPlanAll}, {&CholHostPlan::sub_list, &CholPlan::sub_list, kPlanAll},
+  {&CholHostPlan::sub_own, &CholPlan::sub_own, kPlanAll}, {&CholHostPlan::sub_col, &CholPlan::sub_col, kPlanAll}, {&CholHostPlan::sub_pub, &CholPlan::sub_pub, kPlanAll},
+  {&CholHostPlan::back_info, &CholPlan::back_info, kPlanAll}, {&CholHostPlan::back_ptr, &CholPlan::back_ptr, kPlanAll}, {&CholHostPlan::back_list, &CholPlan::back_list, kPlanAll},
+  {&CholHostPlan::tasks, &CholPlan::tasks, kPlanRep}, {&CholHostPlan::tasks_a, &CholPlan::tasks, kPlanA}, {&CholHostPlan::tasks_b, &CholPlan::tasks, kPlanB},
+  // (read by the FWD2 / FWD2P tasks of a second right-hand side only)
+  {&CholHostPlan::fwd_full, &CholPlan::fwd_range, kPlanRep}, {&CholHostPlan::fwd_a, &CholPlan::fwd_range, kPlanA}, {&CholHostPlan::fwd_b, &CholPlan::fwd_range, kPlanB},
+  {&CholHostPlan::diag_toprow, &CholPlan::diag_toprow, kPlanAll},
+};
+constexpr size_t kNumPlanLists = sizeof kPlanLists / sizeof kPlanLists[0];
+
 struct Solver {
   PhaseTimer timer;
   PhaseTimer xtimer;   // the same for the collectives of a sharded solve, by kind (RSBA_EXCHANGE_*)
   rsba_plan_stats stats{};
   SolverDev sv{};
   std::vector<void*> allocs;
-  // Cholesky plan over the packed tile slots, level-scheduled on the elimination structure (see build_solver)
-  int nlev = 0;
-  std::vector<int32_t> lev_diag_ptr, lev_sub_ptr, lev_upd_ptr, upd;   // [nlev+1] ranges of diag / sub / update items per level
-  int32_t* d_upd = nullptr;
-  std::vector<int32_t> diag_info, diag_ptr, diag_list;                // per column: {slot_jj, old tile}; contributors {slot_jk, old tile k}
-  std::vector<int32_t> diag_own, sub_own;                             // first contributor the owner multiplies itself (the ones before arrive as partial tiles)
-  std::vector<int32_t> diag_fuse;                                     // per column j: SUB item of tile (j, k*), k* = its last contributor, which the DIAG task forms itself (-1: none)
-  int32_t* d_diag_fuse = nullptr;
-  std::vector<int32_t> sub_pub;                                       // per SUB item: DIAG item that wants its X = S_ij - updates published (sv.Xpub slot), -1: nobody
-  int32_t* d_sub_pub = nullptr;
-  std::vector<int32_t> sub_col;                                       // per sub tile: tile index of its column (W_j, z_j)
-  std::vector<int32_t> sub_info, sub_ptr, sub_list;                   // per tile (i,j): {slot_ij, slot_jj}; contributors {slot_ik, slot_jk}
-  std::vector<int32_t> back_info, back_ptr, back_list;                // per column: {slot_jj, old tile}; tiles {slot_ij, old tile i}
-  int32_t *d_diag_info = nullptr, *d_diag_ptr = nullptr, *d_diag_list = nullptr, *d_sub_info = nullptr, *d_sub_ptr = nullptr,
-          *d_sub_list = nullptr, *d_sub_col = nullptr, *d_diag_own = nullptr, *d_sub_own = nullptr, *d_back_info = nullptr, *d_back_ptr = nullptr, *d_back_list = nullptr;
-  std::vector<int32_t> tasks;                                         // {kind, item} in level order, backward solve last
+  // Cholesky plan over the packed tile slots: symbolic factorisation and task graph, the one owner of the host lists (the uploads
+  // reference them; the level-scheduled fallback reads lev_*_ptr during solves); their device copies in the order of kPlanLists
+  CholHostPlan hp;
+  int32_t* d_plan_lists[kNumPlanLists] = {};
   DagArgs* d_dag_args = nullptr;
   int32_t* d_slot_tiles = nullptr;                                    // [nslots][2] {row tile, column tile} of every packed tile
   double* d_verify = nullptr;                                         // [2 * npad] residual and yardstick of the DAG verification
@@ -81,17 +91,13 @@ struct Solver {
   bool verify_dag = true;                                             // RSBA_CHOL_VERIFY=0 switches the check off
   bool test_corrupt_once = false;                                     // RSBA_CHOL_TEST_CORRUPT=1 (tests): the first DAG solve loses one entry of y
   int dag_fallbacks = 0;                                              // solves repeated on the level schedule after a failed check                                      // device copy of {sv, plan} for the persistent kernel
-  int32_t* d_tasks = nullptr;
   unsigned int* d_dag_sync = nullptr;                                 // [ticket, pad x3]
   long long* d_trace = nullptr;                                       // RSBA_CHOL_TRACE=<file>: task time stamps of the last factorisation
   CholPlan plan{};
   int dag_workgroups = 0;
   bool dag_one_per_cu = true;                                         // LDS request above half a CU's: two persistent workgroups never share a CU (RSBA_CHOL_WGS above the CU count lifts it)
   bool use_levels = false;                                            // RSBA_CHOL_LEVELS=1: one launch per (level, kind)
-  std::vector<int32_t> fwd_full, fwd_a, fwd_b, diag_toprow; int32_t *d_fwd_full = nullptr, *d_fwd_a = nullptr, *d_fwd_b = nullptr, *d_diag_toprow = nullptr;   // second right-hand side: contributor ranges per DIAG item and plan
   uint8_t* d_row_sep = nullptr;                                       // [nt] tile columns (old index) in the separators
-  bool two_rhs = false;                                               // the plan carries a second right-hand side through the factorisation (free interFrameRatio: FWD2 / ETA tasks)
-  int last_diag_slot = 0;
   int32_t* d_obs_slot = nullptr;
   double *d_gpose = nullptr, *d_gpoint = nullptr;
   int64_t num_pairs = 0;
@@ -113,9 +119,7 @@ struct Solver {
   // Sharded factorisation (several ranks whose points respect the cut of tile_order.hpp): this rank factors the columns
   // of ITS part of the elimination tree from its own partial S (launch A), the ranks all-reduce the separators' tiles less what
   // their parts subtract from them, every rank factors the separators and solves them backward, then its own part (launch B).
-  bool sharded = false, sharded_off = false;                          // the plan has that form; a suspect solve switched it off for this handle
-  std::vector<int32_t> tasks_a, tasks_b; int32_t *d_tasks_a = nullptr, *d_tasks_b = nullptr;
-  std::vector<int32_t> diag_info_sh, sub_info_sh; int32_t *d_diag_info_sh = nullptr, *d_sub_info_sh = nullptr;   // {.., part0, nparts} of the separators' items without the parts' partials
+  bool sharded_off = false;                                           // a suspect solve switched the sharded form (hp.sharded) off for this handle
   CholPlan plan_a{}, plan_b{}; DagArgs* d_dag_args_a[2] = {nullptr, nullptr}; DagArgs* d_dag_args_b[2] = {nullptr, nullptr};
   int ntop_slots = 0, ntop_tiles = 0;
   int32_t *d_top_slots = nullptr, *d_top_info = nullptr, *d_asm_ptr = nullptr, *d_asm_list = nullptr, *d_top_tiles = nullptr;
@@ -283,17 +287,16 @@ int32_t build_solver_impl(rsba_handle* h) {
     char b[64]; std::snprintf(b, sizeof b, " %s %.1f ms;", name, (t - t_phase) * 1e3); phases += b; t_phase = t;
   };
   SolverDev& sv = s->sv;
-  const int FR = dp.F, M = dp.M, CD = 6 * dp.P;          // FR real frames
-  const int NIB = dp.calibrated ? 0 : dp.NI;               // intrinsics parameter blocks: sess.cam and / or per-frame f.cam (CeresHandler.h:260,277)
-  const int NPF = dp.calibrated ? 0 : (9 + CD - 1) / CD;   // pseudo frames per intrinsics block (solver_state.hpp)
-  const int F = FR + NIB * NPF;                            // camera-side blocks of the reduced system
+  const TileLayout lay(dp.P, dp.F, dp.calibrated != 0, dp.NI);
+  // FR real frames; NIB intrinsics parameter blocks: sess.cam and / or per-frame f.cam (CeresHandler.h:260,277), NPF pseudo frames each;
+  // F camera-side blocks of the reduced system, FT to a tile
+  const int FR = lay.FR, M = dp.M, CD = lay.CD, NIB = lay.NIB, NPF = lay.NPF, F = lay.F, FT = lay.FT;
   const int64_t N = dp.N;
   sv.F = FR; sv.Fx = F; sv.NPF = NPF; sv.NIB = NIB;
   const std::vector<int32_t>& fi = h->frame_intr;          // frame -> intrinsics block
   auto intr_of = [&](int f) { return NIB > 1 ? fi[f] : 0; };
   sv.CD = CD; sv.n = (int64_t)F * CD;
-  const int FT = kTile / CD;
-  sv.nt = (F + FT - 1) / FT; sv.npad = (int64_t)sv.nt * kTile;
+  sv.nt = lay.nt; sv.npad = (int64_t)sv.nt * kTile;
   const std::vector<int32_t>& of = h->obs_frame; const std::vector<int32_t>& op = h->obs_point;
 
   std::unique_lock<std::mutex> scratch_lock(g_plan_scratch_mutex, std::try_to_lock);
@@ -718,32 +721,10 @@ int32_t build_solver_impl(rsba_handle* h) {
   std::vector<double> tile_weight(nt, 0.0);
   for (int f = 0; f < FR; ++f) tile_weight[f / FT] += (double)(h->frame_obs_total.empty() ? frame_ptr[f + 1] - frame_ptr[f] : h->frame_obs_total[f]);
   TileOrder tord = nested_dissection(nt, adj, plan_leaf_size(want_parts ? h->world : 1, nt), want_parts ? h->world : 1, &tile_weight);
-  const std::vector<int32_t>& perm = tord.perm;          // perm[new] = old tile
-  std::vector<int32_t> iperm(nt);
-  for (int k = 0; k < nt; ++k) iperm[perm[k]] = k;
   tick("ordering");
-  // symbolic factorisation in the new order: col[k] = rows i > k of column k (after fill), row[j] = columns k < j of row j
-  std::vector<std::vector<int32_t>> col(nt), row(nt);
-  {
-    std::vector<std::vector<uint8_t>> mark(nt);
-    for (int k = 0; k < nt; ++k) mark[k].assign(nt - k, 0);       // mark[k][i-k] for i >= k
-    for (int t = 0; t < nt; ++t) for (int u : adj[t]) { const int i = std::max(iperm[t], iperm[u]), k = std::min(iperm[t], iperm[u]); mark[k][i - k] = 1; }
-    for (int k = 0; k < nt; ++k) {
-      for (int i = k + 1; i < nt; ++i) if (mark[k][i - k]) col[k].push_back(i);
-      for (size_t u = 0; u < col[k].size(); ++u) for (size_t v = u; v < col[k].size(); ++v) mark[col[k][u]][col[k][v] - col[k][u]] = 1;
-      for (int32_t i : col[k]) row[i].push_back(k);
-    }
-  }
-  // packed tile slots, column by column: (k,k) first, then the sub-diagonal tiles of column k
-  std::vector<int32_t> slot_base(nt + 1, 0);
-  for (int k = 0; k < nt; ++k) slot_base[k + 1] = slot_base[k] + 1 + (int32_t)col[k].size();
-  sv.nslots = slot_base[nt];
-  auto slot_of = [&](int i, int k) -> int32_t {   // new indices, i >= k; -1 if the tile is structurally zero
-    if (i == k) return slot_base[k];
-    auto it = std::lower_bound(col[k].begin(), col[k].end(), i);
-    return (it != col[k].end() && *it == i) ? slot_base[k] + 1 + (int32_t)(it - col[k].begin()) : -1;
-  };
-  s->last_diag_slot = slot_base[iperm[nt - 1]];      // the (possibly padded) last tile of the natural order
+  CholHostPlan& hp = s->hp;
+  chol_symbolic(nt, adj, tord, &hp);
+  sv.nslots = hp.nslots;
   tick("symbolic");
   // ---- sharded factorisation: does every rank's share of the points respect the cut? ----
   // (part of a column = the rank whose subtree it belongs to, -1 = a separator the ranks share.)  Every kind of block the solver takes
@@ -754,7 +735,6 @@ int32_t build_solver_impl(rsba_handle* h) {
   // the block is owned by that part's rank (rsba_partition_points builds the same graph and follows the pseudo tiles too: the vote below
   // checks both), and the tile's replicated terms — damping, identity padding, the gradient after exchange (1) — follow frame_lead like
   // any frame tile's.
-  std::vector<int32_t> cpart(nt, -1);
   bool sharded = want_parts && tord.parts_ok;
   if (const char* e = std::getenv("RSBA_SHARDED")) sharded = sharded && e[0] != '0';   // A/B switch
   if (want_parts) {
@@ -763,8 +743,8 @@ int32_t build_solver_impl(rsba_handle* h) {
     // must be this rank's or a separator (a point seen in separator frames only may still reach a block whose pseudo tile is in a part)
     auto foreign = [&](int t) { const int p = tord.part_of[t]; return p >= 0 && p != h->rank; };
     for (int64_t i = 0; i < N && bad == 0.0; ++i) {
-      if (foreign(of[i] / FT)) bad = 1.0;
-      for (int v = 0; v < NPF && NIB > 0; ++v) if (foreign((FR + intr_of(of[i]) * NPF + v) / FT)) bad = 1.0;
+      if (foreign(lay.frame_tile(of[i]))) bad = 1.0;
+      for (int v = 0; v < NPF && NIB > 0; ++v) if (foreign(lay.pseudo_tile(intr_of(of[i]), v))) bad = 1.0;
     }
     if (local_fail) bad = 2.0;   // this rank cannot build its plan at all: every rank gives up together
     // every rank must take the same form: one all-reduce (max) of the verdicts — through the handle's cost slot (allocated with the
@@ -780,8 +760,6 @@ int32_t build_solver_impl(rsba_handle* h) {
     if (bad >= 2.0) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "another rank could not build its plan (its own call says why)");
     sharded = bad == 0.0;
   }
-  s->sharded = sharded;
-  if (sharded) for (int j = 0; j < nt; ++j) cpart[j] = tord.part_of[perm[j]];
   if (sharded && !h->prior_frames.empty() && !h->prior_split) {
     // The prior between frames f and f - 1 (CeresHandler.h:147-185) adds to U_f, U_f-1, the (f, f-1) block and both gradients: it
     // belongs to the rank that owns the part either frame is in (two adjacent frames are never in two different parts: their tiles
@@ -802,177 +780,16 @@ int32_t build_solver_impl(rsba_handle* h) {
     if (h->prior_invalid > 0) h->prior_invalid = mine;
     h->prior_split = true;
   }
-  // level schedule: column j is ready once every column of row[j] is done
-  std::vector<int32_t> level(nt, 0);
-  int nlev = 0;
-  for (int j = 0; j < nt; ++j) { int l = 0; for (int32_t k : row[j]) l = std::max(l, level[k] + 1); level[j] = l; nlev = std::max(nlev, l + 1); }
-  s->nlev = nlev;
-  std::vector<std::vector<int32_t>> lev_cols(nlev);
-  for (int j = 0; j < nt; ++j) lev_cols[level[j]].push_back(j);
-  // flattened work lists (device copies below)
-  //   diag item d: column j -> {slot_jj, old tile of j}, contributors k in row[j]: {slot_jk, old tile of k}
-  //   sub  item t: tile (i,j) -> {slot_ij, slot_jj}, contributors k in row[j] & row[i]: {slot_ik, slot_jk}
-  //   back item  : column j -> {slot_jj, old tile of j}, tiles i in col[j]: {slot_ij, old tile of i}
-  // A tile with many contributors (separator rows are dense across their segments) would serialise dozens
-  // of 48^3 products in one workgroup; its contributor list is cut into chunks of kChunk that separate
-  // workgroups reduce to partial tiles (fixed split, fixed order: still deterministic), summed by the
-  // factor kernels.  upd items: {kind 0 diag / 1 sub, list begin, list end, scratch slot}.
-  // The owner of a tile keeps the last kTail contributors — the ones from the latest levels, the list being sorted by
-  // level — for itself: on the critical path a freshly finished tile is then multiplied by its consumer directly
-  // instead of passing through a partial tile in HBM (two memory round trips less per level).
-  // An UPDATE task becomes runnable one level after its last contributor, which is where it enters the ticket order.
-  // Look-ahead on the critical path: the LAST contributor k* of column j finishes one level before j and would reach the
-  // DIAG task through the SUB task of tile (j, k*) — W_k* out, L_jk* = X W_k*^T back, two hand-offs through memory.  The DIAG
-  // task takes X = S_jk* - (older updates) — which the SUB task publishes as soon as it has it, long before W_k* exists — and
-  // multiplies by W_k* itself the moment it lands (one hand-off).  The SUB task still writes L_jk* for everyone else; both
-  // follow the same arithmetic, bit for bit.
-  bool fuse_last = true;
-  if (const char* e = std::getenv("RSBA_CHOL_FUSE")) fuse_last = e[0] != '0';
-  std::vector<int32_t> sub_base(nt, 0);   // first SUB item of each column (items of a column follow col[] order)
-  int kChunk = 12, kTail = 2;   // (swept on C4 / C5 after the look-ahead: fewer, longer UPDATE tasks and a short own share — 2.45 -> 2.36 ms per C4 iteration)
-  if (const char* e = std::getenv("RSBA_CHOL_TAIL")) kTail = std::max(1, std::atoi(e));       // tuning aids
-  if (const char* e = std::getenv("RSBA_CHOL_CHUNK")) kChunk = std::max(kTail, std::atoi(e));
-  s->lev_diag_ptr.assign(1, 0); s->lev_sub_ptr.assign(1, 0); s->lev_upd_ptr.assign(1, 0);
-  s->diag_ptr.assign(1, 0); s->sub_ptr.assign(1, 0); s->back_ptr.assign(1, 0);
-  int parts = 0;
-  std::vector<std::vector<int32_t>> upd_by_level(nlev);
-  std::vector<int32_t> klev;   // level of each contributor of the list being built
-  std::vector<int32_t> upd_owner, diag_colnew, sub_colnew; int cur_part = -1;   // rank that runs each UPDATE item (-1: every rank); column (new order) of each DIAG / SUB item
-  std::vector<std::vector<int32_t>> asm_of_slot((size_t)sv.nslots);   // per separator tile of a sharded plan: {part, partial tile} of the parts' UPDATE items that subtract from it
-  for (int l = 0; l < nlev; ++l) {
-    const size_t diag0 = s->diag_info.size() / 4, sub0 = s->sub_info.size() / 4;
-    // contributors [p0, p1) of the list being built (levels in klev, klev[0] belonging to list position lbase); the first nb of them
-    // — sharded plans, separator items only — are the columns of the ranks' parts, grouped by part (pk = their parts): each part's
-    // share is cut into UPDATE items that ITS rank runs, whatever their number; {part0, nparts} covers every partial tile of the item
-    // — what the replicated factorisation subtracts —, info_sh the ones of the separators' own columns only — what is left to
-    // subtract after the exchange has summed the rest in (assemble_top)
-    auto chunk_it = [&](int kind, int32_t p0, int32_t p1, std::vector<int32_t>& info, std::vector<int32_t>& own, int32_t lbase, int nb, const std::vector<int32_t>& pk,
-                        std::vector<int32_t>* info_sh, int32_t tile_slot) {
-      const int32_t first_part = parts;
-      int cnt = 0;
-      for (int32_t q = p0; q < p0 + nb;) {   // the parts' shares
-        int32_t qe = q; while (qe < p0 + nb && pk[qe - p0] == pk[q - p0]) ++qe;
-        for (int32_t c = q; c < qe; c += kChunk) {
-          const int32_t c1 = std::min(c + kChunk, qe);
-          upd_by_level[klev[c1 - 1 - lbase] + 1].push_back((int32_t)(s->upd.size() / 4));
-          upd_owner.push_back(pk[q - p0]); asm_of_slot[tile_slot].push_back(pk[q - p0]); asm_of_slot[tile_slot].push_back(parts);
-          s->upd.push_back(kind); s->upd.push_back(c); s->upd.push_back(c1); s->upd.push_back(parts++); ++cnt;
-        }
-        q = qe;
-      }
-      const int nbparts = cnt;
-      p0 += nb;
-      if (p1 - p0 <= kChunk) own.push_back(p0);
-      else {
-        const int32_t own0 = p1 - kTail;
-        for (int32_t q = p0; q < own0; q += kChunk) {
-          const int32_t q1 = std::min(q + kChunk, own0);
-          upd_by_level[klev[q1 - 1 - lbase] + 1].push_back((int32_t)(s->upd.size() / 4));
-          upd_owner.push_back(cur_part);
-          s->upd.push_back(kind); s->upd.push_back(q); s->upd.push_back(q1); s->upd.push_back(parts++); ++cnt;
-        }
-        own.push_back(own0);
-      }
-      info.push_back(cnt ? first_part : 0); info.push_back(cnt);
-      if (info_sh) { info_sh->push_back(cnt - nbparts ? first_part + nbparts : 0); info_sh->push_back(cnt - nbparts); }
-    };
-    // contributors of a separator item of a sharded plan: the parts' columns first, part by part, then the separators' own — each
-    // group in the order its columns finish
-    auto split_parts = [&](std::vector<int32_t>& ks, std::vector<int32_t>& pk) {
-      std::stable_sort(ks.begin(), ks.end(), [&](int32_t x, int32_t y) { const unsigned px = (unsigned)cpart[x], py = (unsigned)cpart[y]; return px < py; });   // (-1 = separators: last)
-      pk.clear();
-      for (int32_t k : ks) if (cpart[k] >= 0) pk.push_back(cpart[k]);
-      return (int)pk.size();
-    };
-    for (int32_t j : lev_cols[l]) {
-      std::vector<int32_t> rj(row[j]);   // contributors in the order they finish
-      std::stable_sort(rj.begin(), rj.end(), [&](int32_t x, int32_t y) { return level[x] < level[y]; });
-      const bool topcol = sharded && cpart[j] < 0;
-      cur_part = cpart[j];
-      std::vector<int32_t> pk;
-      const int nbj = topcol ? split_parts(rj, pk) : 0;
-      s->diag_info.push_back(slot_base[j]); s->diag_info.push_back(perm[j]);
-      if (sharded) { s->diag_info_sh.push_back(slot_base[j]); s->diag_info_sh.push_back(perm[j]); }
-      diag_colnew.push_back(j);
-      const int32_t dp0 = (int32_t)(s->diag_list.size() / 2);
-      klev.clear();
-      for (int32_t k : rj) { s->diag_list.push_back(slot_of(j, k)); s->diag_list.push_back(perm[k]); klev.push_back(level[k]); }
-      s->diag_ptr.push_back((int32_t)(s->diag_list.size() / 2));
-      {
-        // the contributors a second right-hand side's forward task sums over (FWD2 / FWD2P, cholesky.hip): all of them; in a sharded plan a
-        // separator column takes THIS rank's part in launch A (its share travels) and the separators' own columns in launch B
-        const int32_t dp1 = (int32_t)(s->diag_list.size() / 2);
-        s->fwd_full.push_back(dp0); s->fwd_full.push_back(dp1);
-        if (sharded) {
-          int32_t lo = dp0, hi = dp0;
-          if (topcol) { int q = 0; while (q < nbj && pk[q] != h->rank) ++q; lo = dp0 + q; while (q < nbj && pk[q] == h->rank) ++q; hi = dp0 + q; }
-          else { lo = dp0; hi = dp1; }
-          s->fwd_a.push_back(lo); s->fwd_a.push_back(hi);
-          s->fwd_b.push_back(topcol ? dp0 + nbj : dp0); s->fwd_b.push_back(topcol ? dp1 : dp0);
-        }
-      }
-      chunk_it(0, dp0, (int32_t)(s->diag_list.size() / 2), s->diag_info, s->diag_own, dp0, nbj, pk, sharded ? &s->diag_info_sh : nullptr, slot_base[j]);
-      if (fuse_last && !rj.empty() && (!topcol || cpart[rj.back()] < 0)) {   // (a separator column of a sharded plan never takes a part's column by the hand: it lives on another rank)
-        const int32_t ks = rj.back();
-        const int32_t fs = sub_base[ks] + (int32_t)(std::lower_bound(col[ks].begin(), col[ks].end(), j) - col[ks].begin());
-        s->diag_fuse.push_back(fs);
-        s->sub_pub[fs] = (int32_t)(s->diag_info.size() / 4) - 1;
-      } else s->diag_fuse.push_back(-1);
-      sub_base[j] = (int32_t)(s->sub_info.size() / 4);
-      s->back_info.push_back(slot_base[j]); s->back_info.push_back(perm[j]);
-      for (auto it = col[j].rbegin(); it != col[j].rend(); ++it) { s->back_list.push_back(slot_of(*it, j)); s->back_list.push_back(perm[*it]); }   // bottom-up: the order the y_i arrive in
-      s->back_ptr.push_back((int32_t)(s->back_list.size() / 2));
-      for (int32_t i : col[j]) {
-        s->sub_info.push_back(slot_of(i, j)); s->sub_info.push_back(slot_base[j]); s->sub_col.push_back(perm[j]); s->sub_pub.push_back(-1);
-        if (sharded) { s->sub_info_sh.push_back(slot_of(i, j)); s->sub_info_sh.push_back(slot_base[j]); }
-        sub_colnew.push_back(j);
-        const int32_t sp0 = (int32_t)(s->sub_list.size() / 2);
-        // k in row[j] with tile (i,k) present (rj: for a separator column of a sharded plan the parts' columns first, part by part)
-        klev.clear(); pk.clear();
-        for (int32_t k : rj) { const int32_t sik = slot_of(i, k); if (sik >= 0) { s->sub_list.push_back(sik); s->sub_list.push_back(slot_of(j, k)); klev.push_back(level[k]); if (topcol && cpart[k] >= 0) pk.push_back(cpart[k]); } }
-        s->sub_ptr.push_back((int32_t)(s->sub_list.size() / 2));
-        chunk_it(1, sp0, (int32_t)(s->sub_list.size() / 2), s->sub_info, s->sub_own, sp0, (int)pk.size(), pk, sharded ? &s->sub_info_sh : nullptr, slot_of(i, j));
-      }
-    }
-    s->lev_diag_ptr.push_back((int32_t)(s->diag_info.size() / 4));
-    s->lev_sub_ptr.push_back((int32_t)(s->sub_info.size() / 4));
-    s->lev_upd_ptr.push_back((int32_t)(s->upd.size() / 4));
-    (void)diag0; (void)sub0;
-  }
-  // A free interFrameRatio brings a second right-hand side (its column of the normal equations): z2 = L^-1 b is formed by FWD2 tasks
-  // right behind the DIAG tasks of their columns — light tasks for workgroups the factorisation leaves idle — and ONE ETA task between
-  // the forward and the backward phase turns both forward solves into the ratio's step (solver_state.hpp; cholesky.hip)
-  const bool two_rhs = h->prior_free && !h->prior_frames.empty();
-  s->two_rhs = two_rhs;
-  for (int l = 0; l < nlev; ++l) {
-    for (int32_t u : upd_by_level[l]) { s->tasks.push_back(kTaskUpdate); s->tasks.push_back(u); }
-    for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { s->tasks.push_back(kTaskDiag); s->tasks.push_back(d); }
-    if (two_rhs) for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { s->tasks.push_back(kTaskFwd2); s->tasks.push_back(d); }
-    for (int t = s->lev_sub_ptr[l]; t < s->lev_sub_ptr[l + 1]; ++t) { s->tasks.push_back(kTaskSub); s->tasks.push_back(t); }
-  }
-  if (two_rhs) { s->tasks.push_back(kTaskEta); s->tasks.push_back(0); }
-  for (int l = nlev - 1; l >= 0; --l)
-    for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { s->tasks.push_back(kTaskBack); s->tasks.push_back(d); }
-  if (sharded) {
-    // launch A: this rank's part, forward (the parts' UPDATE items of the separators' tiles included); launch B: the separators,
-    // forward and backward, then this rank's part backward
-    const int me = h->rank;
-    for (int l = 0; l < nlev; ++l) {
-      for (int32_t u : upd_by_level[l]) { std::vector<int32_t>& t = upd_owner[u] == me ? s->tasks_a : s->tasks_b; if (upd_owner[u] == me || upd_owner[u] < 0) { t.push_back(kTaskUpdate); t.push_back(u); } }
-      for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { const int p = cpart[diag_colnew[d]]; if (p == me) { s->tasks_a.push_back(kTaskDiag); s->tasks_a.push_back(d); } else if (p < 0) { s->tasks_b.push_back(kTaskDiag); s->tasks_b.push_back(d); } }
-      if (two_rhs) for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { const int p = cpart[diag_colnew[d]]; if (p == me) { s->tasks_a.push_back(kTaskFwd2); s->tasks_a.push_back(d); } else if (p < 0) { s->tasks_b.push_back(kTaskFwd2); s->tasks_b.push_back(d); } }
-      for (int t = s->lev_sub_ptr[l]; t < s->lev_sub_ptr[l + 1]; ++t) { const int p = cpart[sub_colnew[t]]; if (p == me) { s->tasks_a.push_back(kTaskSub); s->tasks_a.push_back(t); } else if (p < 0) { s->tasks_b.push_back(kTaskSub); s->tasks_b.push_back(t); } }
-    }
-    if (two_rhs) {
-      // launch A ends with what travels: this rank's part's share of every separator column's second right-hand side, and of the two dots;
-      // launch B's ETA task sits between its forward and its backward phase
-      for (int d = 0; d < (int)diag_colnew.size(); ++d) if (cpart[diag_colnew[d]] < 0) { s->tasks_a.push_back(kTaskFwd2P); s->tasks_a.push_back(d); }
-      s->tasks_a.push_back(kTaskEta); s->tasks_a.push_back(0);
-      s->tasks_b.push_back(kTaskEta); s->tasks_b.push_back(0);
-    }
-    for (int l = nlev - 1; l >= 0; --l)
-      for (int d = s->lev_diag_ptr[l]; d < s->lev_diag_ptr[l + 1]; ++d) { const int p = cpart[diag_colnew[d]]; if (p == me || p < 0) { s->tasks_b.push_back(kTaskBack); s->tasks_b.push_back(d); } }
-  }
+  // ---- the task graph: items, chunking, ticket orders (chol_plan.hpp) ----
+  CholTaskInput tin;
+  tin.order = &tord; tin.sharded = sharded; tin.rank = h->rank; tin.pair_I = &tp_I; tin.pair_J = &tp_J;
+  tin.two_rhs = h->prior_free && !h->prior_frames.empty();   // a free interFrameRatio: its column of the normal equations rides through the factorisation
+  if (const char* e = std::getenv("RSBA_CHOL_FUSE")) tin.opt.fuse_last = e[0] != '0';
+  // (the defaults: swept on C4 / C5 after the look-ahead — fewer, longer UPDATE tasks and a short own share, 2.45 -> 2.36 ms per C4 iteration)
+  if (const char* e = std::getenv("RSBA_CHOL_TAIL")) tin.opt.tail = std::max(1, std::atoi(e));       // tuning aids
+  if (const char* e = std::getenv("RSBA_CHOL_CHUNK")) tin.opt.chunk = std::max(tin.opt.tail, std::atoi(e));
+  chol_tasks(tin, &hp);
+  const bool two_rhs = hp.two_rhs;
   tick("tasks");
   // Chunks of the Schur kernel (one workgroup each): at most kSchurChunk consecutive entries of one tile pair, numbered tile
   // pair by tile pair in (I, J) order — the pairs of one tile row, which read the same A_j(I) groups, next to each other; the
@@ -1076,9 +893,9 @@ int32_t build_solver_impl(rsba_handle* h) {
   std::vector<int32_t> tp_dst(ntp); std::vector<uint8_t> tp_trans(ntp, 0);
   std::vector<int64_t> tp_add((size_t)ntp * FT * FT, -1);
   for (int t = 0; t < ntp; ++t) {
-    const int I = tp_I[t], J = tp_J[t], pI = iperm[I], pJ = iperm[J];
+    const int I = tp_I[t], J = tp_J[t], pI = hp.iperm[I], pJ = hp.iperm[J];
     // tile of the pair in the permuted order; if the ordering swapped the two tiles it is stored transposed
-    if (pI >= pJ) tp_dst[t] = slot_of(pI, pJ); else { tp_dst[t] = slot_of(pJ, pI); tp_trans[t] = 1; }
+    if (pI >= pJ) tp_dst[t] = hp.slot_of(pI, pJ); else { tp_dst[t] = hp.slot_of(pJ, pI); tp_trans[t] = 1; }
     // which J^T J block enters block (a,b) of this tile: U layout [frames][pseudo x frames][pseudo x pseudo]
     for (int x = 0; x < FT; ++x) for (int y = 0; y < FT; ++y) {
       const int a = I * FT + x, b = J * FT + y;
@@ -1220,11 +1037,10 @@ int32_t build_solver_impl(rsba_handle* h) {
     up.upload_const(&sv.tp_desc, tp_desc);
   }
   if ((rc = s_alloc(s, &sv.schur_part, (size_t)std::max(sv.nchunk, 1) * (kTile * kTile + kTile)))) return rc;
-  up.upload_ref(&s->d_upd, s->upd);
   // the write-once cells of the persistent Cholesky driver — factor tiles | partial tiles | W | z, y | published X — live in ONE
   // allocation: one memset re-arms them before a launch (five launches before)
   {
-    const size_t nLf = (size_t)sv.nslots * kTile * kTile, nPart = (size_t)std::max(parts, 1) * (kTile * kTile + kTile), nW = (size_t)nt * kTile * kTile, nZ = 3 * (size_t)sv.npad + 8;   // z | y | z2 | {s eta}
+    const size_t nLf = (size_t)sv.nslots * kTile * kTile, nPart = (size_t)std::max(hp.nparts, 1) * (kTile * kTile + kTile), nW = (size_t)nt * kTile * kTile, nZ = 3 * (size_t)sv.npad + 8;   // z | y | z2 | {s eta}
     s->ncells = nLf + nPart + nW + nZ + nW;
     s->cell_off[0] = 0; s->cell_off[1] = nLf; s->cell_off[2] = nLf + nPart; s->cell_off[3] = nLf + nPart + nW; s->cell_off[4] = nLf + nPart + nW + nZ;
     for (int b = 0; b < 2; ++b) {
@@ -1240,74 +1056,24 @@ int32_t build_solver_impl(rsba_handle* h) {
     sv.Lf = cells; sv.chol_part = cells + nLf; sv.Winv = sv.chol_part + nPart; sv.zv = sv.Winv + nW; sv.yv = sv.zv + sv.npad; sv.Xpub = sv.zv + nZ;
     sv.zv2 = nullptr; sv.ceta = nullptr; sv.border2 = nullptr; sv.rt = nullptr;   // (set with the border, below)
   }
-  up.upload_ref(&s->d_tasks, s->tasks);
   if ((rc = s_alloc(s, &s->d_dag_sync, 4))) return rc;
   HIP_TRY(hipMemsetAsync(s->d_dag_sync, 0, 4 * sizeof(unsigned int), h->stream));   // (the persistent kernel leaves its counters at zero behind every launch)
   if ((rc = s_alloc(s, &s->zy2, 2 * (size_t)sv.npad))) return rc;
-  up.upload_ref(&s->d_diag_info, s->diag_info);
-  up.upload_ref(&s->d_diag_ptr, s->diag_ptr);
-  up.upload_ref(&s->d_diag_list, s->diag_list);
-  up.upload_ref(&s->d_sub_info, s->sub_info);
-  up.upload_ref(&s->d_sub_ptr, s->sub_ptr);
-  up.upload_ref(&s->d_sub_list, s->sub_list);
-  up.upload_ref(&s->d_sub_col, s->sub_col);
-  up.upload_ref(&s->d_diag_own, s->diag_own);
-  up.upload_ref(&s->d_diag_fuse, s->diag_fuse);
-  up.upload_ref(&s->d_sub_pub, s->sub_pub);
-  up.upload_ref(&s->d_sub_own, s->sub_own);
-  up.upload_ref(&s->d_back_info, s->back_info);
-  up.upload_ref(&s->d_back_ptr, s->back_ptr);
-  up.upload_ref(&s->d_back_list, s->back_list);
-  {
-    // second right-hand side: per DIAG item the index of its column among the separators' tile columns (ascending new order: the order of top_tiles below)
-    s->diag_toprow.assign(diag_colnew.size(), -1);
-    if (sharded) {
-      std::vector<int32_t> trow_of_col((size_t)nt, -1);
-      int32_t cnt = 0;
-      for (int j = 0; j < nt; ++j) if (cpart[j] < 0) trow_of_col[j] = cnt++;
-      for (size_t d = 0; d < diag_colnew.size(); ++d) s->diag_toprow[d] = trow_of_col[diag_colnew[d]];
-    }
-    up.upload_ref(&s->d_fwd_full, s->fwd_full); up.upload_ref(&s->d_diag_toprow, s->diag_toprow);
-    if (sharded) { up.upload_ref(&s->d_fwd_a, s->fwd_a); up.upload_ref(&s->d_fwd_b, s->fwd_b); }
-  }
+  for (size_t i = 0; i < kNumPlanLists; ++i) if (sharded || (kPlanLists[i].plans & kPlanRep)) up.upload_ref(&s->d_plan_lists[i], hp.*kPlanLists[i].host);
 
   // ---- sharded factorisation: what the exchange between the two launches needs ----
-  std::vector<int32_t> top_slots, top_info, asm_ptr(1, 0), asm_list, top_tiles, top_fill;   // (alive until the uploads have finished)
-  std::vector<uint8_t> row_mine((size_t)nt, 1);
-  std::vector<double> frame_lead;
+  std::vector<double> frame_lead;   // (alive until the uploads have finished)
   sv.frame_lead = nullptr;
   if (sharded) {
-    std::vector<uint8_t> has_pair((size_t)sv.nslots, 0);
-    for (int t = 0; t < ntp; ++t) has_pair[tp_dst[t]] = 1;
-    // the separators' tiles, column by column: {slot, has a tile pair (else: fill only, zero in S), index among the separator tiles of its row of the rhs or -1}
-    for (int j = 0; j < nt; ++j) if (cpart[j] < 0) {
-      const int trow = (int)top_tiles.size();
-      top_tiles.push_back(perm[j]);
-      auto add = [&](int32_t slot, int rhs_row) {
-        top_slots.push_back(slot); top_info.push_back(has_pair[slot]); top_info.push_back(rhs_row);
-        const std::vector<int32_t>& a = asm_of_slot[slot];
-        for (size_t q = 0; q + 1 < a.size(); q += 2) if (a[q] == h->rank) asm_list.push_back(a[q + 1]);   // this rank's partial tiles, in list order
-        asm_ptr.push_back((int32_t)asm_list.size());
-        if (!has_pair[slot]) top_fill.push_back(slot);
-      };
-      add(slot_base[j], trow);
-      for (size_t u = 0; u < col[j].size(); ++u) add(slot_base[j] + 1 + (int32_t)u, -1);   // (rows below a separator column are separators too: fill only reaches ancestors)
-    }
-    s->ntop_slots = (int)top_slots.size(); s->ntop_tiles = (int)top_tiles.size(); s->ntop_fill = (int)top_fill.size();
-    // rows of y this rank contributes to the gather (and whose residual it can check: every tile of those rows is complete here):
-    // its own part; the separators' rows come from rank 0
-    for (int t = 0; t < nt; ++t) { const int p = tord.part_of[t]; row_mine[t] = p == h->rank || (p < 0 && h->rank == 0); }
+    s->ntop_slots = (int)hp.top_slots.size(); s->ntop_tiles = (int)hp.top_tiles.size(); s->ntop_fill = (int)hp.top_fill.size();
     // who adds the replicated terms (damping, gradient, identity padding) of a camera-side frame to its partial S: the rank that
     // owns the frame's part, rank 0 for the separators
     frame_lead.assign((size_t)nt * FT, 0.0);
-    for (int a = 0; a < nt * FT; ++a) frame_lead[a] = row_mine[a / FT] ? 1.0 : 0.0;
-    up.upload(&s->d_top_slots, top_slots); up.upload(&s->d_top_info, top_info); up.upload(&s->d_asm_ptr, asm_ptr); up.upload(&s->d_asm_list, asm_list);
-    up.upload(&s->d_top_tiles, top_tiles); up.upload(&s->d_row_mine, row_mine); up.upload(&s->d_top_fill, top_fill);
-    { std::vector<uint8_t> row_check((size_t)nt, 0); for (int t = 0; t < nt; ++t) row_check[t] = tord.part_of[t] == h->rank; up.upload(&s->d_row_check, row_check); }
-    { std::vector<uint8_t> row_sep((size_t)nt, 0); for (int t = 0; t < nt; ++t) row_sep[t] = tord.part_of[t] < 0; up.upload(&s->d_row_sep, row_sep); }
+    for (int a = 0; a < nt * FT; ++a) frame_lead[a] = hp.row_mine[a / FT] ? 1.0 : 0.0;
+    up.upload_ref(&s->d_top_slots, hp.top_slots); up.upload_ref(&s->d_top_info, hp.top_info); up.upload_ref(&s->d_asm_ptr, hp.asm_ptr); up.upload_ref(&s->d_asm_list, hp.asm_list);
+    up.upload_ref(&s->d_top_tiles, hp.top_tiles); up.upload_ref(&s->d_row_mine, hp.row_mine); up.upload_ref(&s->d_top_fill, hp.top_fill);
+    up.upload_ref(&s->d_row_check, hp.row_check); up.upload_ref(&s->d_row_sep, hp.row_sep);
     up.upload_const(&sv.frame_lead, frame_lead);
-    up.upload_ref(&s->d_tasks_a, s->tasks_a); up.upload_ref(&s->d_tasks_b, s->tasks_b);
-    up.upload_ref(&s->d_diag_info_sh, s->diag_info_sh); up.upload_ref(&s->d_sub_info_sh, s->sub_info_sh);
     // (+ with a second right-hand side: the parts' share of the separators' rows of it, and of the two dots — behind the tiles and the rhs rows)
     if ((rc = s_alloc(s, &s->topx_buf, (size_t)s->ntop_slots * kTile * kTile + (size_t)s->ntop_tiles * kTile + (two_rhs ? (size_t)s->ntop_tiles * kTile + 8 : 0)))) return rc;
     if ((rc = s_alloc(s, &s->ybuf, (size_t)sv.npad))) return rc;
@@ -1408,29 +1174,27 @@ int32_t build_solver_impl(rsba_handle* h) {
     if ((rc = s_alloc(s, &s->pp.cross, n6))) return rc;
     if ((rc = s_alloc(s, &s->pp.diag, n6))) return rc;
     std::vector<int32_t> tds(nt);
-    for (int t = 0; t < nt; ++t) tds[t] = slot_base[iperm[t]];
+    for (int t = 0; t < nt; ++t) tds[t] = hp.slot_base[hp.iperm[t]];
     if ((rc = s_upload_const(s, &s->pp.tile_diag_slot, tds))) return rc;
   }
   HIP_TRY(hipMemset(sv.scalars, 0, 16 * sizeof(double)));
   HIP_TRY(hipMemset(sv.chol_fail, 0, sizeof(int)));
   CholPlan& pl = s->plan;
-  pl.upd = s->d_upd; pl.diag_info = s->d_diag_info; pl.diag_ptr = s->d_diag_ptr; pl.diag_list = s->d_diag_list;
-  pl.sub_info = s->d_sub_info; pl.sub_ptr = s->d_sub_ptr; pl.sub_list = s->d_sub_list; pl.sub_col = s->d_sub_col; pl.diag_own = s->d_diag_own; pl.sub_own = s->d_sub_own;
-  pl.diag_fuse = s->d_diag_fuse; pl.sub_pub = s->d_sub_pub;
-  pl.back_info = s->d_back_info; pl.back_ptr = s->d_back_ptr; pl.back_list = s->d_back_list;
-  pl.tasks = s->d_tasks; pl.ntasks = (int)(s->tasks.size() / 2); pl.ndiag = (int)(s->diag_info.size() / 4);
+  pl.ntasks = (int)(hp.tasks.size() / 2); pl.ndiag = (int)(hp.diag_info.size() / 4);
   pl.ticket = s->d_dag_sync;
-  pl.nslots = sv.nslots; pl.nparts = parts;
-  pl.fwd_range = s->d_fwd_full; pl.diag_toprow = s->d_diag_toprow; pl.fwd2_minus = nullptr; pl.fwd2_partial = nullptr; pl.eta_tiles = nullptr; pl.eta_extra = nullptr; pl.eta_partial = nullptr;
+  pl.nslots = sv.nslots; pl.nparts = hp.nparts;
   if (sharded) {
-    s->plan_a = pl; s->plan_a.tasks = s->d_tasks_a; s->plan_a.ntasks = (int)(s->tasks_a.size() / 2);
-    s->plan_b = pl; s->plan_b.tasks = s->d_tasks_b; s->plan_b.ntasks = (int)(s->tasks_b.size() / 2);
+    s->plan_a = pl; s->plan_a.ntasks = (int)(hp.tasks_a.size() / 2);
+    s->plan_b = pl; s->plan_b.ntasks = (int)(hp.tasks_b.size() / 2);
     if (two_rhs) {
       double* tail = s->topx_buf + (size_t)s->ntop_slots * kTile * kTile + (size_t)s->ntop_tiles * kTile;
-      s->plan_a.fwd_range = s->d_fwd_a; s->plan_a.fwd2_partial = tail; s->plan_a.eta_tiles = s->d_row_check; s->plan_a.eta_partial = tail + (size_t)s->ntop_tiles * kTile;
-      s->plan_b.fwd_range = s->d_fwd_b; s->plan_b.fwd2_minus = tail; s->plan_b.eta_tiles = s->d_row_sep; s->plan_b.eta_extra = tail + (size_t)s->ntop_tiles * kTile;
+      s->plan_a.fwd2_partial = tail; s->plan_a.eta_tiles = s->d_row_check; s->plan_a.eta_partial = tail + (size_t)s->ntop_tiles * kTile;
+      s->plan_b.fwd2_minus = tail; s->plan_b.eta_tiles = s->d_row_sep; s->plan_b.eta_extra = tail + (size_t)s->ntop_tiles * kTile;
     }
-    s->plan_b.diag_info = s->d_diag_info_sh; s->plan_b.sub_info = s->d_sub_info_sh;   // (the parts' partial tiles have been summed in by the exchange)
+  }
+  {
+    CholPlan* const plans[3] = {&s->plan, &s->plan_a, &s->plan_b};
+    for (size_t i = 0; i < kNumPlanLists; ++i) for (int b = 0; b < (sharded ? 3 : 1); ++b) if (kPlanLists[i].plans & (1u << b)) plans[b]->*kPlanLists[i].field = s->d_plan_lists[i];
   }
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
@@ -1442,8 +1206,8 @@ int32_t build_solver_impl(rsba_handle* h) {
   // the elimination tree holds more tasks than there are CUs (C5: 380 per level), and change nothing where the chain dominates (C4: 116 per
   // level, 1.62 ms either way).  RSBA_CHOL_WGS overrides, capped at two per CU.
   s->dag_workgroups = std::max(1, std::min(pl.ntasks, std::max(cus, 1)));
-  const int64_t my_tasks = s->sharded ? (int64_t)s->plan_a.ntasks + s->plan_b.ntasks : (int64_t)pl.ntasks;   // (what THIS rank runs)
-  if (s->nlev > 0 && my_tasks > (int64_t)s->nlev * std::max(cus, 1)) { s->dag_workgroups = std::max(1, std::min(pl.ntasks, 2 * std::max(cus, 1))); s->dag_one_per_cu = false; }
+  const int64_t my_tasks = sharded ? (int64_t)s->plan_a.ntasks + s->plan_b.ntasks : (int64_t)pl.ntasks;   // (what THIS rank runs)
+  if (hp.nlev > 0 && my_tasks > (int64_t)hp.nlev * std::max(cus, 1)) { s->dag_workgroups = std::max(1, std::min(pl.ntasks, 2 * std::max(cus, 1))); s->dag_one_per_cu = false; }
   // A small plan (100 cameras: 267 tasks, ~15 per elimination level) is served better by a quarter as many workgroups as tasks — fewer
   // pollers around the chain: 0.428 -> 0.418 ms per iteration, three runs each — and leaves the rest of the chip to other streams.
   if (pl.ntasks <= 512) s->dag_workgroups = std::max(1, std::min(s->dag_workgroups, std::max(64, pl.ntasks / 4)));
@@ -1456,19 +1220,12 @@ int32_t build_solver_impl(rsba_handle* h) {
   tick("allocations");
   if (dbg_plan)
     std::fprintf(stderr, "[rsba plan] tiles %d, factor tiles %d, levels %d, tasks %d (partials %d); tile pairs %d, entries %lld, schur chunks %d\n", nt, sv.nslots,
-                 s->nlev, pl.ntasks, parts, sv.ntp, (long long)s->num_pairs, sv.nchunk);
+                 hp.nlev, pl.ntasks, hp.nparts, sv.ntp, (long long)s->num_pairs, sv.nchunk);
   const char* lv = std::getenv("RSBA_CHOL_LEVELS");
   s->use_levels = lv && lv[0] == '1';
   {
     DagArgs host_args{sv, pl};
-    {
-      std::vector<int32_t> st2(2 * (size_t)sv.nslots);
-      for (int k = 0; k < nt; ++k) {
-        st2[2 * (size_t)slot_base[k]] = perm[k]; st2[2 * (size_t)slot_base[k] + 1] = perm[k];
-        for (size_t u = 0; u < col[k].size(); ++u) { st2[2 * (size_t)(slot_base[k] + 1 + u)] = perm[col[k][u]]; st2[2 * (size_t)(slot_base[k] + 1 + u) + 1] = perm[k]; }
-      }
-      if ((rc = s_upload(s, &s->d_slot_tiles, st2))) return rc;
-    }
+    if ((rc = s_upload(s, &s->d_slot_tiles, hp.slot_tiles))) return rc;
     if ((rc = s_alloc(s, &s->d_verify, 2 * (size_t)sv.npad))) return rc;
     if ((rc = s_alloc(s, &s->verify_b, (size_t)sv.npad))) return rc;
     HIP_TRY(dev_stream_acquire(&s->vstream));
@@ -1497,17 +1254,13 @@ int32_t build_solver_impl(rsba_handle* h) {
   }
   {
     rsba_plan_stats& ps = s->stats;
-    ps.tiles = nt; ps.factor_tiles = sv.nslots; ps.levels = s->nlev; ps.tasks = pl.ntasks;
+    ps.tiles = nt; ps.factor_tiles = sv.nslots; ps.levels = hp.nlev; ps.tasks = pl.ntasks;
     ps.schur_entries = nent; ps.schur_chunks = sv.nchunk;
     // block products of the Schur complement that are not structurally zero: per entry (frames present on the I side) x (on the J side),
     // summed in the pass that forms the entries' block masks
     ps.schur_block_products = 0;
     for (int64_t v : products_part) ps.schur_block_products += v;
-    // tile factorisation: per DIAG item its contributors (lower half of L L^T: T^3 each) + potrf and inverse (T^3 / 3 each);
-    // per SUB item 2 T^3 per contributor + the product with W (T^3); forward / backward solve 2 T^2 per factor tile, twice
-    const int64_t T3 = (int64_t)kTile * kTile * kTile;
-    ps.cholesky_flops = T3 * ((int64_t)(s->diag_list.size() / 2) + 2 * (int64_t)(s->sub_list.size() / 2) + (int64_t)(s->sub_info.size() / 4)) +
-                        2 * T3 / 3 * (int64_t)(s->diag_info.size() / 4) + 4 * (int64_t)kTile * kTile * ((int64_t)sv.nslots + nt);
+    ps.cholesky_flops = hp.cholesky_flops;
     ps.exchange_doubles = (int64_t)s->exch_tiles * kTile * kTile + sv.npad;   // exchange (2) of a sharded solve: the plan's tile pairs | rhs (the fill-in tiles of the factor's layout stay home)
     ps.schur_groups = sv.ngroups;
     ps.schur_group_bytes = pt_total * (int64_t)sizeof(double);
@@ -1517,12 +1270,8 @@ int32_t build_solver_impl(rsba_handle* h) {
     if (sharded) {   // ... or, when every rank factors its own part: the separators' tiles | their rows of the rhs, and the gather of the step
       ps.exchange_doubles = (int64_t)s->ntop_slots * kTile * kTile + (int64_t)s->ntop_tiles * kTile + sv.npad;
       ps.separator_tiles = s->ntop_tiles; ps.separator_factor_tiles = s->ntop_slots;
-      ps.local_tasks = (int64_t)(s->tasks_a.size() / 2); ps.separator_tasks = (int64_t)(s->tasks_b.size() / 2);
-      // the two dependency chains: elimination levels inside this rank's part, and levels that hold a separator column
-      int lmax = -1; std::vector<uint8_t> sep_level((size_t)nlev, 0);
-      for (int j = 0; j < nt; ++j) { if (cpart[j] == h->rank) lmax = std::max(lmax, level[j]); else if (cpart[j] < 0) sep_level[level[j]] = 1; }
-      ps.local_levels = lmax + 1; ps.separator_levels = 0;
-      for (uint8_t b : sep_level) ps.separator_levels += b;
+      ps.local_tasks = (int64_t)(hp.tasks_a.size() / 2); ps.separator_tasks = (int64_t)(hp.tasks_b.size() / 2);
+      ps.local_levels = hp.local_levels; ps.separator_levels = hp.separator_levels;
     }
   }
   sv.ctl = nullptr;
@@ -1676,9 +1425,9 @@ int32_t reduce_system(rsba_handle* h, double radius) {
   }
   // exchange (2): partial reduced camera systems -> the full one on every rank (then factored redundantly) — unless every rank
   // factors its own part: then only the separators travel, between the two launches of the factorisation (solve_reduced_system)
-  if (s->sharded && !s->sharded_off && !s->use_levels) return RSBA_OK;
+  if (s->hp.sharded && !s->sharded_off && !s->use_levels) return RSBA_OK;
   PhaseScope ps(h, RSBA_PHASE_EXCHANGE);
-  if (s->sharded && s->ntop_fill) HIP_TRY(launch_zero_tiles(sv.S, s->d_top_fill, s->ntop_fill, st));   // (a sharded solve left its reduced values in the fill-only separator tiles)
+  if (s->hp.sharded && s->ntop_fill) HIP_TRY(launch_zero_tiles(sv.S, s->d_top_fill, s->ntop_fill, st));   // (a sharded solve left its reduced values in the fill-only separator tiles)
   if (h->allreduce && s->exch_slots) {   // only the tiles that can be non-zero travel (the fill-in tiles of the layout are zero on every rank)
     const int64_t count = (int64_t)s->exch_tiles * kTile * kTile + sv.npad;
     HIP_TRY(launch_exchange_pack(sv, s->exch_slots, s->exch_tiles, s->exch_buf, false, st));
@@ -1717,11 +1466,11 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays = false) {
     sv.Lf = c + s->cell_off[0]; sv.chol_part = c + s->cell_off[1]; sv.Winv = c + s->cell_off[2]; sv.zv = c + s->cell_off[3]; sv.yv = sv.zv + sv.npad; sv.Xpub = c + s->cell_off[4];
     if (sv.zv2) { sv.zv2 = sv.zv + 2 * sv.npad; sv.ceta = sv.zv + 3 * sv.npad; }
     s->d_dag_args = s->d_dag_args2[now];
-    if (s->sharded && !s->sharded_off) {
+    if (s->hp.sharded && !s->sharded_off) {
       // launch A: the columns of this rank's part, from its own partial S — complete for them: every point that sees one of its tiles is here
       HIP_TRY(launch_chol_dag(sv, s->plan_a, s->d_dag_args_a[now], std::min(s->dag_workgroups, std::max(1, s->plan_a.ntasks)), s->dag_one_per_cu, st));
       // exchange (2'): the separators' tiles, each rank's share less what its part subtracts from them, summed over the ranks
-      const int64_t count = (int64_t)s->ntop_slots * kTile * kTile + (int64_t)s->ntop_tiles * kTile + (s->two_rhs ? (int64_t)s->ntop_tiles * kTile + 8 : 0);   // (+ the second right-hand side's share: launch A left it behind the rows of the first)
+      const int64_t count = (int64_t)s->ntop_slots * kTile * kTile + (int64_t)s->ntop_tiles * kTile + (s->hp.two_rhs ? (int64_t)s->ntop_tiles * kTile + 8 : 0);   // (+ the second right-hand side's share: launch A left it behind the rows of the first)
       ps.stop();
       {
         PhaseScope pe(h, RSBA_PHASE_EXCHANGE);
@@ -1747,27 +1496,27 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays = false) {
     if (s->verify_dag) {
       // (rhs_stays: nobody writes sv.rhs before the check has been waited for — the LM iteration without a free ratio; otherwise the check gets a copy)
       const double* b_rhs = sv.rhs;
-      if (s->two_rhs) { HIP_TRY(launch_border_combine(s->verify_b, sv.rhs, s->border, 0.0, sv.npad, st, s->ratio4 + kRtC)); b_rhs = s->verify_b; }   // what was solved for: g - (s eta) b
+      if (s->hp.two_rhs) { HIP_TRY(launch_border_combine(s->verify_b, sv.rhs, s->border, 0.0, sv.npad, st, s->ratio4 + kRtC)); b_rhs = s->verify_b; }   // what was solved for: g - (s eta) b
       else if (!rhs_stays) { HIP_TRY(hipMemcpyAsync(s->verify_b, sv.rhs, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st)); b_rhs = s->verify_b; }
       HIP_TRY(hipEventRecord(s->ev_solved, st));
       HIP_TRY(hipStreamWaitEvent(s->vstream, s->ev_solved, 0));
       HIP_TRY(launch_chol_verify(sv, s->d_slot_tiles, b_rhs, s->d_verify, s->d_verify + sv.npad, 1e-7, sv.scalars + kDagSuspect, s->vstream,
-                                 s->sharded && !s->sharded_off ? s->d_row_check : nullptr));   // (a rank of a sharded factorisation holds the whole of its part's rows of S, nothing else)
+                                 s->hp.sharded && !s->sharded_off ? s->d_row_check : nullptr));   // (a rank of a sharded factorisation holds the whole of its part's rows of S, nothing else)
       HIP_TRY(hipEventRecord(s->ev_verified, s->vstream));
       s->verify_pending = true;
     }
   } else {
-    for (int l = 0; l < s->nlev; ++l) {
-      const int d0 = s->lev_diag_ptr[l], d1 = s->lev_diag_ptr[l + 1], t0 = s->lev_sub_ptr[l], t1 = s->lev_sub_ptr[l + 1];
-      const int u0 = s->lev_upd_ptr[l], u1 = s->lev_upd_ptr[l + 1];
+    for (int l = 0; l < s->hp.nlev; ++l) {
+      const int d0 = s->hp.lev_diag_ptr[l], d1 = s->hp.lev_diag_ptr[l + 1], t0 = s->hp.lev_sub_ptr[l], t1 = s->hp.lev_sub_ptr[l + 1];
+      const int u0 = s->hp.lev_upd_ptr[l], u1 = s->hp.lev_upd_ptr[l + 1];
       HIP_TRY(launch_chol_level(sv, s->plan, kTaskUpdate, u0, u1 - u0, st));
       HIP_TRY(launch_chol_level(sv, s->plan, kTaskDiag, d0, d1 - d0, st));
-      if (s->two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskFwd2, d0, d1 - d0, st));
+      if (s->hp.two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskFwd2, d0, d1 - d0, st));
       HIP_TRY(launch_chol_level(sv, s->plan, kTaskSub, t0, t1 - t0, st));
     }
-    if (s->two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskEta, 0, 1, st));
-    for (int l = s->nlev - 1; l >= 0; --l) {
-      const int d0 = s->lev_diag_ptr[l], d1 = s->lev_diag_ptr[l + 1];
+    if (s->hp.two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskEta, 0, 1, st));
+    for (int l = s->hp.nlev - 1; l >= 0; --l) {
+      const int d0 = s->hp.lev_diag_ptr[l], d1 = s->hp.lev_diag_ptr[l + 1];
       HIP_TRY(launch_chol_level(sv, s->plan, kTaskBack, d0, d1 - d0, st));
     }
   }
@@ -1782,8 +1531,8 @@ int32_t solve_again(rsba_handle* h, const double* b2, const double** v_out) {
   PhaseScope ps(h, RSBA_PHASE_CHOLESKY);
   if (!s->use_levels) HIP_TRY(launch_chol_solve(sv, s->plan, s->d_dag_args, b2, s->zy2, s->d_dag_sync + 2, s->dag_workgroups, st));
   else {   // the same tasks, one launch per level: no polling (what a suspect persistent result is redone with)
-    for (int l = 0; l < s->nlev; ++l) HIP_TRY(launch_chol_solve_level(sv, s->plan, false, s->lev_diag_ptr[l], s->lev_diag_ptr[l + 1] - s->lev_diag_ptr[l], b2, s->zy2, st));
-    for (int l = s->nlev - 1; l >= 0; --l) HIP_TRY(launch_chol_solve_level(sv, s->plan, true, s->lev_diag_ptr[l], s->lev_diag_ptr[l + 1] - s->lev_diag_ptr[l], b2, s->zy2, st));
+    for (int l = 0; l < s->hp.nlev; ++l) HIP_TRY(launch_chol_solve_level(sv, s->plan, false, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
+    for (int l = s->hp.nlev - 1; l >= 0; --l) HIP_TRY(launch_chol_solve_level(sv, s->plan, true, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
   }
   *v_out = s->zy2 + sv.npad;
   if (!s->use_levels && s->verify_dag) {
@@ -1807,7 +1556,7 @@ int32_t factor_and_solve(rsba_handle* h, double radius, RatioStep* ratio = nullp
   if (ratio) HIP_TRY(launch_ratio_prepare(s->ratio4, ratio->diag, ratio->gs, ratio->scale, st));
   int32_t rc = reduce_system(h, radius);
   if (rc) return rc;
-  if ((rc = solve_reduced_system(h, /*rhs_stays=*/!s->two_rhs))) return rc;
+  if ((rc = solve_reduced_system(h, /*rhs_stays=*/!s->hp.two_rhs))) return rc;
   if (ratio) {
     HIP_TRY(hipMemcpyAsync(&ratio->eta, s->ratio4 + kRtEta, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2017,7 +1766,7 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
   struct ShardedOff { Solver* s; bool was; ~ShardedOff() { s->sharded_off = was; } } sharded_guard{s, s->sharded_off};
   s->sharded_off = true;
   if ((rc = reduce_system(h, 1e300))) return rc;
-  if (s->two_rhs) HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));   // (a plan that carries the ratio's column through its factorisation: s eta = 0 here — the plain solves S y = e_k)
+  if (s->hp.two_rhs) HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));   // (a plan that carries the ratio's column through its factorisation: s eta = 0 here — the plain solves S y = e_k)
   std::vector<double> col((size_t)CD * CD, 0.0);
   const double one = 1.0;
   // CD (+1 with the border) solves through the factorisation; the DAG driver's verification flag is sticky, so one read after
@@ -2159,7 +1908,7 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
       if (FILE* f = std::fopen(path, "wb")) {
         const int32_t n = sl->plan.ntasks;
         std::fwrite(&n, sizeof(n), 1, f);
-        std::fwrite(sl->tasks.data(), sizeof(int32_t), sl->tasks.size(), f);
+        std::fwrite(sl->hp.tasks.data(), sizeof(int32_t), sl->hp.tasks.size(), f);
         std::fwrite(tr.data(), sizeof(long long), tr.size(), f);
         std::fclose(f);
       }

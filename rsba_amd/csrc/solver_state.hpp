@@ -13,12 +13,12 @@
 
 #include "../../include/rsba_amd.h"
 #include "device_state.hpp"
+#include "chol_plan.hpp"   // kTile, the task kinds
 
 namespace rsba {
 
 constexpr int kSchurChunk = 512;   // entries per workgroup of the Schur kernel (its four waves take every fourth)
 constexpr int kMaxRankSlots = 64;   // per-rank slots behind the camera exchange's payload (more ranks than this: the gradient maximum takes its own all-reduce)
-constexpr int kTile = 48;   // Cholesky tile: 4 rolling-shutter frames (12 unknowns) or 8 global-shutter frames
 constexpr int kGroupFull = 3 * kTile;   // doubles of a P-record group in full form: [3][kTile]
 // ... and factored (two-pose frames: the 12 camera-side rows of a frame are (1 - tau) q | tau q with q = Jq^T Jp L^-T, 6 x 3):
 //   [c][16] sources 0..15 of coordinate c = 0, 1, 2 (source s = 6 x frame-in-tile + pose coordinate) | [c][8] sources 16..23 | tau[4] | pad[4]
@@ -156,7 +156,7 @@ hipError_t allow_dynamic_lds_impl(const void* kernel, size_t bytes);   // capi.h
 template <class K>
 inline hipError_t allow_dynamic_lds(K kernel, size_t bytes) { return allow_dynamic_lds_impl(reinterpret_cast<const void*>(kernel), bytes); }
 
-// Cholesky task plan (cholesky.hip): flattened work lists of the symbolic phase, device pointers
+// Cholesky task plan (cholesky.hip): the work lists of chol_plan.hpp, device pointers
 struct CholPlan {
   const int32_t *upd, *diag_info, *diag_ptr, *diag_list, *sub_info, *sub_ptr, *sub_list, *sub_col, *diag_own, *sub_own, *back_info, *back_ptr, *back_list;
   const int32_t* diag_fuse;  // per DIAG item: the SUB item of its last contributor, whose product with W the DIAG task forms itself (-1: none)
@@ -176,9 +176,6 @@ struct CholPlan {
   const double* eta_extra;    // [2] + the other columns' share, summed by the exchange (null: none)
   double* eta_partial;        // non-null: the task only leaves its two dots here (launch A of a sharded factorisation)
 };
-
-// FWD2: item = DIAG item whose column's z2 it forms; FWD2P: the same item's sum over THIS rank's part only (sharded: what travels)
-enum : int { kTaskUpdate = 0, kTaskDiag = 1, kTaskSub = 2, kTaskBack = 3, kTaskFwd2 = 4, kTaskEta = 5, kTaskFwd2P = 6 };
 
 // per-pose priors (kernels_pose_prior.hip): linearisation of the priorPoses coordinates [pp_count][6] and where the pose
 // entries sit in the packed tiles

@@ -35,6 +35,21 @@ inline int plan_leaf_size(int nparts, int nt) {
   return k;
 }
 
+constexpr int kTile = 48;   // Cholesky tile: 4 rolling-shutter frames (12 unknowns) or 8 global-shutter frames
+
+// Where the camera-side blocks of the reduced system sit in its tiles — the ONE statement of it (the plan, its vote, the cut of
+// rsba_partition_points and the tests' debug entries must agree): the real frames first, then, with intrinsics as parameter blocks,
+// NPF = ceil(9 / CD) pseudo frames per block (solver_state.hpp), FT frames to a tile.
+struct TileLayout {
+  int FR, CD, FT, NIB, NPF, F, nt;   // real frames; unknowns per frame; frames per tile; intrinsics blocks; pseudo frames per block; FR + pseudo frames; tiles
+  TileLayout(int poses_per_frame, int num_frames, bool calibrated, int num_intrinsics)
+      : FR(num_frames), CD(6 * poses_per_frame), FT(kTile / CD), NIB(calibrated ? 0 : num_intrinsics), NPF(calibrated ? 0 : (9 + CD - 1) / CD),
+        F(FR + NIB * NPF), nt((F + FT - 1) / FT) {}
+  int frame_tile(int f) const { return f / FT; }
+  int pseudo_frame(int c, int v) const { return FR + c * NPF + v; }   // pseudo frame v of intrinsics block c, as a camera-side block
+  int pseudo_tile(int c, int v) const { return pseudo_frame(c, v) / FT; }
+};
+
 struct TileOrder {
   std::vector<int32_t> perm;      // perm[new] = old tile
   std::vector<int32_t> leaf_of;   // per old tile: leaf of the dissection, -1 = a separator / the dense border
