@@ -14,7 +14,12 @@ iteration (HIP events recorded by the solver, rsba_get_phase_times).  At N = 1 t
 ("cpu_baseline": evaluation at 1 and at the best of all / half / quarter of the host's threads, and its LM iteration) and
 the rows next to the path add bounded wall-clock figures under "next_rows".
 
-    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR]
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the result line
+(metric, value, ms_per_step, the workload).  Everything else — "roofline", "lm" and "lm_headline", "roofline_lm",
+"cpu_baseline", "next_rows", "shard_eval_n8" (the kernel on each of eight shards), "device_memory" — takes runs of its
+own after the timed region and is measured with --full only; the timed region is the same either way.
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -408,14 +413,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C4", choices=["C2", "C4", "C5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lm", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what is not the headline: the kernel's roofline, the LM iteration and its "
+                                                        "phases, the CPU baseline, the rows next to the path, the 8-shard prediction, device memory")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-lm", action="store_true", help="with --full: leave the LM iteration out")
     ap.add_argument("--lm-iters", type=int, default=12)
-    ap.add_argument("--no-next-rows", action="store_true")
+    ap.add_argument("--no-next-rows", action="store_true", help="with --full: leave the rows next to the path and the 8-shard prediction out")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64, under 64 MB in all)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline alone
+        args.no_lm = args.no_cpu_baseline = args.no_next_rows = True
 
     import torch
     import torch.distributed as dist
@@ -520,23 +529,30 @@ def main():
     total_obs = float(n_obs.item())
     assert int(total_obs) == full.num_observations, (total_obs, full.num_observations)
 
-    # dominant kernel, HIP events on the stream it is launched on (rank 0's shard)
-    kernel_ms = dp.time_evaluate(True, warmup=50, iters=max(50, args.steps))
-    abytes = algorithmic_bytes(prob)
-    achieved = abytes / (kernel_ms * 1e-3) / 1e9
-    # HBM traffic of the same kernel on the same workload from the committed PMC passes (separate
-    # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of this command; tools/profile_round.sh)
-    traffic, traffic_src, traffic_prov = None, None, None
-    if world == 1:
-        key = "hbm_bytes_per_launch" if args.config == "C4" else f"hbm_bytes_per_launch_{args.config}"
-        prof = sorted(p for p in os.listdir(os.path.join(ROOT, "profiles")) if os.path.exists(os.path.join(ROOT, "profiles", p, "pmc_summary.json")))
-        for pr in reversed(prof):
-            with open(os.path.join(ROOT, "profiles", pr, "pmc_summary.json")) as fh:
-                pm = json.load(fh)
-            if pm.get(key):
-                traffic, traffic_src = pm[key], f"profiles/{pr}/pmc_summary.json (2*FETCH_SIZE + WRITE_SIZE, calibrated)"
-                traffic_prov = provenance(pm, f"profiles/{pr}/pmc_summary.json")
-                break
+    roofline = None
+    if args.full:
+        # dominant kernel, HIP events on the stream it is launched on (rank 0's shard)
+        kernel_ms = dp.time_evaluate(True, warmup=50, iters=max(50, args.steps))
+        abytes = algorithmic_bytes(prob)
+        achieved = abytes / (kernel_ms * 1e-3) / 1e9
+        # HBM traffic of the same kernel on the same workload from the committed PMC passes (separate
+        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of this command; tools/profile_round.sh)
+        traffic, traffic_src, traffic_prov = None, None, None
+        if world == 1:
+            key = "hbm_bytes_per_launch" if args.config == "C4" else f"hbm_bytes_per_launch_{args.config}"
+            prof = sorted(p for p in os.listdir(os.path.join(ROOT, "profiles")) if os.path.exists(os.path.join(ROOT, "profiles", p, "pmc_summary.json")))
+            for pr in reversed(prof):
+                with open(os.path.join(ROOT, "profiles", pr, "pmc_summary.json")) as fh:
+                    pm = json.load(fh)
+                if pm.get(key):
+                    traffic, traffic_src = pm[key], f"profiles/{pr}/pmc_summary.json (2*FETCH_SIZE + WRITE_SIZE, calibrated)"
+                    traffic_prov = provenance(pm, f"profiles/{pr}/pmc_summary.json")
+                    break
+        kname = "rsba::eval_kernel<%s,%d,1>" % ("true" if prob.calibrated else "false", prob.poses_per_frame)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic, "traffic_source": traffic_src, "traffic_provenance": traffic_prov, "kernel": kname, "kernel_ms": kernel_ms,
+                    "algorithmic_bytes_per_launch": abytes, "bytes_per_observation": abytes / max(1, prob.num_observations),
+                    "rank": 0}
 
     lm, lm_roof = None, None
     lm_hung = False
@@ -631,7 +647,6 @@ def main():
 
     out = None
     if rank == 0:
-        kname = "rsba::eval_kernel<%s,%d,1>" % ("true" if prob.calibrated else "false", prob.poses_per_frame)
         out = {
             "metric": "residual+Jacobian evals/sec", "value": total_obs * args.steps / elapsed, "unit": "obs evals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "untimed_clock_ramp_steps": 200, "ms_per_step": elapsed / args.steps * 1e3,
@@ -641,12 +656,9 @@ def main():
                                    + ("calibrated" if full.calibrated else f"shared intrinsics as a parameter block, Huber({full.huber_a:g})"),
                        "observations_total": int(total_obs), "observations_this_rank": int(prob.num_observations), "jacobian_cols": prob.jacobian_cols,
                        "partition": partition},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_provenance": traffic_prov, "kernel": kname, "kernel_ms": kernel_ms,
-                         "algorithmic_bytes_per_launch": abytes, "bytes_per_observation": abytes / max(1, prob.num_observations),
-                         "rank": 0},
-            "roofline_lm": lm_roof,
         }
+    if rank == 0 and args.full:
+        out["roofline"], out["roofline_lm"] = roofline, lm_roof
         try:
             free_b, total_b = torch.cuda.mem_get_info(local_rank)
             out["device_memory"] = {"in_use_bytes": int(total_b - free_b), "total_bytes": int(total_b),

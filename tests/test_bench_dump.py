@@ -15,6 +15,32 @@ def test_bench_refuses_a_run_without_timed_steps():
     assert r.returncode == 2 and "--steps" in r.stderr
 
 
+def test_bench_has_the_full_option():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
+@pytest.mark.gpu
+def test_a_plain_run_reports_the_headline_alone_and_full_adds_the_rest():
+    """Without --full the line carries the headline and its workload, and nothing that takes a run of its own after the timed steps;
+    with --full the same command also prices the kernel and the LM iteration (C2: the small scene)."""
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--config", "C2", *extra],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    moved = {"roofline", "roofline_lm", "lm", "lm_headline", "cpu_baseline", "next_rows", "shard_eval_n8", "device_memory"}
+    plain = run()
+    assert not moved & set(plain)
+    assert plain["metric"] == "residual+Jacobian evals/sec" and plain["unit"] == "obs evals/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    assert plain["steps"] == 5 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - plain["config"]["observations_total"] / (plain["ms_per_step"] * 1e-3)) <= 1e-9 * plain["value"]
+    full = run("--full", "--lm-iters", "6", "--no-cpu-baseline")
+    assert {"roofline", "roofline_lm", "lm", "lm_headline", "device_memory"} <= set(full)
+    assert {k: v for k, v in full.items() if k in plain and k not in ("value", "ms_per_step")} == {k: v for k, v in plain.items() if k not in ("value", "ms_per_step")}
+    assert full["roofline"]["kernel_ms"] > 0 and "error" not in full["lm"] and full["lm_headline"]["ms_per_lm_iteration"] > 0
+
+
 @pytest.mark.gpu
 def test_dumped_outputs_are_the_evaluation_of_the_headline_scene(tmp_path):
     """C4 (2.04 M observations) does not fit the budget: a seeded sample is written, with its indices; every sampled row equals

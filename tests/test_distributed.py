@@ -117,7 +117,7 @@ def run_bench(nproc, config, extra_env=None, lm_iters=6, timeout=1200):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RSBA_BENCH_TEST_ONE_GPU="1", **(extra_env or {}))
-    args = ["--gpus", str(nproc), "--steps", "5", "--warmup", "1", "--config", config, "--no-cpu-baseline", "--no-next-rows", "--lm-iters", str(lm_iters)]
+    args = ["--full", "--gpus", str(nproc), "--steps", "5", "--warmup", "1", "--config", config, "--no-cpu-baseline", "--no-next-rows", "--lm-iters", str(lm_iters)]
     cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args if nproc == 1 else \
           [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py")] + args
@@ -158,7 +158,7 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(tmp_path):
         with socket.socket() as s:
             s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RSBA_BENCH_TEST_ONE_GPU="1")
-        args = ["--gpus", str(nproc), "--steps", "5", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--no-next-rows", "--lm-iters", "6"]
+        args = ["--full", "--gpus", str(nproc), "--steps", "5", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--no-next-rows", "--lm-iters", "6"]
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args if nproc == 1 else \
               [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.join(ROOT, "bench.py")] + args

@@ -6,10 +6,10 @@ R=${1:-r06}
 OUT=gpurun_out/$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --steps 50 --warmup 5 --lm-iters 12 > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --config C5 --steps 20 --warmup 3 --lm-iters 8 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+python bench.py --full --steps 50 --warmup 5 --lm-iters 12 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --config C5 --steps 20 --warmup 3 --lm-iters 8 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 for C in C4 C5; do
-  B="python bench.py --config $C --steps 30 --warmup 5 --no-cpu-baseline --no-next-rows --lm-iters 12"
+  B="python bench.py --full --config $C --steps 30 --warmup 5 --no-cpu-baseline --no-next-rows --lm-iters 12"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$C -o t -- $B > $OUT/trace_$C.log 2>&1
   cp $OUT/trace_$C/t_kernel_stats.csv $OUT/kernel_stats_$C.csv; rm -rf $OUT/trace_$C
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$C -o f -- $B --no-lm > $OUT/pmc_fetch_$C.log 2>&1
@@ -55,7 +55,7 @@ for C in C4 C5; do
   tools/pmc_pass.sh $OUT/pmc_lds_$C "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" python tools/lm_time.py $C $IT
 done
 python tools/pmc_valu_summary.py $OUT
-python bench.py --config C2 --steps 50 --warmup 5 --lm-iters 12 --no-cpu-baseline --no-next-rows > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python bench.py --full --config C2 --steps 50 --warmup 5 --lm-iters 12 --no-cpu-baseline --no-next-rows > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 ./tools/hbm_calib > $OUT/hbm_calib.txt 2>&1
 ./tools/mfma_f64_rate > $OUT/mfma_f64_rate.txt 2>&1
 python - "$OUT" <<'PY'
