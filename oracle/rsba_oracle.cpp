@@ -911,7 +911,9 @@ int32_t orc_pose_covariance(const orc_problem* p, int32_t frame, double* cov) {
   if (!reduced_system(E, pc, E.J, E.r, D2, S, rhs, Vinv, bp)) return 0;
   // free camera-side coordinates
   std::vector<int64_t> freec;
-  for (int64_t a = 0; a < nc; ++a) if (!E.colmask[a]) freec.push_back(a);
+  // (a camera-side block that no residual touches — a frame without observations or priors — is not a parameter block of the program:
+  // its row of S is exactly zero, and it is left out like a fixed coordinate)
+  for (int64_t a = 0; a < nc; ++a) if (!E.colmask[a] && S.get(a, a) != 0.0) freec.push_back(a);
   const int64_t nf = (int64_t)freec.size();
   std::vector<double> A((size_t)nf * nf);
   for (int64_t a = 0; a < nf; ++a) for (int64_t b = 0; b < nf; ++b) A[a * nf + b] = S.get(freec[a], freec[b]);

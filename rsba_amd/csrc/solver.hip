@@ -1803,8 +1803,10 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
   }
   s->use_levels = levels_before;
   int fail = 0, nfail = 0;
+  std::vector<double> ud(CD, 0.0);   // diag(U) of the frame: exactly zero where no residual touches the coordinate
   HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ud.data(), sv.udiag + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (nfail) return rsba_set_error(RSBA_ERR_EVALUATION_FAILED, "residual and Jacobian evaluation failed");
   if (fail) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "J^T J is rank deficient (fix the gauge): no covariance, as ceres::Covariance::Compute returns false");
@@ -1815,7 +1817,9 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
     border_scale = 1.0 / schur;
   }
   for (int a = 0; a < CD; ++a) for (int b = 0; b < CD; ++b) {
-    const double ma = h->mask_pose[(size_t)frame * CD + a], mb = h->mask_pose[(size_t)frame * CD + b];
+    // (a coordinate no residual touches — a frame without observations or priors — is not a parameter of the program: like a fixed
+    // one it sits in S as a vanishing, decoupled diagonal, whose inverse is not a covariance)
+    const double ma = ud[a] != 0.0 ? h->mask_pose[(size_t)frame * CD + a] : 0.0, mb = ud[b] != 0.0 ? h->mask_pose[(size_t)frame * CD + b] : 0.0;
     cov[(size_t)a * CD + b] = (ma != 0.0 && mb != 0.0) ? col[(size_t)b * CD + a] + (s->border ? vf[a] * vf[b] * border_scale : 0.0) : 0.0;
   }
   return RSBA_OK;

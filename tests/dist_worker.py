@@ -2,6 +2,7 @@
    python -m torch.distributed.run --nproc-per-node 2 ... tests/dist_worker.py <mode> <outdir>
 mode "cpu": host-side exchange logic over gloo, partial blocks from the oracle (no GPU needed)
 mode "step:...": one iteration of the sharded solve, the solved parameters written for a comparison with a host reference
+mode "cov:...": pose covariance blocks on a handle with an exchange attached, then one iteration on that handle and on a fresh one
 mode "gpu": the sharded on-device LM solve, both ranks on GPU 0, exchange staged through gloo ("gpu_priors": with motion priors,
 "gpu_free_ratio": with a free interFrameRatio, "gpu_pose_priors": with GoodPosePrior blocks)"""
 import json
@@ -160,6 +161,60 @@ def step_mode(mode, outdir, rank, world, dist, torch):
     dist.destroy_process_group()
 
 
+def sharded_cov_frames(full):
+    """The frames a "cov:" mode asks for, the same on 2 and 4 ranks: the first free frame, the first frame of the first top-separator
+    tile of the 2-rank and of the 4-rank cut (rsba_debug_partition_tiles: host only, instrumented library), the frame before the
+    2-rank one (inside a part) and the last frame."""
+    from helpers import partition_tiles
+    FT, F = 48 // (6 * full.poses_per_frame), full.num_frames
+    out = {1, F - 1}
+    for world in (2, 4):
+        part_of = partition_tiles(full, world)[: (F + FT - 1) // FT]           # (real frames' tiles: the pseudo tiles lie behind them)
+        sep = np.flatnonzero(part_of < 0)
+        assert len(sep), "the cut has a separator among the real frames' tiles"
+        out.add(int(sep[0]) * FT)
+        if world == 2:
+            out.add(int(sep[0]) * FT - 1)
+    return sorted(out)
+
+
+def cov_mode(mode, outdir, rank, world, dist, torch):
+    """"cov:<config>[:flags]": the covariance blocks of sharded_cov_frames on a handle with an exchange attached (every rank asks for
+    the same frames in the same order: the call sums the replicated reduced system over the ranks), the plan's sharded flag before
+    and after, then ONE iteration on that handle and the same iteration on a fresh handle that never computed a covariance."""
+    from lm_step_cases import ONE_STEP
+    from rsba_amd import capi
+    from rsba_amd.distributed import attach
+    cfg, flags = mode.split(":")[1], mode.split(":")[2:]
+    full = nd_problem(cfg, flags)
+    frames = sharded_cov_frames(full)
+    owner, _ = capi.partition_points(full, world)
+    torch.cuda.set_device(0)
+    solved = []
+    for with_cov in (True, False):
+        shard = full.shard(rank, world, owner)
+        dp = capi.DeviceProblem(shard, device=0)
+        attach(dp)
+        before = dp.plan_stats()["sharded_factorisation"]
+        if with_cov:
+            cov = np.stack([dp.pose_covariance(f) for f in frames])
+            again = dp.pose_covariance(frames[0])
+            after = dp.plan_stats()["sharded_factorisation"]
+        s, tr = dp.solve(capi.default_options(**ONE_STEP))
+        sharded_solve = dp.plan_stats()["sharded_factorisation"]
+        dp.close()
+        solved.append((s.final_cost, s.num_iterations, [t.cost for t in tr], shard.poses.tobytes(), shard.points.tobytes(), shard.intrinsics.tobytes(),
+                       float(shard.inter_frame_ratio), None if shard.pose_prior_values is None else shard.pose_prior_values.tobytes()))
+        dist.barrier()
+    np.savez(os.path.join(outdir, f"rank{rank}.npz"), cov=cov, frames=np.array(frames))
+    out = {"rank": rank, "sharded_before": before, "sharded_after": after, "sharded_solve": sharded_solve, "repeat_equal": bool(np.array_equal(again, cov[0])),
+           "step_equal": solved[0] == solved[1], "iters": solved[0][1], "costs": solved[0][2]}
+    with open(os.path.join(outdir, f"rank{rank}.json"), "w") as f:
+        json.dump(out, f)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 def planfail_mode(mode, outdir, rank, world, dist, torch):
     """"planfail:<hook>": the symbolic phase fails on RANK 1 ONLY (a test hook of the instrumented library: RSBA_TEST_FAIL_PLAN before the lists are
     built, RSBA_TEST_FAIL_DEVICE_PLAN = the device lists' allocations).  The ranks vote in the middle of the plan: rank 1 must still enter
@@ -251,6 +306,8 @@ def main():
         return nd_mode(mode, outdir, rank, world, dist, torch)
     if mode.startswith("step:"):
         return step_mode(mode, outdir, rank, world, dist, torch)
+    if mode.startswith("cov:"):
+        return cov_mode(mode, outdir, rank, world, dist, torch)
     if mode == "mock_timeout":
         return mock_timeout_mode(outdir, rank, world, dist, torch)
     if mode.startswith("planfail:"):

@@ -34,6 +34,30 @@ def corrupt_dag(capi):
     return out
 
 
+def corrupt_covariance(capi):
+    """C2, the covariance block of the frame that holds the entry RSBA_CHOL_TEST_CORRUPT makes the first persistent-driver solve lose
+    (solver.hip: yv[(n / 2 / 6) * 6 + 1]) — with the loss, on the level schedule, and plain; then a solve on the same handle."""
+    from rsba_amd.scene import make_config
+    out = {}
+    for mode in ("corrupt", "levels", "plain"):
+        for k in ("RSBA_CHOL_TEST_CORRUPT", "RSBA_CHOL_LEVELS"):
+            os.environ.pop(k, None)
+        if mode == "corrupt":
+            os.environ["RSBA_CHOL_TEST_CORRUPT"] = "1"
+        if mode == "levels":
+            os.environ["RSBA_CHOL_LEVELS"] = "1"
+        p = make_config("C2").problem
+        entry = (p.num_frames * 12 // 2 // 6) * 6 + 1
+        frame = entry // 12
+        with capi.DeviceProblem(p) as dp:
+            cov = dp.pose_covariance(frame)
+            os.environ.pop("RSBA_CHOL_LEVELS", None)       # (the solve below reads it per call: the DAG driver in every mode)
+            s, _ = dp.solve(capi.default_options(max_num_iterations=6))
+        out[mode] = dict(cov=cov.tolist(), final_cost=s.final_cost, iters=s.num_iterations, solve_fallbacks=s.num_dag_fallbacks)
+        out["frame"], out["entry"] = frame, entry - 12 * frame
+    return out
+
+
 def failed_plan(capi, hook):
     p = small_scene()
     q = p.copy()
@@ -57,6 +81,8 @@ def main():
     from rsba_amd import capi
     if case == "corrupt_dag":
         out = corrupt_dag(capi)
+    elif case == "corrupt_covariance":
+        out = corrupt_covariance(capi)
     elif case.startswith("failed_plan:"):
         out = failed_plan(capi, case.split(":")[1])
     else:

@@ -273,3 +273,50 @@ SHAPES = ["F1", "Fm1", "F0", "Fp1", "F2p1", "single_view", "twice", "far_pair", 
           "rotation_only", "position_only", "const_points", "intr_shared", "intr_perframe", "intr_mixed", "intr_run3", "intr_const",
           "huber", "radius1e-3", "radius1e4", "radius1e10"]
 CASES = [f"rs_{s}" for s in SHAPES] + [f"gs_{s}" for s in SHAPES] + ["rs_nt25", "gs_nt25"]
+
+
+# ---- pose covariance (tests/test_lm_step_reference.py, tests/test_gpu_covariance.py) ------------------------------------------------
+
+# the scenes the covariance unit was first measured on (the CPU oracle against the extended-precision inverse) ...
+COV_TABLE = ["rs_Fp1", "gs_F2p1", "rs_huber", "rs_intr_shared", "rs_intr_run3", "gs_intr_perframe", "rs_prior_intr_perframe", "rs_acc_free",
+             "rs_vel_r0", "rs_pp_some", "gs_pp_all", "rs_scanline", "rs_far_pair", "rs_twice", "rs_const_frame", "rs_nt25"]
+# ... and the rest of the list: structural edges, masks, more intrinsics layouts, priors across tiles, 25 one-pose tiles, C2
+COV_CASES = COV_TABLE + ["rs_F2p1", "rs_dense_point", "rs_empty_frame", "rs_const_points", "rs_rotation_only",
+                         "rs_intr_mixed", "rs_intr_const", "rs_prior_subset", "rs_prior_nt", "rs_free_huber", "rs_pp_all_huber",
+                         "rs_scanline_priors", "gs_nt25", "C2"]
+# J^T J without damping is rank deficient: points seen once (two residuals for three unknowns: V_j of rank 2 — every other point of
+# rs_F1, every 17th of rs_single_view), the SphericalPrior (1e20 on three coordinates: their columns are parallel to fp64), nothing
+# fixed (the 7-dimensional gauge)
+COV_REFUSED = ["rs_F1", "rs_single_view", "rs_spherical", "free_gauge"]
+
+
+def cov_case(name):
+    """The problem of a covariance case (undamped: the solver options of case() do not matter here)."""
+    if name == "C2":
+        from rsba_amd.scene import make_config
+        return make_config("C2").problem
+    if name == "free_gauge":
+        return make_scene(8, 200, rolling=True, seed=63).problem
+    return case(name)[0]
+
+
+def cov_frames(p):
+    """The frames a covariance case asks for: the first free frame, one on each side of the first tile edge (FT - 1, FT), the first
+    frame of each of the three middle tiles when the video is longer than a leaf of the dissection (8 tiles: the top separator of
+    a band of tiles is its middle BFS level, see tile_order.hpp), the last frame, the first one-pose frame of a two-pose session,
+    and every constant or empty frame (all zeros)."""
+    F, P = p.num_frames, p.poses_per_frame
+    FT = 48 // (6 * P)
+    mask = np.zeros((F, P), dtype=np.uint8) if p.pose_fixed_mask is None else p.pose_fixed_mask.reshape(F, P).copy()
+    if p.frame_global is not None:
+        mask[p.frame_global.astype(bool), 1:] = 0x3F
+    seen = np.bincount(p.obs_frame, minlength=F) > 0
+    dead = np.all(mask == 0x3F, axis=1) | ~seen
+    out = {int(np.flatnonzero(~dead)[0]), F - 1} | {int(f) for f in np.flatnonzero(dead)}
+    out |= {f for f in (FT - 1, FT) if f < F}
+    nt = (F + FT - 1) // FT
+    if nt > 8:
+        out |= {t * FT for t in (nt // 2 - 1, nt // 2, nt // 2 + 1)}
+    if p.frame_global is not None and p.frame_global.any():
+        out.add(int(np.flatnonzero(p.frame_global)[0]))
+    return sorted(out)

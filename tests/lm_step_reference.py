@@ -277,18 +277,16 @@ def initial_blocks(prob):
                 pose_priors=np.zeros((0, 6)) if prob.pose_prior_values is None else prob.pose_prior_values)
 
 
-def lm_step(prob, r, J, *, initial_trust_region_radius: float = 1e4, min_lm_diagonal: float = 1e-6, max_lm_diagonal: float = 1e32,
-            jacobi_scaling: bool = True, refinements: int = 3, dense_limit: int = 6000, solver: str = "lu", want_kappa: bool = True,
-            edit=None) -> LMStep:
-    """The first LM step of ``prob`` linearised at its parameters; ``r`` [N, 2] and ``J`` [N, 2, K] are the raw blocks of the
-    observations there (the prior blocks are evaluated here).  Above ``dense_limit`` unknowns the fp64 solves inside the refinement
-    use a sparse LU of the whole system (``solver="lu"``) or, where its fill does not fit, a dense Cholesky of the camera system that
-    eliminates the points (``"reduced"``); either way the refinement residual is that of the whole system in np.longdouble, so the
-    answer does not rest on the elimination.  ``edit(H, free, scale)``, if given, returns a changed scaled, damped matrix (np.longdouble
-    csr) to solve with instead: the sensitivity tests' hook."""
+def assemble(prob, r, J, *, constant=None):
+    """The whole Jacobian of ``prob`` over its unknowns, in np.longdouble: the observations' blocks after the Huber corrector (rows
+    2 i + d), then the prior blocks'.  ``constant``: global columns held constant on top of the problem's own (the sensitivity tests'
+    hook).  -> (J csr [rows, n], residuals [rows], free: global column of each unknown, pos: unknown of each global column (-1: none;
+    pos[-1] serves the entries that are not a parameter), ncam, nparam)."""
     rc, Jc = corrected(float(prob.huber_a), r, J)
-    N, _, K = Jc.shape
     gcol, ncam, nparam, fixed = columns(prob)
+    if constant is not None:
+        fixed = fixed.copy()
+        fixed[np.asarray(constant, dtype=np.int64)] = True
     blocks = [(rc, Jc, gcol)]
     for rp, Jp, gp, loss in prior_blocks(prob):
         if loss:
@@ -316,6 +314,20 @@ def lm_step(prob, r, J, *, initial_trust_region_radius: float = 1e4, min_lm_diag
         row0 += nb * d
     Jld = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows_), np.concatenate(cols_))), shape=(row0, n))
     rld = np.concatenate(rl)
+    return Jld, rld, free, pos, ncam, nparam
+
+
+def lm_step(prob, r, J, *, initial_trust_region_radius: float = 1e4, min_lm_diagonal: float = 1e-6, max_lm_diagonal: float = 1e32,
+            jacobi_scaling: bool = True, refinements: int = 3, dense_limit: int = 6000, solver: str = "lu", want_kappa: bool = True,
+            edit=None) -> LMStep:
+    """The first LM step of ``prob`` linearised at its parameters; ``r`` [N, 2] and ``J`` [N, 2, K] are the raw blocks of the
+    observations there (the prior blocks are evaluated here).  Above ``dense_limit`` unknowns the fp64 solves inside the refinement
+    use a sparse LU of the whole system (``solver="lu"``) or, where its fill does not fit, a dense Cholesky of the camera system that
+    eliminates the points (``"reduced"``); either way the refinement residual is that of the whole system in np.longdouble, so the
+    answer does not rest on the elimination.  ``edit(H, free, scale)``, if given, returns a changed scaled, damped matrix (np.longdouble
+    csr) to solve with instead: the sensitivity tests' hook."""
+    Jld, rld, free, pos, ncam, nparam = assemble(prob, r, J)
+    n = len(free)
     colsq = np.asarray(Jld.multiply(Jld).sum(axis=0)).reshape(-1)
     scale = (1.0 / (1.0 + np.sqrt(colsq.astype(np.float64)))) if jacobi_scaling else np.ones(n)
     Js = (Jld @ sp.diags(scale.astype(LD))).tocsr()
@@ -473,3 +485,130 @@ def step_norm_bound(prob, ref: LMStep, c: float):
 def solved_blocks(q):
     """(poses, points, intrinsics, ratio, pose_priors) of a solved problem, the arguments of step_ratio / block_errors."""
     return q.poses, q.points, q.intrinsics, float(q.inter_frame_ratio), q.pose_prior_values
+
+
+# ---- pose covariance: blocks of (J^T J)^-1 -----------------------------------------------------------------------------------
+
+@dataclasses.dataclass
+class Covariance:
+    blocks: dict                # {frame: [CD, CD] np.longdouble}: zero rows and columns where a coordinate is not an unknown
+    free: dict                  # {frame: bool [CD]}: the coordinates of the block that are unknowns
+    kappa: float                # 2-norm condition number of the symmetrically scaled J^T J (nan when ok is False)
+    refinement: list            # max |E - H^ Y| over all columns after the first solve and after each round of refinement
+    ok: bool                    # False: J^T J is rank deficient (the fp64 factorisation of its scaled form fails, or kappa n eps >= 1)
+    error: float = 0.0          # estimate of the reference's own error, in the unit of covariance_ratio (asserted <= 2^-6)
+
+
+def _ld_matmul(A, Y, threads: int = 8):
+    """A @ Y in np.longdouble, the columns of Y shared out among a few threads (the sparse product runs without the interpreter
+    lock, and x87 arithmetic is all it does)."""
+    from concurrent.futures import ThreadPoolExecutor
+    k = Y.shape[1]
+    if k < 2 * threads:
+        return A @ Y
+    parts = np.array_split(np.arange(k), threads)
+    with ThreadPoolExecutor(threads) as ex:
+        outs = list(ex.map(lambda c: A @ np.ascontiguousarray(Y[:, c]), parts))
+    return np.concatenate(outs, axis=1)
+
+
+def covariance_blocks(prob, r, J, frames, *, dense_limit: int = 6000, max_refinements: int = 8, constant=None, edit=None) -> Covariance:
+    """What ceres::Covariance returns for the pose block(s) of each of ``frames``: the (frame, frame) block of (J^T J)^-1, J the
+    Jacobian of assemble() — no Jacobi scaling, no damping, every unknown of the problem in it (points, intrinsics, the free ratio,
+    the priorPoses blocks): nothing is eliminated.  H = J^T J is scaled symmetrically, H^ = H / (d d^T) with d = sqrt(diag H), and
+    factored ONCE in fp64 (dense Cholesky up to ``dense_limit`` unknowns, a sparse LU above); every column H^ y = e_k of every asked
+    frame goes through that factorisation together and is refined against H^ in np.longdouble until the residual stops falling, then
+    unscaled by 1 / (d_a d_k).  ``constant``: see assemble(); ``edit(H, free)`` returns a changed unscaled H (np.longdouble csr)."""
+    Jld, _, free, pos, ncam, nparam = assemble(prob, r, J, constant=constant)
+    n = len(free)
+    CD = layout(prob)["CD"]
+    frames = [int(f) for f in frames]
+    bad = Covariance(blocks={}, free={}, kappa=float("nan"), refinement=[], ok=False)
+    H = (Jld.T @ Jld).tocsr()
+    if edit is not None:
+        H = sp.csr_matrix(edit(H, free))
+    d = np.sqrt(H.diagonal())
+    if n == 0 or not np.all(d > 0):
+        return bad
+    Dinv = sp.diags(LD(1) / d)
+    Hs = (Dinv @ H @ Dinv).tocsr()
+    H64 = Hs.astype(np.float64)
+    try:
+        if n <= dense_limit:
+            A = H64.toarray()
+            cf = scipy.linalg.cho_factor(A, lower=True)
+            solve = lambda v: scipy.linalg.cho_solve(cf, v)  # noqa: E731
+            ev = scipy.linalg.eigvalsh(A)
+            lmin, lmax = float(ev[0]), float(ev[-1])
+        else:
+            lu = spl.splu(H64.tocsc())
+            solve = lu.solve
+            lmax = float(spl.eigsh(H64, k=1, which="LA", return_eigenvectors=False, tol=1e-4)[0])
+            inv = spl.LinearOperator(H64.shape, matvec=lambda v: solve(np.asarray(v, dtype=np.float64).reshape(-1)), dtype=np.float64)
+            lmin = 1.0 / float(spl.eigsh(inv, k=1, which="LA", return_eigenvectors=False, tol=1e-4)[0])
+    except (np.linalg.LinAlgError, RuntimeError):        # not positive definite / exactly singular
+        return bad
+    if not (lmin > n * DBL_EPSILON * lmax):               # numerically rank deficient: no fp64 inverse means anything
+        return bad
+    kappa = lmax / lmin
+    ks = [(f, a, int(pos[f * CD + a])) for f in frames for a in range(CD) if pos[f * CD + a] >= 0]
+    blocks = {f: np.zeros((CD, CD), dtype=LD) for f in frames}
+    isfree = {f: pos[f * CD + np.arange(CD)] >= 0 for f in frames}
+    hist, error = [], 0.0
+    if ks:
+        E = np.zeros((n, len(ks)), dtype=LD)
+        E[[k for _, _, k in ks], np.arange(len(ks))] = 1
+        Y = solve(E.astype(np.float64)).astype(LD)
+        res = E - _ld_matmul(Hs, Y)
+        hist.append(float(np.max(np.abs(res))))
+        for _ in range(max_refinements):
+            dY = solve(res.astype(np.float64))
+            Y2 = Y + dY.astype(LD)
+            res2 = E - _ld_matmul(Hs, Y2)
+            e2 = float(np.max(np.abs(res2)))
+            if not e2 < hist[-1]:
+                break
+            fell = hist[-1] / max(e2, 1e-300)
+            Y, res = Y2, res2
+            hist.append(e2)
+            if fell < 2.0:                               # (a round that gains less than a bit: the residual has stopped falling)
+                break
+        # what is left of the error, from one more fp64 solve of the last residual, in the unit of the comparison (covariance_ratio).
+        # (The residual itself cannot fall below its own rounding, 2^-64 |H^| |y|: 2e-12 for a weakly determined frame at kappa^ 3e9.)
+        dY = solve(res.astype(np.float64))
+        diag = np.array([float(Y[k, c]) for c, (_, _, k) in enumerate(ks)])
+        assert np.all(diag >= 1.0 - 1e-9), diag.min()      # H^ has a unit diagonal: that of its inverse is >= 1
+        left = 0.0
+        for c, (f, a, k) in enumerate(ks):
+            rows = pos[f * CD + np.arange(CD)]
+            m = rows >= 0
+            blocks[f][m, a] = Y[rows[m], c] / (d[rows[m]] * d[k])
+            own = np.array([diag[c2] for c2, (f2, _, _) in enumerate(ks) if f2 == f])
+            left = max(left, float(np.max(np.abs(dY[rows[m], c]) / (kappa * EPS * np.sqrt(own * diag[c])))))
+        assert left <= 2.0 ** -6, (left, hist)
+        error = left
+    return Covariance(blocks=blocks, free=isfree, kappa=kappa, refinement=hist, ok=True, error=error)
+
+
+def covariance_ratio(ref: Covariance, frame: int, got) -> float:
+    """Worst |got_ab - C_ab| / u_ab over the free coordinates of one block, u_ab = kappa * 2^-53 * sqrt(C_aa C_bb); inf when a
+    fixed row or column of ``got`` is not exactly zero.  The same unit bounds |got - got^T| (covariance_asymmetry)."""
+    C, m = ref.blocks[frame], ref.free[frame]
+    got = np.asarray(got, dtype=np.float64)
+    if np.any(got[~m, :] != 0) or np.any(got[:, ~m] != 0):
+        return float("inf")
+    if not m.any():
+        return 0.0
+    s = np.sqrt(np.diag(C)[m])
+    u = LD(ref.kappa) * LD(EPS) * s[:, None] * s[None, :]
+    return float(np.max(np.abs(got[np.ix_(m, m)] - C[np.ix_(m, m)]) / u))
+
+
+def covariance_asymmetry(ref: Covariance, frame: int, got) -> float:
+    """Worst |got_ab - got_ba| / u_ab over the free coordinates of one block."""
+    C, m = ref.blocks[frame], ref.free[frame]
+    if not m.any():
+        return 0.0
+    got = np.asarray(got, dtype=np.float64)[np.ix_(m, m)]
+    s = np.sqrt(np.diag(C)[m])
+    return float(np.max(np.abs(got - got.T) / (LD(ref.kappa) * LD(EPS) * s[:, None] * s[None, :])))

@@ -660,3 +660,40 @@ def test_sharded_step_matches_the_host_reference(tmp_path, oracle, mode, world):
     nrm, allowed = R.step_norm_bound(full, ref, C_TOL)
     assert abs(t[1]["step_norm"] - nrm) <= allowed
     assert abs(t[0]["gradient_max_norm"] - ref.gradient_max_norm) <= 1e-12 * ref.gradient_max_norm
+
+
+_cov_refs = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("mode", ["cov:S300:priors:freeratio", "cov:S300:posepriors", "cov:S300:perframe:mixedintr:seed8", "cov:C2:intr"])
+def test_covariance_on_a_handle_with_an_exchange(tmp_path, oracle, mode, world):
+    """rsba_pose_covariance on every rank of a sharded problem: the plan is the sharded one (plan_stats), the call takes its
+    replicated form — the whole reduced system summed onto every rank — and puts the sharded form back: every rank's blocks are the
+    same bits and within the covariance bound of the extended-precision inverse of the WHOLE problem's J^T J; the frames asked lie
+    in a part, in a top separator of the 2-rank and of the 4-rank cut, and at both ends.  One LM iteration after the calls is, bit for
+    bit, the iteration of a handle that never computed a covariance."""
+    import lm_step_reference as R
+    from dist_worker import nd_problem, sharded_cov_frames
+    from test_lm_step_reference import C_COV, covariance_worst
+    res = run_two_ranks(mode, tmp_path, world)
+    if mode not in _cov_refs:
+        full = nd_problem(mode.split(":")[1], mode.split(":")[2:])
+        r, J, ok = oracle.evaluate_blocks(full)
+        assert ok.all()
+        frames = sharded_cov_frames(full)
+        _cov_refs[mode] = (frames, R.covariance_blocks(full, r, J, frames))
+    frames, ref = _cov_refs[mode]
+    assert ref.ok
+    got = np.load(os.path.join(tmp_path, "rank0.npz"))
+    assert list(got["frames"]) == frames
+    worst = covariance_worst(ref, {f: got["cov"][i] for i, f in enumerate(frames)})
+    print(f"{mode} on {world} ranks: covariance ratio {worst:.3f}, kappa^ {ref.kappa:.2e}")
+    assert worst <= C_COV, (worst, ref.kappa)
+    for k in range(1, world):
+        assert np.array_equal(np.load(os.path.join(tmp_path, f"rank{k}.npz"))["cov"], got["cov"])
+    for o in res:
+        assert o["sharded_before"] == 1 and o["sharded_after"] == 1 and o["sharded_solve"] == 1
+        assert o["repeat_equal"] and o["step_equal"] and o["iters"] == 2
+        assert o["costs"] == res[0]["costs"]
