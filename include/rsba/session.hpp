@@ -6,6 +6,7 @@
 // the reference.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace rsba_amd {
@@ -23,9 +24,10 @@ struct ObservationRef {   // sfm.thrift:33-42
 
 struct Observation {      // sfm.thrift:13-22
   double x = 0, y = 0;
+  std::string descriptor;               // field 3, binary: FEATURE_SIZE = 128 floats as raw bytes (struct/VideoSfM.cc:11-13,33-36); empty unless the loader was asked to keep it
   std::vector<ObservationRef> matches;
   int32_t track = 0;
-  struct { bool matches = false, track = false; } __isset;
+  struct { bool descriptor = false, matches = false, track = false; } __isset;
 };
 
 struct Track {            // sfm.thrift:25-30
@@ -70,6 +72,7 @@ struct SfmOptions {
     unsigned minReprojections = 3;
     unsigned maxReprojections = 10;   // 0 = no limit (VideoSfMHandler.cc:248)
     unsigned minDistanceToCamera = 0;
+    unsigned maxFramesToMatch = 5;    // SfmOptions.h:45; parseFrame matches a new frame against that many earlier ones (VideoSfMClient.cc:196)
   } tracks;
   struct Ceres {
     bool useOnlyValidMatches = true;

@@ -14,7 +14,9 @@
 //     transport write() is one event (TBinaryProtocol issues one per primitive), events never straddle a 16 MiB
 //     chunk boundary (the tail of a chunk is zero-filled, a zero size means "continue at the next chunk").
 //     Reading concatenates the payloads.
-// Optional fields the solver side has no use for (descriptor, color) are skipped on read and not written.
+// Optional fields the solver side has no use for (descriptor, color) are skipped on read and not written.  The matcher
+// (match_frames.hpp) does need Observation.descriptor: loadCache(path, obj, true) keeps it, saveCache(path, obj, true) writes
+// it where set, in the IDL's field order.  The defaults leave both as they were.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -67,6 +69,7 @@ struct EventWriter {
 // ---- TBinaryProtocol ----
 struct Reader {
   const std::vector<uint8_t>& b; size_t p = 0;
+  bool keep_descriptors = false;
   explicit Reader(const std::vector<uint8_t>& bytes) : b(bytes) {}
   void need(size_t n) const { if (p + n > b.size()) throw std::runtime_error("truncated Thrift stream"); }
   uint8_t u8() { need(1); return b[p++]; }
@@ -107,6 +110,7 @@ struct Reader {
 
 struct Writer {
   EventWriter& t;
+  bool write_descriptors = false;
   explicit Writer(EventWriter& tr) : t(tr) {}
   void u8(uint8_t v) { t.write(&v, 1); }
   void i16(int16_t v) { const uint8_t b[2] = {(uint8_t)((uint16_t)v >> 8), (uint8_t)v}; t.write(b, 2); }
@@ -138,6 +142,10 @@ inline void read(Reader& r, Observation& o) {                           // sfm.t
     const int16_t id = r.i16();
     if (id == 1 && t == T_DOUBLE) o.x = r.f64();
     else if (id == 2 && t == T_DOUBLE) o.y = r.f64();
+    else if (id == 3 && t == T_STRING && r.keep_descriptors) {
+      const int32_t n = r.i32(); if (n < 0) throw std::runtime_error("negative length"); r.need((size_t)n);
+      o.descriptor.assign(reinterpret_cast<const char*>(r.b.data() + r.p), (size_t)n); r.p += (size_t)n; o.__isset.descriptor = true;
+    }
     else if (id == 5 && t == T_LIST) { const int32_t n = r.list(T_STRUCT); o.matches.resize((size_t)n); for (auto& m : o.matches) read(r, m); o.__isset.matches = true; }
     else if (id == 6 && t == T_I32) { o.track = r.i32(); o.__isset.track = true; }
     else r.skip(t);                                                     // descriptor (3), color (4)
@@ -187,6 +195,7 @@ inline void write(Writer& w, const ObservationRef& o) {
 }
 inline void write(Writer& w, const Observation& o) {
   w.field(T_DOUBLE, 1); w.f64(o.x); w.field(T_DOUBLE, 2); w.f64(o.y);
+  if (w.write_descriptors && o.__isset.descriptor) { w.field(T_STRING, 3); w.i32((int32_t)o.descriptor.size()); w.t.write(o.descriptor.data(), (uint32_t)o.descriptor.size()); }
   if (o.__isset.matches) { w.field(T_LIST, 5); w.list(T_STRUCT, o.matches.size()); for (const auto& m : o.matches) write(w, m); }
   if (o.__isset.track) { w.field(T_I32, 6); w.i32(o.track); }
   w.stop();
@@ -231,17 +240,19 @@ inline void check_indices(const Session& s) {
 
 // VideoSfMCache::unserialize(T&) for T = Session / Frame.  Throws std::runtime_error on unreadable input.
 template <class T>
-inline void loadCache(const std::string& path, T& obj) {
+inline void loadCache(const std::string& path, T& obj, bool keepDescriptors = false) {
   const std::vector<uint8_t> bytes = cache_detail::read_events(path);
   cache_detail::Reader r(bytes);
+  r.keep_descriptors = keepDescriptors;
   cache_detail::read(r, obj);
   cache_detail::check_indices(obj);
 }
 // VideoSfMCache::save(const T&): the same event / protocol layout the reference's serialize() produces
 template <class T>
-inline void saveCache(const std::string& path, const T& obj) {
+inline void saveCache(const std::string& path, const T& obj, bool writeDescriptors = false) {
   cache_detail::EventWriter t(path);
   cache_detail::Writer w(t);
+  w.write_descriptors = writeDescriptors;
   cache_detail::write(w, obj);
 }
 

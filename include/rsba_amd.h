@@ -273,6 +273,37 @@ int32_t rsba_track_candidates(int32_t device, const double* cams, int32_t num_ca
                               const uint8_t* request, const double* track_pt, int64_t num_cand, double sq_threshold, double min_distance,
                               uint8_t* tri_ok, double* tri_pt, uint8_t* reproj_ok);
 
+/* == the neighbour search of VideoSfMClient::Match (VideoSfMClient.cc:73-129: cv::BFMatcher().knnMatch, NORM_L2, no cross-check)
+ * for a list of (query frame, train frame) pairs, as parseFrame forms them (:196-201), without a handle.  OpenCV is not part of
+ * the reference tree; the rules below are THIS library's definition of the search:
+ *   distance(i, j) = sqrtf(float(sum_c (q_ic - t_jc)^2)); for every query row i the k' = min(k, n_train) train rows with the
+ *   smallest distance, ascending; TIES GO TO THE LOWER TRAIN INDEX.  A pair with n_train < 2 yields no neighbours (the
+ *   reference reads ms[1] out of bounds there), a pair with n_query == 0 none either (the reference divides by zero).
+ * desc [frame_offset[num_frames]][dim] holds every frame's descriptors, frame f's rows at frame_offset[f] .. frame_offset[f + 1]
+ * (frame_offset[0] = 0, non-decreasing).  dim must be 128 (FEATURE_SIZE, struct/VideoSfM.cc:11-13): RSBA_ERR_UNSUPPORTED
+ * otherwise.  k in [1, 5] (Match asks for 2, or 5 with `multiple`).  Pair p searches frame pair_query[p]'s rows among frame
+ * pair_train[p]'s; a frame may serve in any number of pairs, as query and as train.  The descriptors must be FINITE: they are
+ * not checked, and a NaN or an infinity gives an unspecified result for the queries it touches.
+ * Outputs (host arrays): pair p's results start at slot out_offset[p] (a non-negative multiple of k; the pairs' ranges must not
+ * overlap), k slots per query: nn_index (train row within its frame) and nn_dist, ordered by (distance, index); slots past k'
+ * hold index -1 and distance +inf.  nn_count[out_offset[p] / k + i] = k' of pair p's query i, 0 for a pair with n_train < 2.
+ * The arrays must reach the largest end = out_offset[p] + k * n_query(p), and the call writes ALL of [0, end): slots (and counts)
+ * in gaps that the pairs' ranges leave come back as unused (-1, +inf, 0), whatever they held.
+ * Exactness: the search runs in the GEMM form ||q||^2 + ||t||^2 - 2 q.t on the f32 matrix cores, the k' survivors' distances
+ * are recomputed in the direct form above (an fmaf chain in c order).  For integer-valued descriptors in [0, 255] — what
+ * OpenCV's SIFT emits — every intermediate is an integer below 2^24, so indices, counts and distances equal the integer
+ * restatement bit for bit.  For general data the search may confuse neighbours whose squared distances differ by less than
+ * ~130 * 2^-24 * (||q||^2 + ||t||^2 + 2 sum |q_c||t_c|); the reported distance is always the direct form's.
+ * Each host thread keeps one device arena, pinned staging buffer and stream between calls, as for rsba_track_candidates; there
+ * is no CPU fallback.
+ * rsba_match_last_kernel_ms (a measurement aid for tools/match_time.py, no part of the matching itself): the HIP-event time of
+ * the three kernel passes of the calling thread's last successful rsba_match_descriptors call that reached the device.
+ * RSBA_ERR_INVALID_ARGUMENT when ms is NULL or this thread has made no such call yet. */
+int32_t rsba_match_descriptors(int32_t device, const float* desc, int32_t dim, const int64_t* frame_offset, int32_t num_frames,
+                               const int32_t* pair_query, const int32_t* pair_train, int64_t num_pairs, int32_t k,
+                               const int64_t* out_offset, int32_t* nn_index, float* nn_dist, int32_t* nn_count);
+int32_t rsba_match_last_kernel_ms(float* ms);
+
 /* == the covariance blocks VideoSfMHandler::BA prints with opt.debug.calcCovariances (VideoSfMHandler.cc:602-621:
  * ceres::Covariance::Compute on (p0,p0), (p0,p1), (p1,p1) of a frame): cov [CD][CD] row-major,
  * CD = 6 * poses_per_frame, = the (frame, frame) block of (J^T J)^-1 at the current parameters, loss function applied,

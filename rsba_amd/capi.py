@@ -26,6 +26,7 @@ EXPORTS = [
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
+    "rsba_match_descriptors", "rsba_match_last_kernel_ms",
 ]
 NUM_EXCHANGES = 6
 NUM_PHASES = 13
@@ -448,6 +449,40 @@ def track_candidates(cams, frame_cam, frame_poses, shutter, scanlines, obs_frame
                                        _ptr(ca), _ptr(cb), _ptr(rq), _ptr(tp), C.c_int64(n), C.c_double(sq_threshold), C.c_double(min_distance),
                                        _ptr(tri_ok), _ptr(tri_pt), _ptr(rep)))
     return tri_ok.astype(bool), tri_pt, rep.astype(bool)
+
+
+def match_descriptors(desc_per_frame, pairs, k=2, device=0):
+    """The k-nearest-neighbour search of VideoSfMClient::Match for a list of (query frame, train frame) pairs in one call, no
+    handle (rsba_amd.h: rsba_match_descriptors).  desc_per_frame: one [n_f, 128] float32 array per frame (n_f may be 0).
+    -> per pair: index [n_query, k] int32 (-1 = unused), distance [n_query, k] float32 (+inf = unused), count [n_query] int32"""
+    ds = [np.ascontiguousarray(d, dtype=np.float32) for d in desc_per_frame]
+    dim = next((d.shape[1] for d in ds if d.ndim == 2), 128)
+    ds = [d.reshape(-1, dim) for d in ds]
+    off = np.zeros(len(ds) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(d) for d in ds])
+    desc = np.ascontiguousarray(np.concatenate(ds) if off[-1] else np.zeros((1, dim), dtype=np.float32))
+    pq = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32); pt = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+    k = int(k)
+    nq = [len(ds[q]) if 0 <= q < len(ds) else 0 for q in pq]
+    out = np.zeros(len(pairs) + 1, dtype=np.int64)
+    out[1:] = np.cumsum(nq) * max(k, 1)
+    total = int(out[-1])
+    idx = np.full(max(total, 1), -1, dtype=np.int32); dist = np.full(max(total, 1), np.inf, dtype=np.float32)
+    cnt = np.zeros(max(total // max(k, 1), 1), dtype=np.int32)
+    _check(lib().rsba_match_descriptors(C.c_int32(device), _ptr(desc), C.c_int32(dim), _ptr(off), C.c_int32(len(ds)), _ptr(pq), _ptr(pt),
+                                        C.c_int64(len(pairs)), C.c_int32(k), _ptr(out), _ptr(idx), _ptr(dist), _ptr(cnt)))
+    res = []
+    for p in range(len(pairs)):
+        a, b = int(out[p]), int(out[p + 1])
+        res.append((idx[a:b].reshape(-1, k), dist[a:b].reshape(-1, k), cnt[a // k:b // k].copy()))
+    return res
+
+
+def match_last_kernel_ms() -> float:
+    """HIP-event time of the kernels of this thread's last match_descriptors call."""
+    ms = C.c_float(0)
+    _check(lib().rsba_match_last_kernel_ms(C.byref(ms)))
+    return float(ms.value)
 
 
 def rccl_unique_id() -> bytes:
