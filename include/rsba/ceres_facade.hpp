@@ -224,7 +224,8 @@ struct Solver {
     LinearSolverType linear_solver_type = SPARSE_NORMAL_CHOLESKY;
     bool minimizer_progress_to_stdout = false;
     int max_num_iterations = 50;
-    int min_linear_solver_iterations = 1;
+    int min_linear_solver_iterations = 1, max_linear_solver_iterations = 500;   // read by ITERATIVE_SCHUR only, as in Ceres
+    double eta = 1e-1;                                                          // likewise
     int num_threads = 1, num_linear_solver_threads = 1;
     bool jacobi_scaling = true;
     bool use_nonmonotonic_steps = false;
@@ -242,6 +243,7 @@ struct Solver {
     int num_successful_steps = 0, num_unsuccessful_steps = 0;
     int num_residual_blocks = 0, num_residual_blocks_reduced = 0, num_parameters_reduced = 0;
     int num_dag_fallbacks = 0;   // extension: see rsba_solver_summary
+    int num_linear_solver_iterations = 0;   // conjugate-gradient iterations over all linear solves (ITERATIVE_SCHUR; 0 with an exact solver)
     double total_time_in_seconds = 0, jacobian_evaluation_time_in_seconds = 0, linear_solver_time_in_seconds = 0;
     std::vector<rsba_iteration> iterations;
     bool IsSolutionUsable() const { return termination_type == CONVERGENCE || termination_type == NO_CONVERGENCE || termination_type == USER_SUCCESS; }
@@ -256,7 +258,8 @@ struct Solver {
       o << "Solver Summary (rsba_amd, MI355X)\n"
         << "Residual blocks      " << num_residual_blocks << " (reduced " << num_residual_blocks_reduced << ")\n"
         << "Effective parameters " << num_parameters_reduced << "\n"
-        << "Linear solver        SPARSE_SCHUR (on-device point elimination + tile-sparse Cholesky)\n"
+        << (num_linear_solver_iterations > 0 ? "Linear solver        ITERATIVE_SCHUR (on-device point elimination + block-Jacobi preconditioned CG)\n"
+                                             : "Linear solver        SPARSE_SCHUR (on-device point elimination + tile-sparse Cholesky)\n")
         << "Cost: initial " << initial_cost << "  final " << final_cost << "  change " << (initial_cost - final_cost) << "\n"
         << "Minimizer iterations " << iterations.size() << " (successful " << num_successful_steps << ", unsuccessful " << num_unsuccessful_steps << ")\n"
         << "Time (s): residual+jacobian " << jacobian_evaluation_time_in_seconds << "  linear solver " << linear_solver_time_in_seconds
@@ -597,7 +600,8 @@ class Problem {
 };
 
 // ceres::Solve(options, &problem, &summary) (CeresHandler.h:419).  Synchronous; never throws; status in
-// the summary.  Any linear_solver_type is served by the one exact Schur-complement solver.
+// the summary.  ITERATIVE_SCHUR is served by the preconditioned conjugate gradients of rsba_set_linear_solver (with
+// min / max_linear_solver_iterations and eta); every other linear_solver_type by the one exact Schur-complement solver.
 inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
   *summary = Solver::Summary();
   Problem::Flat f;
@@ -615,9 +619,18 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
   o.min_lm_diagonal = options.min_lm_diagonal; o.max_lm_diagonal = options.max_lm_diagonal;
   o.function_tolerance = options.function_tolerance; o.gradient_tolerance = options.gradient_tolerance; o.parameter_tolerance = options.parameter_tolerance;
   o.level_scheduled_cholesky = options.level_scheduled_cholesky ? 1 : 0;
+  if (options.linear_solver_type == ITERATIVE_SCHUR) {
+    rsba_linear_solver_options lo; rsba_default_linear_solver_options(&lo);
+    lo.type = RSBA_LINEAR_SOLVER_PCG; lo.min_iterations = options.min_linear_solver_iterations; lo.max_iterations = options.max_linear_solver_iterations; lo.eta = options.eta;
+    st = rsba_set_linear_solver(h, &lo);
+    if (st != RSBA_OK) { summary->termination_type = FAILURE; summary->message = std::string(rsba_status_string(st)) + ": " + rsba_last_error(); rsba_destroy(h); return; }
+  }
   rsba_solver_summary s;
   std::vector<rsba_iteration> trace((size_t)options.max_num_iterations + 2);
   st = rsba_solve(h, &o, &s, trace.data(), (int32_t)trace.size());
+  rsba_linear_solver_stats ls{};
+  (void)rsba_get_linear_solver_stats(h, &ls);
+  summary->num_linear_solver_iterations = (int)ls.total_iterations;
   double solved_ratio = 0.0;
   if (f.ratio_free) (void)rsba_get_inter_frame_ratio(h, &solved_ratio);
   rsba_destroy(h);

@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define RSBA_AMD_ABI_VERSION 3
+#define RSBA_AMD_ABI_VERSION 4
 
 typedef enum rsba_status {
   RSBA_OK = 0,
@@ -180,6 +180,48 @@ int32_t rsba_time_evaluate(rsba_handle* h, int32_t with_jacobians, int32_t warmu
 void rsba_default_solver_options(rsba_solver_options* opt);
 int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rsba_solver_summary* summary,
                    rsba_iteration* trace, int32_t trace_capacity);
+
+/* == the choice ceres::Solver::Options::linear_solver_type makes between the exact reduced solve (SPARSE_SCHUR / DENSE_SCHUR)
+ * and ITERATIVE_SCHUR, the solver VideoSfMHandler::BA's min_linear_solver_iterations = 3 is meant for (VideoSfMHandler.cc:579-583:
+ * the option is read by Ceres' iterative Schur solver only).  Mirrors linear_solver_type, min_linear_solver_iterations,
+ * max_linear_solver_iterations and eta of ceres::Solver::Options.  Ceres is not part of the reference tree; the rules below are
+ * THIS library's definition of the iterative solve:
+ *   type 1 solves the reduced camera system S y = rhs of every LM iteration (S explicit, in its packed 48 x 48 tiles, after the
+ *   same Schur elimination and damping as the exact solve) by conjugate gradients preconditioned with the block diagonal M of S:
+ *   one CD x CD block per frame (CD = 6 * poses_per_frame), one 9 x 9 block per intrinsics parameter block, each Cholesky-factored
+ *   once per linear solve.  From y_0 = 0: r_0 = rhs, z = M^-1 r, p = z; then q = S p, alpha = r.z / p.q, y += alpha p,
+ *   r -= alpha q, z = M^-1 r, beta = r.z_new / r.z_old, p = z + beta p.  After iteration k >= min_iterations the solve stops when
+ *     r_tolerance >= 0 and |r_k|_2 <= r_tolerance * |rhs|_2, or
+ *     eta > 0 and k (Q_k - Q_k-1) / Q_k < eta with Q_k = -1/2 y_k.(rhs + r_k), Q_0 = 0 (the model's decrease has levelled off),
+ *   and always at k = max_iterations: reaching the cap is no failure, the step is used as it is.  (eta <= 0 and r_tolerance < 0
+ *   switch their test off.)  A block of M that is not positive definite, or a p.q that is not positive and finite, fails the linear
+ *   solve: the LM step is invalid, as after a failed pivot of the exact solve.  Every sum has a fixed order: two solves of the same
+ *   problem agree bit for bit.
+ * rsba_set_linear_solver is valid between solves and takes effect at the next rsba_solve.  With type 1 the trust-region decisions
+ * are taken by the host (once per chunk of CG iterations it reads the convergence flag), the time of the iterations counts in
+ * RSBA_PHASE_CHOLESKY, rsba_pose_covariance keeps using the exact factorisation, and rsba_solve returns RSBA_ERR_UNSUPPORTED
+ * (the handle stays usable) for a free interFrameRatio, for a handle with an exchange attached and together with
+ * options.level_scheduled_cholesky.  Type 0 (the default) is the exact solve, bit for bit what it was.
+ * rsba_get_linear_solver_stats: the counts of the last rsba_solve (all zero after one with type 0) and, of its last linear solve,
+ * the iterations and |r|_2 / |rhs|_2 at the end. */
+enum { RSBA_LINEAR_SOLVER_EXACT = 0, RSBA_LINEAR_SOLVER_PCG = 1 };
+typedef struct rsba_linear_solver_options {
+  int32_t type;                  /* 0: RSBA_LINEAR_SOLVER_EXACT (linear_solver_type SPARSE_SCHUR), 1: RSBA_LINEAR_SOLVER_PCG (ITERATIVE_SCHUR, JACOBI) */
+  int32_t min_iterations;        /* 1    min_linear_solver_iterations (VideoSfMHandler.cc:583 sets 3) */
+  int32_t max_iterations;        /* 500  max_linear_solver_iterations */
+  int32_t reserved;
+  double eta;                    /* 0.1  eta */
+  double r_tolerance;            /* -1: off */
+} rsba_linear_solver_options;
+typedef struct rsba_linear_solver_stats {
+  int64_t num_linear_solves, total_iterations;            /* of the last rsba_solve */
+  int32_t max_iterations, num_solves_at_cap, num_failed_solves;
+  int32_t last_iterations;                                /* of its last linear solve */
+  double last_relative_residual;
+} rsba_linear_solver_stats;
+void rsba_default_linear_solver_options(rsba_linear_solver_options* opt);
+int32_t rsba_set_linear_solver(rsba_handle* h, const rsba_linear_solver_options* opt);
+int32_t rsba_get_linear_solver_stats(rsba_handle* h, rsba_linear_solver_stats* out);
 
 /* Measurement aids: where an LM iteration spends its device time, and the sizes of the symbolic plan the
  * kernels' algorithmic bytes / flops follow from.  Phase p covers the launches listed; ms[p] is the HIP-event time summed

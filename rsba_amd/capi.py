@@ -27,7 +27,9 @@ EXPORTS = [
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
     "rsba_match_descriptors", "rsba_match_last_kernel_ms",
+    "rsba_default_linear_solver_options", "rsba_set_linear_solver", "rsba_get_linear_solver_stats",
 ]
+LINEAR_SOLVER_EXACT, LINEAR_SOLVER_PCG = 0, 1   # rsba_amd.h: RSBA_LINEAR_SOLVER_*
 NUM_EXCHANGES = 6
 NUM_PHASES = 13
 
@@ -90,6 +92,17 @@ class DeviceView(C.Structure):
     ]
 
 
+class LinearSolverOptions(C.Structure):
+    _fields_ = [("type", C.c_int32), ("min_iterations", C.c_int32), ("max_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("eta", C.c_double), ("r_tolerance", C.c_double)]
+
+
+class LinearSolverStats(C.Structure):
+    _fields_ = [("num_linear_solves", C.c_int64), ("total_iterations", C.c_int64), ("max_iterations", C.c_int32),
+                ("num_solves_at_cap", C.c_int32), ("num_failed_solves", C.c_int32), ("last_iterations", C.c_int32),
+                ("last_relative_residual", C.c_double)]
+
+
 class PhaseTimes(C.Structure):
     _fields_ = [("ms", C.c_double * NUM_PHASES), ("calls", C.c_int32 * NUM_PHASES), ("reserved", C.c_int32)]
 
@@ -132,6 +145,7 @@ def lib():
         _lib.rsba_destroy.restype = None
         _lib.rsba_release_host_scratch.restype = None
         _lib.rsba_default_solver_options.restype = None
+        _lib.rsba_default_linear_solver_options.restype = None
         _lib.rsba_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         _lib.rsba_destroy.argtypes = [C.c_void_p]
         _lib.rsba_phase_name.restype = C.c_char_p
@@ -245,6 +259,22 @@ class DeviceProblem:
         v = C.c_double(0.0)
         _check(lib().rsba_get_inter_frame_ratio(self._h, C.byref(v)))
         return v.value
+
+    def set_linear_solver(self, **kw):
+        """rsba_set_linear_solver: how the next solve() solves the reduced camera system — type (LINEAR_SOLVER_EXACT, the default, or
+        LINEAR_SOLVER_PCG), min_iterations, max_iterations, eta, r_tolerance; what is not given takes its default (rsba_amd.h)."""
+        o = LinearSolverOptions()
+        lib().rsba_default_linear_solver_options(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        _check(lib().rsba_set_linear_solver(self._h, C.byref(o)))
+
+    def linear_solver_stats(self) -> dict:
+        """rsba_get_linear_solver_stats: what the iterative linear solver did in the last solve()."""
+        st = LinearSolverStats()
+        _check(lib().rsba_get_linear_solver_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in LinearSolverStats._fields_}
 
     def set_stream(self, raw_stream: int | None):
         _check(lib().rsba_set_stream(self._h, C.c_void_p(raw_stream or 0)))

@@ -555,6 +555,27 @@ int32_t rsba_reproject(rsba_handle* h, const int32_t* frames, const int32_t* poi
   return RSBA_OK;
 }
 
+void rsba_default_linear_solver_options(rsba_linear_solver_options* o) {
+  if (!o) return;
+  // ceres::Solver::Options defaults: SPARSE_SCHUR as CeresHandler.h:403-412 leaves it, min / max_linear_solver_iterations 1 / 500, eta 0.1
+  o->type = RSBA_LINEAR_SOLVER_EXACT; o->min_iterations = 1; o->max_iterations = 500; o->reserved = 0; o->eta = 0.1; o->r_tolerance = -1.0;
+}
+
+int32_t rsba_set_linear_solver(rsba_handle* h, const rsba_linear_solver_options* o) {
+  if (!h || !o) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->type != RSBA_LINEAR_SOLVER_EXACT && o->type != RSBA_LINEAR_SOLVER_PCG) return fail(RSBA_ERR_INVALID_ARGUMENT, "linear solver type: 0 (exact) or 1 (preconditioned conjugate gradients)");
+  if (o->min_iterations < 0 || o->max_iterations < 1 || !(o->eta == o->eta) || !(o->r_tolerance == o->r_tolerance))
+    return fail(RSBA_ERR_INVALID_ARGUMENT, "linear solver options: min_iterations >= 0, max_iterations >= 1, eta and r_tolerance numbers");
+  h->lin_opt = *o;
+  return RSBA_OK;
+}
+
+int32_t rsba_get_linear_solver_stats(rsba_handle* h, rsba_linear_solver_stats* out) {
+  if (!h || !out) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  *out = h->lin_stats;
+  return RSBA_OK;
+}
+
 void rsba_default_solver_options(rsba_solver_options* o) {
   if (!o) return;
   // Ceres 1.9 Solver::Options defaults; iteration cap as CeresHandler.h:405

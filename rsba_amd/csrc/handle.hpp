@@ -41,6 +41,8 @@ struct rsba_handle {
   std::vector<int32_t> pp_blocks;      // pose blocks carrying a GoodPosePrior
   double* pp_host = nullptr;           // caller's priorPoses values [count][6], written back by rsba_solve
   rsba::Solver* solver = nullptr;      // normal-equation / Schur / LM state, built on first use
+  rsba_linear_solver_options lin_opt{RSBA_LINEAR_SOLVER_EXACT, 1, 500, 0, 0.1, -1.0};   // rsba_set_linear_solver: how the next rsba_solve solves the reduced camera system
+  rsba_linear_solver_stats lin_stats{};   // ... and what the iterative solver did in the last one
   // multi-GPU exchange (rsba_set_exchange / rsba_set_block_structure)
   rsba_allreduce_fn allreduce = nullptr;
   void* allreduce_ctx = nullptr;

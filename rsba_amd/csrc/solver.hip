@@ -28,6 +28,7 @@
 #include "tile_order.hpp"
 #include "chol_plan.hpp"
 #include "plan_device.hpp"
+#include "pcg.hpp"
 #include "test_hooks.hpp"
 
 namespace rsba {
@@ -135,6 +136,8 @@ struct Solver {
   PosePriorDev pp{};                                                  // per-pose priors: linearisation of the priorPoses coordinates
   double* merge_buf = nullptr;                                        // sharded solve: [4 M] owned point values | owner flags
   double* ucross = nullptr;                                           // [F][CD][CD] motion-prior blocks (f, f-1), behind sv.U's J^T J blocks
+  // iterative reduced solve (rsba_set_linear_solver type 1; pcg.hpp): lists and vectors, made by the first solve that asks for them
+  bool pcg_on = false; bool pcg_ready = false; PcgHostPlan pcg_hp; PcgDev pcg{};
 };
 
 }  // namespace rsba
@@ -1544,6 +1547,59 @@ int32_t solve_again(rsba_handle* h, const double* b2, const double** v_out) {
   return RSBA_OK;
 }
 
+// S y = rhs by preconditioned conjugate gradients over the packed tiles (kernels_pcg.hip): the lists and vectors on first use, ...
+int32_t ensure_pcg(rsba_handle* h) {
+  Solver* s = h->solver; const SolverDev& sv = s->sv;
+  if (s->pcg_ready) return RSBA_OK;
+  if (!pcg_build_plan(s->hp.slot_tiles, sv.nt, sv.F, sv.CD, sv.NIB, sv.NPF, &s->pcg_hp)) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "iterative linear solver: the tile layout of the reduced camera system has no diagonal tile for some row");
+  PcgDev& pc = s->pcg; const PcgHostPlan& hp = s->pcg_hp;
+  int32_t rc;
+  if ((rc = s_upload_const(s, &pc.row_ptr, hp.row_ptr))) return rc;
+  if ((rc = s_upload_const(s, &pc.row_list, hp.row_list))) return rc;
+  if ((rc = s_upload_const(s, &pc.blk_row, hp.blk_row))) return rc;
+  if ((rc = s_upload_const(s, &pc.blk_size, hp.blk_size))) return rc;
+  if ((rc = s_upload_const(s, &pc.blk_slots, hp.blk_slots))) return rc;
+  pc.nblk = (int)hp.blk_row.size(); pc.nbw = (pc.nblk + kPcgBlockThreads - 1) / kPcgBlockThreads;
+  if ((rc = s_alloc(s, &pc.fac, (size_t)(kPcgBlockMax * (kPcgBlockMax + 1) / 2) * pc.nblk))) return rc;
+  double* v = nullptr;
+  if ((rc = s_alloc(s, &v, 6 * (size_t)sv.npad))) return rc;
+  pc.y = v; pc.r = v + sv.npad; pc.z = v + 2 * sv.npad; pc.q = v + 3 * sv.npad; pc.p[0] = v + 4 * sv.npad; pc.p[1] = v + 5 * sv.npad;
+  if ((rc = s_alloc(s, &pc.part_pq, (size_t)sv.nt))) return rc;
+  if ((rc = s_alloc(s, &pc.part, 3 * (size_t)pc.nbw))) return rc;
+  if ((rc = s_alloc(s, &pc.sc, (size_t)kPcgScSize))) return rc;
+  s->pcg_ready = true;
+  return RSBA_OK;
+}
+// ... then the iterations, enqueued in chunks: after each the host reads the scalars once (the flag every kernel of the iteration looks at
+// first: launches behind the end of the solve return at once).  The step stays in s->pcg.y.
+int32_t solve_reduced_pcg(rsba_handle* h) {
+  Solver* s = h->solver; const SolverDev& sv = s->sv; hipStream_t st = h->stream;
+  PhaseScope ps(h, RSBA_PHASE_CHOLESKY);
+  if (int32_t rc = ensure_pcg(h)) return rc;
+  const PcgDev& pc = s->pcg;
+  const rsba_linear_solver_options& lo = h->lin_opt;
+  const PcgRule rule{lo.min_iterations, lo.max_iterations, lo.eta, lo.r_tolerance};
+  HIP_TRY(launch_pcg_begin(sv, pc, st));
+  double sc[kPcgScSize] = {};
+  int enqueued = 0, flip = 0, chunk = 8;
+  for (;;) {
+    const int n = std::min(chunk, lo.max_iterations - enqueued);
+    for (int k = 0; k < n; ++k) { HIP_TRY(launch_pcg_iteration(sv, pc, rule, flip, st)); flip ^= 1; }
+    enqueued += n;
+    HIP_TRY(hipMemcpyAsync(sc, pc.sc, sizeof sc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (sc[kPcgDone] != 0.0 || enqueued >= lo.max_iterations) break;
+    chunk = std::min(2 * chunk, 64);
+  }
+  rsba_linear_solver_stats& ls = h->lin_stats;
+  const int iters = (int)sc[kPcgK];
+  ++ls.num_linear_solves; ls.total_iterations += iters; ls.max_iterations = std::max(ls.max_iterations, iters);
+  if (sc[kPcgDone] == 2.0) ++ls.num_solves_at_cap;
+  if (sc[kPcgDone] == 3.0) ++ls.num_failed_solves;
+  ls.last_iterations = iters; ls.last_relative_residual = sc[kPcgRel];
+  return RSBA_OK;
+}
+
 // ratio (free interFrameRatio only): in {h_s + D/radius, g_s, scale of the ratio}, out the ratio's scaled step eta.
 // The ratio's column b of the damped normal equations is a 1-wide dense border of S.  With S = L L^T, z = L^-1 g, z2 = L^-1 b:
 //   eta = (g_s - s z2.z) / (h_s + D - s^2 z2.z2),   L^T y = z - (s eta) z2
@@ -1556,6 +1612,13 @@ int32_t factor_and_solve(rsba_handle* h, double radius, RatioStep* ratio = nullp
   if (ratio) HIP_TRY(launch_ratio_prepare(s->ratio4, ratio->diag, ratio->gs, ratio->scale, st));
   int32_t rc = reduce_system(h, radius);
   if (rc) return rc;
+  if (s->pcg_on) {   // the iterative solver: no factor, no verification — its own residual is its check
+    if ((rc = solve_reduced_pcg(h))) return rc;
+    s->sv.step = s->pcg.y;
+    PhaseScope ps(h, RSBA_PHASE_BACK_SUBSTITUTE);
+    HIP_TRY(launch_back_substitute(h->dp, sv, st));
+    return RSBA_OK;
+  }
   if ((rc = solve_reduced_system(h, /*rhs_stays=*/!s->hp.two_rhs))) return rc;
   if (ratio) {
     HIP_TRY(hipMemcpyAsync(&ratio->eta, s->ratio4 + kRtEta, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1833,6 +1896,15 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver; SolverDev& sv = s->sv; DeviceProblem& dp = h->dp; hipStream_t st = h->stream;
+  // The iterative linear solver (rsba_set_linear_solver): what it does not take is refused before anything of the solve has run
+  s->pcg_on = h->lin_opt.type == RSBA_LINEAR_SOLVER_PCG;
+  h->lin_stats = rsba_linear_solver_stats{};
+  if (s->pcg_on) {
+    const char* why = s->border ? "a free interFrameRatio (its border column needs a second solve)"
+                    : h->allreduce ? "a handle with an exchange attached (one rank only)"
+                    : opt->level_scheduled_cholesky ? "options.level_scheduled_cholesky (there is no factorisation to schedule)" : nullptr;
+    if (why) { s->pcg_on = false; return rsba_set_error(RSBA_ERR_UNSUPPORTED, (std::string("the iterative linear solver does not take ") + why).c_str()); }
+  }
   sum->termination_type = RSBA_NO_CONVERGENCE;
   s->timer.on = opt->profile_phases != 0;
   if (s->timer.on) s->timer.reset();
@@ -1848,7 +1920,7 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
     // problem-size figures of the whole (all-rank) problem
     const double npri = sv.lead ? (double)h->prior_frames.size() + (double)h->pp_blocks.size() + (dp.pp_spherical >= 0 ? 1.0 : 0.0) : 0.0;
     // (+ how many ranks cannot run the loop without the host — no observations, or phase timers on: every rank must take the same form of the loop)
-    const bool host_form_only = dp.N == 0 || s->timer.on || test_hook("RSBA_DEVICE_LM_OFF_ON_THIS_RANK") != nullptr;
+    const bool host_form_only = dp.N == 0 || s->timer.on || s->pcg_on || test_hook("RSBA_DEVICE_LM_OFF_ON_THIS_RANK") != nullptr;   // (the iterative linear solver reads its convergence flag on the host)
     double cnt[4] = {(double)dp.N + npri, (double)(s->num_reduced_blocks + s->num_priors_reduced), (double)s->num_reduced_params, host_form_only ? 1.0 : 0.0};
     if (h->allreduce) {
       HIP_TRY(hipMemcpyAsync(sv.scalars + 8, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
