@@ -59,6 +59,77 @@ class HuberLoss : public LossFunction {
  private:
   double a_, b_;
 };
+// The other losses of ceres/loss_function.h, in its closed forms (the rule: rsba_amd.h, rsba_loss); the solve applies them on the device.
+class TrivialLoss : public LossFunction {
+ public:
+  void Evaluate(double s, double rho[3]) const override { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }
+};
+class SoftLOneLoss : public LossFunction {
+ public:
+  explicit SoftLOneLoss(double a) : a_(a), b_(a * a), c_(1.0 / b_) {}
+  void Evaluate(double s, double rho[3]) const override {
+    const double sum = 1.0 + s * c_, tmp = std::sqrt(sum);
+    rho[0] = 2.0 * b_ * (tmp - 1.0); rho[1] = std::max(std::numeric_limits<double>::min(), 1.0 / tmp); rho[2] = -(c_ * rho[1]) / (2.0 * sum);
+  }
+  double a() const { return a_; }
+ private:
+  double a_, b_, c_;
+};
+class CauchyLoss : public LossFunction {
+ public:
+  explicit CauchyLoss(double a) : a_(a), b_(a * a), c_(1.0 / b_) {}
+  void Evaluate(double s, double rho[3]) const override {
+    const double sum = 1.0 + s * c_, inv = 1.0 / sum;
+    rho[0] = b_ * std::log(sum); rho[1] = std::max(std::numeric_limits<double>::min(), inv); rho[2] = -c_ * (inv * inv);
+  }
+  double a() const { return a_; }
+ private:
+  double a_, b_, c_;
+};
+class ArctanLoss : public LossFunction {
+ public:
+  explicit ArctanLoss(double a) : a_(a), b_(1.0 / (a * a)) {}
+  void Evaluate(double s, double rho[3]) const override {
+    const double sum = 1.0 + s * s * b_, inv = 1.0 / sum;
+    rho[0] = a_ * std::atan2(s, a_); rho[1] = std::max(std::numeric_limits<double>::min(), inv); rho[2] = -2.0 * s * b_ * (inv * inv);
+  }
+  double a() const { return a_; }
+ private:
+  double a_, b_;
+};
+class TolerantLoss : public LossFunction {
+ public:
+  TolerantLoss(double a, double b) : a_(a), b_(b), c_(b * std::log(1.0 + std::exp(-a / b))) {}
+  void Evaluate(double s, double rho[3]) const override {
+    const double x = (s - a_) / b_;
+    if (x > 36.7) { rho[0] = s - a_ - c_; rho[1] = 1.0; rho[2] = 0.0; }   // (e^36.7 ~ 2^53: beyond it the loss is this to the last bit)
+    else {
+      const double e_x = std::exp(x);
+      rho[0] = b_ * std::log(1.0 + e_x) - c_; rho[1] = std::max(std::numeric_limits<double>::min(), e_x / (1.0 + e_x)); rho[2] = 0.5 / (b_ * (1.0 + std::cosh(x)));
+    }
+  }
+  double a() const { return a_; }
+  double b() const { return b_; }
+ private:
+  double a_, b_, c_;
+};
+// ceres::ScaledLoss: a times rho of the inner loss; a null inner loss is the trivial one
+class ScaledLoss : public LossFunction {
+ public:
+  ScaledLoss(const LossFunction* rho, double a, Ownership ownership) : rho_(rho), a_(a), ownership_(ownership) {}
+  ~ScaledLoss() override { if (ownership_ == TAKE_OWNERSHIP) delete rho_; }
+  void Evaluate(double s, double rho[3]) const override {
+    if (!rho_) { rho[0] = a_ * s; rho[1] = a_; rho[2] = 0.0; return; }
+    rho_->Evaluate(s, rho);
+    rho[0] *= a_; rho[1] *= a_; rho[2] *= a_;
+  }
+  const LossFunction* inner() const { return rho_; }
+  double scale() const { return a_; }
+ private:
+  ScaledLoss(const ScaledLoss&) = delete;
+  ScaledLoss& operator=(const ScaledLoss&) = delete;
+  const LossFunction* rho_; double a_; Ownership ownership_;
+};
 
 // ceres::LocalParameterization / ceres::SubsetParameterization (CeresHandler.h:355,367,378)
 class LocalParameterization {
@@ -350,11 +421,17 @@ class Problem {
     // per-pose priors: lowered to rsba_set_pose_priors
     std::vector<int32_t> pp_blocks; std::vector<double> pp_values; std::vector<double*> pp_ptr;   // GoodPosePrior: pose block, priorPoses values / where they came from
     double pp_rotation = 0, pp_position = 0; int32_t spherical_block = -1;
+    // a loss beyond HuberLoss (which desc.huber_a carries): lowered to rsba_set_loss
+    bool has_loss = false; rsba_loss loss;
   };
   // device problem of a flattened graph: rsba_create + the prior blocks
   static int32_t create_handle(const Flat& f, int device, rsba_handle** h) {
     int32_t st = rsba_create(&f.desc, device, h);
     if (st != RSBA_OK) return st;
+    if (f.has_loss) {
+      st = rsba_set_loss(*h, &f.loss);
+      if (st != RSBA_OK) { rsba_destroy(*h); *h = nullptr; return st; }
+    }
     if (!f.frame_global.empty()) {
       st = rsba_set_global_shutter_frames(*h, f.frame_global.data());
       if (st != RSBA_OK) { rsba_destroy(*h); *h = nullptr; return st; }
@@ -573,9 +650,23 @@ class Problem {
     d.poses = f->poses.data(); d.points = f->points.data(); d.intrinsics = f->intr.data(); d.frame_intrinsics = f->frame_intr.data();
     d.obs_xy = f->xy.data(); d.obs_frame = f->obs_frame.data(); d.obs_point = f->obs_point.data();
     d.pose_fixed_mask = f->pose_mask.data(); d.point_constant = f->point_const.data(); d.intrinsics_constant = f->intr_const.data();
+    // the loss: HuberLoss through huber_a as ever; the other losses of the library, and ONE ScaledLoss around any of them, through rsba_set_loss
     const HuberLoss* hl = dynamic_cast<const HuberLoss*>(loss0);
-    if (loss0 && !hl) return fail("only ceres::HuberLoss is supported");
     d.huber_a = hl ? hl->a() : 0.0;
+    if (loss0 && !hl) {
+      rsba_default_loss(&f->loss);
+      const LossFunction* l = loss0;
+      if (const ScaledLoss* sl = dynamic_cast<const ScaledLoss*>(l)) { f->loss.scale = sl->scale(); l = sl->inner(); }
+      if (!l || dynamic_cast<const TrivialLoss*>(l)) f->loss.type = RSBA_LOSS_TRIVIAL;
+      else if (const HuberLoss* q = dynamic_cast<const HuberLoss*>(l)) { f->loss.type = RSBA_LOSS_HUBER; f->loss.a = q->a(); }
+      else if (const SoftLOneLoss* q = dynamic_cast<const SoftLOneLoss*>(l)) { f->loss.type = RSBA_LOSS_SOFT_L_ONE; f->loss.a = q->a(); }
+      else if (const CauchyLoss* q = dynamic_cast<const CauchyLoss*>(l)) { f->loss.type = RSBA_LOSS_CAUCHY; f->loss.a = q->a(); }
+      else if (const ArctanLoss* q = dynamic_cast<const ArctanLoss*>(l)) { f->loss.type = RSBA_LOSS_ARCTAN; f->loss.a = q->a(); }
+      else if (const TolerantLoss* q = dynamic_cast<const TolerantLoss*>(l)) { f->loss.type = RSBA_LOSS_TOLERANT; f->loss.a = q->a(); f->loss.b = q->b(); }
+      else return fail("unsupported loss function: accepted are TrivialLoss, HuberLoss, SoftLOneLoss, CauchyLoss, ArctanLoss, TolerantLoss, and one ScaledLoss "
+                       "around one of them (user-defined losses, ComposedLoss and nested ScaledLoss are not: the solve has no host callback)");
+      f->has_loss = true;
+    }
     return true;
   }
 

@@ -60,7 +60,7 @@ typedef struct rsba_problem_desc {
                                        CeresHandler.h:350-382); 0x3f = SetParameterBlockConstant (:342-348); NULL = free */
   const uint8_t* point_constant;    /* [M] SetParameterBlockConstant on points (CeresHandler.h:288-300); NULL = free */
   const uint8_t* intrinsics_constant; /* [NI] (CeresHandler.h:284,347); NULL = free */
-  double huber_a;                /* opt.ceres.huberLoss: > 0 -> one shared ceres::HuberLoss(a) (CeresHandler.h:85-90) */
+  double huber_a;                /* opt.ceres.huberLoss: > 0 -> one shared ceres::HuberLoss(a) (CeresHandler.h:85-90); any other loss: rsba_set_loss */
 } rsba_problem_desc;
 
 typedef struct rsba_handle rsba_handle;   /* stands for the ceres::Problem member of CeresHandler (CeresHandler.h:78) */
@@ -222,6 +222,38 @@ typedef struct rsba_linear_solver_stats {
 void rsba_default_linear_solver_options(rsba_linear_solver_options* opt);
 int32_t rsba_set_linear_solver(rsba_handle* h, const rsba_linear_solver_options* opt);
 int32_t rsba_get_linear_solver_stats(rsba_handle* h, rsba_linear_solver_stats* out);
+
+/* == the loss function CeresHandler passes to every reprojection block and to the motion-prior blocks, beyond the one HuberLoss that
+ * rsba_problem_desc::huber_a describes: the losses of ceres/loss_function.h (Ceres-Solver 1.9.0), one for the whole problem.  Ceres is
+ * not part of the tree; the text below is THIS library's definition.
+ * With s = |r|^2 of a residual block a loss returns rho = {rho(s), rho'(s), rho''(s)}; min = DBL_MIN; every form is evaluated as written:
+ *   TRIVIAL                 rho = {s, 1, 0}
+ *   HUBER(a)      b = a^2;  s <= b: {s, 1, 0};  s > b: with r = sqrt(s)  {2 a r - b, max(min, a / r), -rho1 / (2 s)}
+ *   SOFT_L_ONE(a) b = a^2, c = 1 / b, sum = 1 + s c, t = sqrt(sum):      {2 b (t - 1), max(min, 1 / t), -(c rho1) / (2 sum)}
+ *   CAUCHY(a)     b = a^2, c = 1 / b, sum = 1 + s c, inv = 1 / sum:      {b log(sum), max(min, inv), -c inv^2}
+ *   ARCTAN(a)     b = 1 / a^2, sum = 1 + s^2 b, inv = 1 / sum:           {a atan2(s, a), max(min, inv), -2 s b inv^2}
+ *   TOLERANT(a, b) c = b log(1 + exp(-a / b)), x = (s - a) / b;  x > 36.7: {s - a - c, 1, 0};
+ *                 otherwise with e = exp(x)                              {b log(1 + e) - c, max(min, e / (1 + e)), 0.5 / (b (1 + cosh x))}
+ * and scale > 0 multiplies all three (ceres::ScaledLoss; 1 = no scaling).
+ * The corrector (ceres corrector.cc) is the same for every loss.  If s == 0 or rho2 <= 0: r~ = sqrt(rho1) r, J~ = sqrt(rho1) J.
+ * Otherwise D = 1 + 2 s rho2 / rho1, alpha = 1 - sqrt(D), r~ = sqrt(rho1) / (1 - alpha) r, J~ = sqrt(rho1) (J - (alpha / s) r (r^T J)).
+ * The cost of a block is rho0 / 2 of the UNcorrected residual.  Of the set only TOLERANT has rho2 > 0.
+ * The loss applies exactly where huber_a applies: reprojection blocks and motion-prior blocks; never to GoodPosePrior / SphericalPrior
+ * blocks, PnP, the filter or track creation.
+ * rsba_set_loss is valid between calls and takes effect at the next rsba_evaluate / rsba_gradient / rsba_solve / rsba_pose_covariance.
+ * A handle created with huber_a > 0 reports {HUBER, a, scale 1}, one created without {TRIVIAL, scale 1}; rsba_set_loss({HUBER, a, scale 1})
+ * gives the bits of a handle created with huber_a = a, and TRIVIAL at scale 1 those of one created without a loss: both run the code
+ * they ran before this call existed.  RSBA_ERR_INVALID_ARGUMENT (the handle keeps its loss) for a, TOLERANT's b or scale that is not
+ * positive and finite (a and b are ignored where the type does not use them), and for an unknown type.
+ * Several ranks (rsba_set_exchange): every rank sets the same loss before the collective call. */
+enum { RSBA_LOSS_TRIVIAL = 0, RSBA_LOSS_HUBER = 1, RSBA_LOSS_SOFT_L_ONE = 2, RSBA_LOSS_CAUCHY = 3, RSBA_LOSS_ARCTAN = 4, RSBA_LOSS_TOLERANT = 5 };
+typedef struct rsba_loss {
+  int32_t type, reserved;
+  double a, b, scale;
+} rsba_loss;
+void rsba_default_loss(rsba_loss* loss);                       /* TRIVIAL, a = b = 0, scale 1 */
+int32_t rsba_set_loss(rsba_handle* h, const rsba_loss* loss);
+int32_t rsba_get_loss(rsba_handle* h, rsba_loss* out);
 
 /* Measurement aids: where an LM iteration spends its device time, and the sizes of the symbolic plan the
  * kernels' algorithmic bytes / flops follow from.  Phase p covers the launches listed; ms[p] is the HIP-event time summed

@@ -28,8 +28,10 @@ EXPORTS = [
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
     "rsba_match_descriptors", "rsba_match_last_kernel_ms",
     "rsba_default_linear_solver_options", "rsba_set_linear_solver", "rsba_get_linear_solver_stats",
+    "rsba_default_loss", "rsba_set_loss", "rsba_get_loss",
 ]
 LINEAR_SOLVER_EXACT, LINEAR_SOLVER_PCG = 0, 1   # rsba_amd.h: RSBA_LINEAR_SOLVER_*
+LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TOLERANT = range(6)   # rsba_amd.h: RSBA_LOSS_*
 NUM_EXCHANGES = 6
 NUM_PHASES = 13
 
@@ -103,6 +105,10 @@ class LinearSolverStats(C.Structure):
                 ("last_relative_residual", C.c_double)]
 
 
+class Loss(C.Structure):
+    _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("scale", C.c_double)]
+
+
 class PhaseTimes(C.Structure):
     _fields_ = [("ms", C.c_double * NUM_PHASES), ("calls", C.c_int32 * NUM_PHASES), ("reserved", C.c_int32)]
 
@@ -146,6 +152,7 @@ def lib():
         _lib.rsba_release_host_scratch.restype = None
         _lib.rsba_default_solver_options.restype = None
         _lib.rsba_default_linear_solver_options.restype = None
+        _lib.rsba_default_loss.restype = None
         _lib.rsba_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         _lib.rsba_destroy.argtypes = [C.c_void_p]
         _lib.rsba_phase_name.restype = C.c_char_p
@@ -275,6 +282,20 @@ class DeviceProblem:
         st = LinearSolverStats()
         _check(lib().rsba_get_linear_solver_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in LinearSolverStats._fields_}
+
+    def set_loss(self, type: int = LOSS_TRIVIAL, a: float = 0.0, b: float = 0.0, scale: float = 1.0):
+        """rsba_set_loss: the loss of the reprojection and motion-prior blocks from the next evaluate / gradient / solve / covariance on —
+        LOSS_TRIVIAL, LOSS_HUBER(a), LOSS_SOFT_L_ONE(a), LOSS_CAUCHY(a), LOSS_ARCTAN(a), LOSS_TOLERANT(a, b), times ``scale`` (rsba_amd.h)."""
+        o = Loss()
+        lib().rsba_default_loss(C.byref(o))
+        o.type, o.a, o.b, o.scale = int(type), float(a), float(b), float(scale)
+        _check(lib().rsba_set_loss(self._h, C.byref(o)))
+
+    def loss(self) -> dict:
+        """rsba_get_loss: {"type", "a", "b", "scale"} of the handle's loss."""
+        o = Loss()
+        _check(lib().rsba_get_loss(self._h, C.byref(o)))
+        return dict(type=int(o.type), a=float(o.a), b=float(o.b), scale=float(o.scale))
 
     def set_stream(self, raw_stream: int | None):
         _check(lib().rsba_set_stream(self._h, C.c_void_p(raw_stream or 0)))

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <numeric>
 #include <mutex>
@@ -230,6 +231,7 @@ int32_t rsba_create(const rsba_problem_desc* d, int32_t device, rsba_handle** ou
   dp.ntiles = std::max<int64_t>((N + kEvalBlock - 1) / kEvalBlock, 1);
   dp.K = (dp.calibrated ? 0 : 9) + 6 * dp.P + 3;
   dp.huber_a = d->huber_a;
+  dp.loss_type = d->huber_a > 0.0 ? RSBA_LOSS_HUBER : RSBA_LOSS_TRIVIAL; dp.loss_a = d->huber_a > 0.0 ? d->huber_a : 0.0; dp.loss_scale = 1.0;   // (rsba_set_loss: any other loss)
   const size_t npose = (size_t)dp.F * dp.P * 6;
 
   stage("handle");
@@ -573,6 +575,43 @@ int32_t rsba_set_linear_solver(rsba_handle* h, const rsba_linear_solver_options*
 int32_t rsba_get_linear_solver_stats(rsba_handle* h, rsba_linear_solver_stats* out) {
   if (!h || !out) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   *out = h->lin_stats;
+  return RSBA_OK;
+}
+
+void rsba_default_loss(rsba_loss* l) {
+  if (!l) return;
+  l->type = RSBA_LOSS_TRIVIAL; l->reserved = 0; l->a = 0.0; l->b = 0.0; l->scale = 1.0;
+}
+
+int32_t rsba_set_loss(rsba_handle* h, const rsba_loss* l) {
+  if (!h || !l) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  auto good = [](double v) { return v > 0.0 && std::isfinite(v); };
+  if (l->type < RSBA_LOSS_TRIVIAL || l->type > RSBA_LOSS_TOLERANT) return fail(RSBA_ERR_INVALID_ARGUMENT, "loss type: RSBA_LOSS_TRIVIAL .. RSBA_LOSS_TOLERANT");
+  if (l->type != RSBA_LOSS_TRIVIAL && !good(l->a)) return fail(RSBA_ERR_INVALID_ARGUMENT, "loss parameter a must be positive and finite");
+  if (l->type == RSBA_LOSS_TOLERANT && !good(l->b)) return fail(RSBA_ERR_INVALID_ARGUMENT, "TOLERANT: loss parameter b must be positive and finite");
+  if (!good(l->scale)) return fail(RSBA_ERR_INVALID_ARGUMENT, "loss scale must be positive and finite");
+  DeviceProblem& dp = h->dp;
+  const bool was_general = dp.loss_general != 0;
+  const double a = l->type == RSBA_LOSS_TRIVIAL ? 0.0 : l->a;
+  // none, and Huber at scale 1: the one number the kernels have always looked at — their instantiations of old, bit for bit
+  const bool general = l->scale != 1.0 || (l->type != RSBA_LOSS_TRIVIAL && l->type != RSBA_LOSS_HUBER);
+  dp.loss_general = general ? 1 : 0; dp.loss_type = l->type; dp.loss_a = a; dp.loss_scale = l->scale;
+  dp.huber_a = (!general && l->type == RSBA_LOSS_HUBER) ? a : 0.0;
+  dp.loss_b = 0.0; dp.loss_c = 0.0;
+  switch (l->type) {   // the constants of ceres' constructors
+    case RSBA_LOSS_SOFT_L_ONE: case RSBA_LOSS_CAUCHY: dp.loss_b = a * a; dp.loss_c = 1.0 / dp.loss_b; break;
+    case RSBA_LOSS_ARCTAN: dp.loss_b = 1.0 / (a * a); break;
+    case RSBA_LOSS_TOLERANT: dp.loss_b = l->b; dp.loss_c = l->b * std::log(1.0 + std::exp(-a / l->b)); break;
+    default: break;
+  }
+  if (was_general && !general) return rsba_solver_loss_changed(h);
+  return RSBA_OK;
+}
+
+int32_t rsba_get_loss(rsba_handle* h, rsba_loss* out) {
+  if (!h || !out) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  const DeviceProblem& dp = h->dp;
+  out->type = dp.loss_type; out->reserved = 0; out->a = dp.loss_a; out->b = dp.loss_type == RSBA_LOSS_TOLERANT ? dp.loss_b : 0.0; out->scale = dp.loss_scale;
   return RSBA_OK;
 }
 

@@ -80,8 +80,12 @@ struct DeviceProblem {
   double* prior_partial;         // [2 * ceil(F / 64)] per-wave partial sums of the prior reductions
   unsigned* prior_ticket;        // arrival counter of those reductions (zero between launches)
   const double* ctl;             // trust-region state on the device (LmCtlSlot; solver.hip: the LM loop's decisions taken by a kernel), null = the host decides
+  // The problem's loss beyond "none" and Huber (rsba_set_loss).  loss_general = 0: none, or HuberLoss(huber_a) at scale 1 — the kernels'
+  // instantiations that look at huber_a alone, as ever; 1: the launchers pick the GENERAL instantiations, which evaluate
+  // general_rho(loss_type, ..) (obs_math.hpp) and apply the whole corrector (lm_record.hpp).  huber_a is 0 then.
+  int loss_general, loss_type;   // LossType
+  double loss_a, loss_b, loss_c, loss_scale;   // a; the constants b, c of the loss' form (TOLERANT: its parameter b, and c); ScaledLoss' factor
 };
-
 // Trust-region control on the device: the scalars of Ceres' TrustRegionMinimizer loop live in HBM, a single-thread
 // kernel takes its decisions (kernels_normal.hip: lm_decide_*), and the kernels of an iteration look at them instead of waiting for
 // the host: the host enqueues iterations AHEAD and reads the state of each from a slot of host memory the last kernel of the iteration

@@ -24,7 +24,8 @@ __device__ __forceinline__ double swap_pair(double v) {
   return __hiloint2double(hi, lo);
 }
 
-template <bool CAL, int P, int MODE>
+// GEN: the general instantiation of a problem whose loss is neither none nor Huber at scale 1 (dp.loss_general; lm_record.hpp)
+template <bool CAL, int P, int MODE, bool GEN = false>
 __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const DeviceProblem dp) {
   if (MODE == kLmJacobian && lm_stopped(dp.ctl)) return;   // (device-side trust region: the solve is over, iterations enqueued ahead fall through)
   constexpr int CD = 6 * P;
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const DeviceProblem dp
         for (int k = 0; k < CD; ++k) psc[k] = dp.scale_pose[(size_t)f * CD + k];
       }
       bool dropped;
-      lm_observation<CAL, P>(dp, f, j, xy.x, xy.y, pose, psc, o, half_rho, dropped);   // loss-corrected, masked, scaled (lm_record.hpp)
+      lm_observation<CAL, P, GEN>(dp, f, j, xy.x, xy.y, pose, psc, o, half_rho, dropped);   // loss-corrected, masked, scaled (lm_record.hpp)
       if (valid && !o.ok) nfail = 1.0;
       if (!valid) half_rho = 0.0;
       if (dropped) { fixed = half_rho; half_rho = 0.0; }
@@ -104,7 +105,8 @@ __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const DeviceProblem dp
       // Ceres 1.9 ResidualBlock::Evaluate: cost = rho0/2 from the uncorrected residual
       const double s = o.r[0] * o.r[0] + o.r[1] * o.r[1];
       double rho[3] = {s, 1.0, 0.0};
-      if (dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
+      if constexpr (GEN) general_rho(dp.loss_type, dp.loss_a, dp.loss_b, dp.loss_c, dp.loss_scale, s, rho);
+      else if (dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
       half_rho = (o.ok && valid) ? 0.5 * rho[0] : 0.0;
     }
 
@@ -314,15 +316,19 @@ hipError_t launch_cost_reduce(const DeviceProblem& dp, double* out2, hipStream_t
 
 int eval_num_blocks(int64_t n) { return (int)((n + kEvalBlock - 1) / kEvalBlock); }
 
-template <bool CAL, int P>
-static hipError_t launch_mode(const DeviceProblem& dp, EvalMode mode, hipStream_t st) {
+template <bool CAL, int P, bool GEN>
+static hipError_t launch_mode_as(const DeviceProblem& dp, EvalMode mode, hipStream_t st) {
   const dim3 grid(eval_num_blocks(dp.N)), block(kEvalBlock);
   switch (mode) {
-    case kResidualOnly: hipLaunchKernelGGL((eval_kernel<CAL, P, kResidualOnly>), grid, block, 0, st, dp); break;
-    case kRawJacobian: hipLaunchKernelGGL((eval_kernel<CAL, P, kRawJacobian>), grid, block, 0, st, dp); break;
-    case kLmJacobian: hipLaunchKernelGGL((eval_kernel<CAL, P, kLmJacobian>), grid, block, 0, st, dp); break;
+    case kResidualOnly: hipLaunchKernelGGL((eval_kernel<CAL, P, kResidualOnly, GEN>), grid, block, 0, st, dp); break;
+    case kRawJacobian: hipLaunchKernelGGL((eval_kernel<CAL, P, kRawJacobian, GEN>), grid, block, 0, st, dp); break;
+    case kLmJacobian: hipLaunchKernelGGL((eval_kernel<CAL, P, kLmJacobian, GEN>), grid, block, 0, st, dp); break;
   }
   return hipGetLastError();
+}
+template <bool CAL, int P>
+static hipError_t launch_mode(const DeviceProblem& dp, EvalMode mode, hipStream_t st) {
+  return dp.loss_general ? launch_mode_as<CAL, P, true>(dp, mode, st) : launch_mode_as<CAL, P, false>(dp, mode, st);
 }
 
 hipError_t launch_eval(const DeviceProblem& dp, EvalMode mode, hipStream_t st) {

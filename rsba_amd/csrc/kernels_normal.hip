@@ -928,7 +928,8 @@ __global__ void slot_xy_kernel(const DeviceProblem dp, double2* __restrict__ slo
 }
 
 // the record of slot s (clamped by the caller): pose and scales straight from L2 (F x 192 B: resident)
-template <bool CAL, int P>
+// (GEN: the general-loss instantiation, lm_record.hpp — chosen by the launchers from dp.loss_general, like every GEN below)
+template <bool CAL, int P, bool GEN = false>
 __device__ __forceinline__ void slot_record(const DeviceProblem& dp, const SolverDev& sv, int64_t s, ObsOut<CAL, P>& o, int& frame, int& point) {
   constexpr int CD = 6 * P;
   frame = sv.slot_frame[s]; point = sv.slot_point[s];
@@ -937,7 +938,7 @@ __device__ __forceinline__ void slot_record(const DeviceProblem& dp, const Solve
 #pragma unroll
   for (int k = 0; k < CD; ++k) { pose[k] = dp.poses[(size_t)frame * CD + k]; psc[k] = dp.scale_pose[(size_t)frame * CD + k]; }
   double half_rho; bool dropped;
-  lm_observation<CAL, P>(dp, frame, point, xy.x, xy.y, pose, psc, o, half_rho, dropped);
+  lm_observation<CAL, P, GEN>(dp, frame, point, xy.x, xy.y, pose, psc, o, half_rho, dropped);
 }
 
 // K5b without records: P = Jc^T (Jp L^-T) of 64 consecutive slots per wave and step, into the group layout (see project_kernel).
@@ -949,7 +950,7 @@ __device__ __forceinline__ void slot_record(const DeviceProblem& dp, const Solve
 // ALLF: every slot's group is factored (SolverDev::all_real_factored — the rule for two-pose problems; a tile that mixes real and pseudo
 // frames is the exception): 19 doubles per slot go through LDS instead of 36 — 40 KB per workgroup instead of 76, and with the register
 // budget of three waves per SIMD the pass, which is bound by its fp64 arithmetic, runs three workgroups per CU instead of two.
-template <bool CAL, int P, bool ALLF>
+template <bool CAL, int P, bool ALLF, bool GEN = false>
 __global__ __launch_bounds__(256, ALLF ? 3 : 1) void project_rc_kernel(const DeviceProblem dp, const SolverDev sv, int nch) {
   if (lm_stopped(sv.ctl)) return;   // (device-side trust region: the solve is over, iterations enqueued ahead fall through)
   static_assert(!ALLF || P == 2, "factored groups are a two-pose form");
@@ -966,7 +967,7 @@ __global__ __launch_bounds__(256, ALLF ? 3 : 1) void project_rc_kernel(const Dev
     const int64_t s = s0 + lane < se ? s0 + lane : se - 1;   // (lanes past the end repeat the last slot; nothing of theirs is stored)
     ObsOut<CAL, P> o;
     int frame, j;
-    slot_record<CAL, P>(dp, sv, s, o, frame, j);
+    slot_record<CAL, P, GEN>(dp, sv, s, o, frame, j);
     const double* li = sv.Linv + (size_t)j * 6;
     const double i00 = li[0], i10 = li[1], i11 = li[2], i20 = li[3], i21 = li[4], i22 = li[5];
     double B[2][3];
@@ -1059,7 +1060,7 @@ inline int sweep_points(int64_t M) {
 // WAVE_DOUBLES: a wave's share of the dynamic LDS (>= 64 NCP; the fused sweep below keeps a staging area in the same doubles).  per_slot also
 // gets the slot's index and the wave's LDS; per_batch(wave's LDS, slots of the batch) runs once the 64 slots of a batch have been through
 // per_slot, between two wave barriers, BEFORE the batch's numbers go into the same LDS.
-template <bool CAL, int P, int NC, int NCP, int WAVE_DOUBLES, class PerSlot, class PerBatch, class PerPoint>
+template <bool CAL, int P, bool GEN, int NC, int NCP, int WAVE_DOUBLES, class PerSlot, class PerBatch, class PerPoint>
 __device__ __forceinline__ double point_sweep_hooked(const DeviceProblem& dp, const SolverDev& sv, double* smem, int sp, int64_t block, PerSlot per_slot, PerBatch per_batch, PerPoint per_point) {
   static_assert(NC % NCP == 0 && kSweepPoints * NC <= 64 * NCP && WAVE_DOUBLES >= 64 * NCP, "passes of equal width; the final gather fits the buffer");
   constexpr int NPART = NC / NCP, NPAIR = kSweepPoints * NCP, PER = (NPAIR + 63) / 64;   // pairs (point, component of a pass): sized for the most points a wave takes; sp <= kSweepPoints of them this launch
@@ -1094,7 +1095,7 @@ __device__ __forceinline__ double point_sweep_hooked(const DeviceProblem& dp, co
         const int64_t s = c0 + lane < se ? c0 + lane : se - 1;
         ObsOut<CAL, P> o;
         int frame, pt;
-        slot_record<CAL, P>(dp, sv, s, o, frame, pt);
+        slot_record<CAL, P, GEN>(dp, sv, s, o, frame, pt);
         per_slot(o, frame, pt, s, cbuf, c);
       }
       per_batch(cbuf, nrec, wave_sync);
@@ -1138,18 +1139,18 @@ __device__ __forceinline__ double point_sweep_hooked(const DeviceProblem& dp, co
   __syncthreads();
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
-template <bool CAL, int P, int NC, int NCP = NC, class PerSlot, class PerPoint>
+template <bool CAL, int P, bool GEN, int NC, int NCP = NC, class PerSlot, class PerPoint>
 __device__ __forceinline__ double point_sweep(const DeviceProblem& dp, const SolverDev& sv, double* smem, int sp, int64_t block, PerSlot per_slot, PerPoint per_point) {
-  return point_sweep_hooked<CAL, P, NC, NCP, 64 * NCP>(dp, sv, smem, sp, block,
+  return point_sweep_hooked<CAL, P, GEN, NC, NCP, 64 * NCP>(dp, sv, smem, sp, block,
     [&](const ObsOut<CAL, P>& o, int frame, int pt, int64_t, double*, double* c) { per_slot(o, frame, pt, c); },
     [](double*, int, auto&) {}, per_point);
 }
 
 // K2b without records: V_j, g_p,j
-template <bool CAL, int P>
+template <bool CAL, int P, bool GEN>
 __device__ __forceinline__ void point_blocks_sweep(const DeviceProblem& dp, const SolverDev& sv, double* smem, int sp, int64_t block) {
   constexpr int CD = (CAL ? 0 : 9) + 6 * P;   // columns in front of the point's
-  point_sweep<CAL, P, 9>(dp, sv, smem, sp, block,
+  point_sweep<CAL, P, GEN, 9>(dp, sv, smem, sp, block,
     [&](const ObsOut<CAL, P>& o, int, int, double c[9]) {
       const double r0 = o.r[0], r1 = o.r[1], p0[3] = {o.J[0][CD], o.J[0][CD + 1], o.J[0][CD + 2]}, p1[3] = {o.J[1][CD], o.J[1][CD + 1], o.J[1][CD + 2]};
       c[0] = p0[0] * p0[0] + p1[0] * p1[0]; c[1] = p0[0] * p0[1] + p1[0] * p1[1]; c[2] = p0[0] * p0[2] + p1[0] * p1[2];
@@ -1165,32 +1166,32 @@ __device__ __forceinline__ void point_blocks_sweep(const DeviceProblem& dp, cons
       return 0.0;
     });
 }
-template <bool CAL, int P>
+template <bool CAL, int P, bool GEN = false>
 __global__ __launch_bounds__(256) void point_blocks_rc_kernel(const DeviceProblem dp, const SolverDev sv, int sp) {
   if (lm_not_accepted(sv.ctl)) return;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  point_blocks_sweep<CAL, P>(dp, sv, smem, sp, blockIdx.x);
+  point_blocks_sweep<CAL, P, GEN>(dp, sv, smem, sp, blockIdx.x);
 }
 // The linearisation of an accepted candidate in ONE launch (the loop that runs without the host): the frames' camera blocks, the copy of
 // the candidate over x, and the points' blocks side by side — neither reads what the other writes; the point sweeps read the candidate
 // where it still lies (dq: dp with the trial buffers for parameters), since the copy over x is in flight beside them.
-template <bool CAL, int P>
+template <bool CAL, int P, bool GEN = false>
 __global__ __launch_bounds__(256) void linearize_blocks_kernel(const DeviceProblem dp, const DeviceProblem dq, const SolverDev sv, int sp, int ntake) {
   if (lm_not_accepted(sv.ctl)) return;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int b = blockIdx.x;
   if (b < dp.F) camera_reduce_frame<6 * P, CAL>(dp, sv, b);
   else if (b < dp.F + ntake) take_candidate_block(dp, sv, b - dp.F);
-  else point_blocks_sweep<CAL, P>(dq, sv, smem, sp, (int64_t)b - dp.F - ntake);
+  else point_blocks_sweep<CAL, P, GEN>(dq, sv, smem, sp, (int64_t)b - dp.F - ntake);
 }
 
 // K7 + K8 without records (see point_step_kernel)
-template <bool CAL, int P>
+template <bool CAL, int P, bool GEN = false>
 __global__ __launch_bounds__(256) void point_step_rc_kernel(const DeviceProblem dp, const SolverDev sv, int sp) {
   if (lm_stopped(sv.ctl)) return;
   constexpr int CD = 6 * P, OP = CAL ? 0 : 9, OX = OP + CD;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const double mc = point_sweep<CAL, P, 5>(dp, sv, smem, sp, blockIdx.x,
+  const double mc = point_sweep<CAL, P, GEN, 5>(dp, sv, smem, sp, blockIdx.x,
     [&](const ObsOut<CAL, P>& o, int frame, int, double c[5]) {
       const double* yc = sv.step + (size_t)frame * CD;
       double t0 = 0.0, t1 = 0.0;
@@ -1224,12 +1225,12 @@ __global__ __launch_bounds__(256) void point_step_rc_kernel(const DeviceProblem 
 
 // the virtual records of the intrinsics pseudo frames without records, ONE intrinsics block (the shared sess.cam): per point
 // Q_j = sum_o Ji_o^T (Jp_o L_j^-T) (9 x 3), cut into the NPF pseudo-frame records of the point's virtual slots (see virtual_records_kernel)
-template <int P>
+template <int P, bool GEN = false>
 __global__ __launch_bounds__(256) void virtual_records_rc_kernel(const DeviceProblem dp, const SolverDev sv, int sp) {
   if (lm_stopped(sv.ctl)) return;
   constexpr int CD = 6 * P, OX = 9 + CD;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  point_sweep<false, P, 27, 9>(dp, sv, smem, sp, blockIdx.x,
+  point_sweep<false, P, GEN, 27, 9>(dp, sv, smem, sp, blockIdx.x,
     [&](const ObsOut<false, P>& o, int, int j, double c[27]) {
       const double* li = sv.Linv + (size_t)j * 6;
       const double i00 = li[0], i10 = li[1], i11 = li[2], i20 = li[3], i21 = li[4], i22 = li[5];
@@ -1271,12 +1272,13 @@ __global__ __launch_bounds__(256) void virtual_records_rc_kernel(const DevicePro
 // passes evaluate the same observations against the same point factors, and together they are bound by the vector unit they share.
 // A wave's LDS: [64][19] staging of q = Jq^T (Jp L^-T) | tau per slot, then 64 group positions; the sums' nine-component passes reuse its front.
 constexpr int kFusedStage = 19, kFusedWaveDoubles = 64 * kFusedStage + 32;
+template <bool GEN = false>
 __global__ __launch_bounds__(256) void virtual_project_rc_kernel(const DeviceProblem dp, const SolverDev sv, int sp) {
   if (lm_stopped(sv.ctl)) return;
   constexpr int P = 2, CD = 12, OX = 9 + CD;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63;
-  point_sweep_hooked<false, P, 27, 9, kFusedWaveDoubles>(dp, sv, smem, sp, blockIdx.x,
+  point_sweep_hooked<false, P, GEN, 27, 9, kFusedWaveDoubles>(dp, sv, smem, sp, blockIdx.x,
     [&](const ObsOut<false, P>& o, int, int j, int64_t s, double* wl, double c[27]) {
       const double* li = sv.Linv + (size_t)j * 6;
       const double i00 = li[0], i10 = li[1], i11 = li[2], i20 = li[3], i21 = li[4], i22 = li[5];
@@ -1672,6 +1674,10 @@ hipError_t launch_camera_blocks(const DeviceProblem& dp, const SolverDev& sv, hi
   else { if (dp.calibrated) LAUNCH((camera_reduce_kernel<6, true>), grid, 256, st, dp, sv); else LAUNCH((camera_reduce_kernel<6, false>), grid, 256, st, dp, sv); }
   return hipSuccess;
 }
+// the launchers of the kernels that recompute records: f(std::true_type) for a problem with a general loss (dp.loss_general: the GEN
+// instantiations), f(std::false_type) otherwise — the instantiations there have always been
+template <class F>
+static inline void by_loss(const DeviceProblem& dp, F f) { if (dp.loss_general) f(std::true_type{}); else f(std::false_type{}); }
 // camera blocks + the accepted candidate's copy over x + point blocks by one launch (linearize_blocks_kernel); *done = false: not for
 // this problem (records kept, or nothing to sweep) — the caller launches them one after the other
 hipError_t launch_linearize_blocks(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st, bool* done) {
@@ -1684,8 +1690,11 @@ hipError_t launch_linearize_blocks(const DeviceProblem& dp, const SolverDev& sv,
   const int ntake = (int)((nparam + 255) / 256), sp = sweep_points(dp.M), npts = (int)((dp.M + 4 * sp - 1) / (4 * sp));
   const size_t lds = (size_t)4 * 64 * 9 * sizeof(double);
   const dim3 grid((unsigned)(dp.F + ntake + npts));
-  if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((linearize_blocks_kernel<true, 2>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); else hipLaunchKernelGGL((linearize_blocks_kernel<true, 1>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); }
-  else { if (sv.CD == 12) hipLaunchKernelGGL((linearize_blocks_kernel<false, 2>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); else hipLaunchKernelGGL((linearize_blocks_kernel<false, 1>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); }
+  by_loss(dp, [&](auto gen) {
+    constexpr bool GEN = decltype(gen)::value;
+    if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((linearize_blocks_kernel<true, 2, GEN>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); else hipLaunchKernelGGL((linearize_blocks_kernel<true, 1, GEN>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); }
+    else { if (sv.CD == 12) hipLaunchKernelGGL((linearize_blocks_kernel<false, 2, GEN>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); else hipLaunchKernelGGL((linearize_blocks_kernel<false, 1, GEN>), grid, dim3(256), lds, st, dp, dq, sv, sp, ntake); }
+  });
   *done = true;
   return hipGetLastError();
 }
@@ -1698,8 +1707,11 @@ hipError_t launch_point_blocks(const DeviceProblem& dp, const SolverDev& sv, hip
     if (dp.M <= 0) return hipSuccess;
     const size_t lds = (size_t)4 * 64 * 9 * sizeof(double);
     const int sp = sweep_points(dp.M), grid = (int)((dp.M + 4 * sp - 1) / (4 * sp));
-    if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((point_blocks_rc_kernel<true, 2>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_blocks_rc_kernel<true, 1>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
-    else { if (sv.CD == 12) hipLaunchKernelGGL((point_blocks_rc_kernel<false, 2>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_blocks_rc_kernel<false, 1>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+    by_loss(dp, [&](auto gen) {
+      constexpr bool GEN = decltype(gen)::value;
+      if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((point_blocks_rc_kernel<true, 2, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_blocks_rc_kernel<true, 1, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+      else { if (sv.CD == 12) hipLaunchKernelGGL((point_blocks_rc_kernel<false, 2, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_blocks_rc_kernel<false, 1, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+    });
     return hipGetLastError();
   }
   LAUNCH(point_blocks_kernel, nblocks256(dp.M), 256, st, dp, sv);
@@ -1782,7 +1794,7 @@ hipError_t launch_project(const DeviceProblem& dp, const SolverDev& sv, hipStrea
   if (project_covers_virtual_records(dp, sv)) {
     const size_t lds = (size_t)4 * kFusedWaveDoubles * sizeof(double);
     const int sp = sweep_points(dp.M), grid = (int)((dp.M + 4 * sp - 1) / (4 * sp));
-    hipLaunchKernelGGL(virtual_project_rc_kernel, dim3(grid), dim3(256), lds, st, dp, sv, sp);
+    by_loss(dp, [&](auto gen) { hipLaunchKernelGGL((virtual_project_rc_kernel<decltype(gen)::value>), dim3(grid), dim3(256), lds, st, dp, sv, sp); });
     return hipGetLastError();
   }
   const int KC = dp.K - 3;
@@ -1791,9 +1803,12 @@ hipError_t launch_project(const DeviceProblem& dp, const SolverDev& sv, hipStrea
     const bool allf = CD == 12 && sv.all_real_factored != 0;
     const size_t lds = (size_t)4 * (64 * (allf ? 19 : ((CD * 3) | 1)) + 32) * sizeof(double);
     const int nch = project_chunks(dp.N), grid = (int)((dp.N + 256 * (int64_t)nch - 1) / (256 * (int64_t)nch));
-    if (allf) { if (dp.calibrated) hipLaunchKernelGGL((project_rc_kernel<true, 2, true>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<false, 2, true>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
-    else if (dp.calibrated) { if (CD == 12) hipLaunchKernelGGL((project_rc_kernel<true, 2, false>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<true, 1, false>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
-    else { if (CD == 12) hipLaunchKernelGGL((project_rc_kernel<false, 2, false>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<false, 1, false>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
+    by_loss(dp, [&](auto gen) {
+      constexpr bool GEN = decltype(gen)::value;
+      if (allf) { if (dp.calibrated) hipLaunchKernelGGL((project_rc_kernel<true, 2, true, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<false, 2, true, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
+      else if (dp.calibrated) { if (CD == 12) hipLaunchKernelGGL((project_rc_kernel<true, 2, false, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<true, 1, false, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
+      else { if (CD == 12) hipLaunchKernelGGL((project_rc_kernel<false, 2, false, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); else hipLaunchKernelGGL((project_rc_kernel<false, 1, false, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, nch); }
+    });
     return hipGetLastError();
   }
   if (sv.CD == 12 && KC == 12) return launch_project_as<12, 12>(dp, sv, st);
@@ -1815,8 +1830,11 @@ hipError_t launch_virtual_records(const DeviceProblem& dp, const SolverDev& sv, 
   if (sv.slot_xy) {   // (one intrinsics block: recomputed like the rest)
     const size_t lds = (size_t)4 * 64 * 9 * sizeof(double);   // (nine of the 27 components at a time: point_sweep)
     const int sp = sweep_points(dp.M), grid = (int)((dp.M + 4 * sp - 1) / (4 * sp));
-    if (sv.CD == 12) hipLaunchKernelGGL(virtual_records_rc_kernel<2>, dim3(grid), dim3(256), lds, st, dp, sv, sp);
-    else hipLaunchKernelGGL(virtual_records_rc_kernel<1>, dim3(grid), dim3(256), lds, st, dp, sv, sp);
+    by_loss(dp, [&](auto gen) {
+      constexpr bool GEN = decltype(gen)::value;
+      if (sv.CD == 12) hipLaunchKernelGGL((virtual_records_rc_kernel<2, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp);
+      else hipLaunchKernelGGL((virtual_records_rc_kernel<1, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp);
+    });
     return hipGetLastError();
   }
   if (sv.CD == 12) LAUNCH(virtual_records_kernel<12>, nblocks256(sv.nvgroups), 256, st, dp, sv);
@@ -1867,8 +1885,11 @@ hipError_t launch_back_substitute(const DeviceProblem& dp, const SolverDev& sv, 
     const size_t lds = (size_t)4 * 64 * 5 * sizeof(double);
     const int grid = point_step_blocks(dp, sv);
     const int sp = sweep_points(dp.M);
-    if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((point_step_rc_kernel<true, 2>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_step_rc_kernel<true, 1>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
-    else { if (sv.CD == 12) hipLaunchKernelGGL((point_step_rc_kernel<false, 2>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_step_rc_kernel<false, 1>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+    by_loss(dp, [&](auto gen) {
+      constexpr bool GEN = decltype(gen)::value;
+      if (dp.calibrated) { if (sv.CD == 12) hipLaunchKernelGGL((point_step_rc_kernel<true, 2, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_step_rc_kernel<true, 1, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+      else { if (sv.CD == 12) hipLaunchKernelGGL((point_step_rc_kernel<false, 2, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); else hipLaunchKernelGGL((point_step_rc_kernel<false, 1, GEN>), dim3(grid), dim3(256), lds, st, dp, sv, sp); }
+    });
     return hipGetLastError();
   }
   if (sv.CD == 12) return KC == 12 ? launch_point_step<12, 12>(dp, sv, st) : launch_point_step<12, 21>(dp, sv, st);

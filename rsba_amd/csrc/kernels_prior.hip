@@ -40,7 +40,11 @@ __device__ __forceinline__ void prior_coefficients(const DeviceProblem& dp, doub
 }
 
 // the functors' residuals in their own order of operations (T = double path); loss weight rho' and cost rho / 2
-struct PriorValue { double r[12]; double weight, cost; };
+// GEN (every template parameter of that name here): the instantiation for a general loss (dp.loss_general, lm_record.hpp).  Its corrector
+// may take the rank-one branch (rho'' > 0), J~^T J~ = rho' J^T J + 2 rho'' (J^T r)(J^T r)^T over ALL 25 columns of the block (Triggs): w2 =
+// 2 rho'' where that branch applies, 0 otherwise.  J~^T r~ = rho' J^T r either way: the gradients keep their form.
+struct PriorValue { double r[12]; double weight, cost, w2, s; };
+template <bool GEN>
 __device__ __forceinline__ PriorValue prior_value(const DeviceProblem& dp, int f) {
   PriorValue v;
   const double* cur = dp.poses + (size_t)f * 12; const double* prev = cur - 12;
@@ -66,7 +70,10 @@ __device__ __forceinline__ PriorValue prior_value(const DeviceProblem& dp, int f
 #pragma unroll
   for (int i = 0; i < 12; ++i) s += v.r[i] * v.r[i];
   double rho[3] = {s, 1.0, 0.0};
-  if (dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
+  if constexpr (GEN) {
+    general_rho(dp.loss_type, dp.loss_a, dp.loss_b, dp.loss_c, dp.loss_scale, s, rho);
+    v.w2 = (s == 0.0 || rho[2] <= 0.0) ? 0.0 : 2.0 * rho[2]; v.s = s;
+  } else if (dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
   v.weight = rho[1]; v.cost = 0.5 * rho[0];
   return v;
 }
@@ -86,7 +93,18 @@ __device__ __forceinline__ void prior_ratio_column(const DeviceProblem& dp, int 
   }
 }
 
+// w = J^T r of a block over the poses of its own frame (back = 0: columns f.p0 | f.p1) or of the frame before (back = 2), no column scales
+__device__ __forceinline__ void prior_jtr(const DeviceProblem& dp, const double Ca[4], const double Cb[4], const PriorValue& v, int back, double w[12]) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) w[6 * p + i] = si * (Ca[back + p] * v.r[i] + Cb[back + p] * v.r[6 + i]);
+  }
+}
+
 // U_f, g_f and the (f, f-1) cross block: one thread per frame
+template <bool GEN>
 __global__ __launch_bounds__(64) void prior_blocks_kernel(const DeviceProblem dp, const SolverDev sv, double* __restrict__ ucross) {
   if (lm_not_accepted(sv.ctl)) return;   // (device-side trust region: a rejected candidate is not linearised)
   const int f = blockIdx.x * 64 + threadIdx.x;
@@ -96,10 +114,13 @@ __global__ __launch_bounds__(64) void prior_blocks_kernel(const DeviceProblem dp
   double Ca[4], Cb[4];
   prior_coefficients(dp, Ca, Cb);
   PriorValue mine, next;
-  if (heads) mine = prior_value(dp, f);
-  if (referred) next = prior_value(dp, f + 1);
+  if (heads) mine = prior_value<GEN>(dp, f);
+  if (referred) next = prior_value<GEN>(dp, f + 1);
   const double* sc = dp.scale_pose + (size_t)f * 12;
   double* U = sv.U + (size_t)f * 144; double* g = sv.gc + (size_t)f * 12;
+  if constexpr (GEN) {   // the cross block is dense with the rank-one term, and zero where a block took the plain branch: all of it is written
+    if (heads) for (int k = 0; k < 144; ++k) ucross[(size_t)f * 144 + k] = 0.0;
+  }
   for (int i = 0; i < 6; ++i) {
     const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0), s2 = si * si;
     double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, gv[2] = {0.0, 0.0};
@@ -126,6 +147,22 @@ __global__ __launch_bounds__(64) void prior_blocks_kernel(const DeviceProblem dp
       }
     }
   }
+  if constexpr (GEN) {
+    if (heads && mine.w2 != 0.0) {
+      double wc[12], wp[12];
+      prior_jtr(dp, Ca, Cb, mine, 0, wc); prior_jtr(dp, Ca, Cb, mine, 2, wp);
+      const double* scp = sc - 12;
+      for (int a = 0; a < 12; ++a) for (int b = 0; b < 12; ++b) {
+        U[a * 12 + b] += mine.w2 * (wc[a] * sc[a]) * (wc[b] * sc[b]);
+        ucross[(size_t)f * 144 + a * 12 + b] += mine.w2 * (wc[a] * sc[a]) * (wp[b] * scp[b]);
+      }
+    }
+    if (referred && next.w2 != 0.0) {
+      double wp[12];
+      prior_jtr(dp, Ca, Cb, next, 2, wp);
+      for (int a = 0; a < 12; ++a) for (int b = 0; b < 12; ++b) U[a * 12 + b] += next.w2 * (wp[a] * sc[a]) * (wp[b] * sc[b]);
+    }
+  }
 }
 
 // The two reductions below run one wave per 64 frames across the chip.  Every wave leaves its partial in
@@ -143,12 +180,13 @@ __device__ __forceinline__ bool last_wave_of_grid(const DeviceProblem& dp) {
 
 // cost of the prior blocks at dp.poses, added to {cost, fixed cost}; a block whose four poses are all constant (and whose
 // ratio block is constant too) is not part of the reduced program and its cost is "fixed" (Ceres: Program::RemoveFixedBlocks)
+template <bool GEN>
 __global__ __launch_bounds__(64) void prior_cost_kernel(const DeviceProblem dp, double* cost2, int invalid) {
   if (lm_stopped(dp.ctl)) return;        // (device-side trust region: iterations behind a termination fall through — every wave alike: the ticket stays armed)
   const int f = blockIdx.x * 64 + threadIdx.x;
   double c = 0.0, cf = 0.0;
   if (f < dp.F && dp.prior_of[f]) {
-    const PriorValue v = prior_value(dp, f);
+    const PriorValue v = prior_value<GEN>(dp, f);
     bool all_const = dp.prior_free == 0;   // with a free ratio the block always keeps one variable parameter block
     for (int k = 0; k < 24; ++k) all_const = all_const && dp.scale_pose[(size_t)(f - 1) * 12 + k] == 0.0;
     if (all_const) cf = v.cost; else c = v.cost;
@@ -165,6 +203,7 @@ __global__ __launch_bounds__(64) void prior_cost_kernel(const DeviceProblem dp, 
 }
 
 // model cost change of the prior blocks for the camera step in sv.step:  -sum m.(r~ + m/2),  m = -J~ y
+template <bool GEN>
 __global__ __launch_bounds__(64) void prior_model_kernel(const DeviceProblem dp, const SolverDev sv, double* out, double ratio_step, const double* ratio_step_ptr) {
   if (lm_stopped(dp.ctl)) return;
   if (ratio_step_ptr) { const double c = *ratio_step_ptr; ratio_step = isfinite(c) ? c : 0.0; }   // (device-side trust region: the ETA task of the factorisation left s eta there)
@@ -173,19 +212,38 @@ __global__ __launch_bounds__(64) void prior_model_kernel(const DeviceProblem dp,
   if (f < dp.F && dp.prior_of[f]) {
     double Ca[4], Cb[4];
     prior_coefficients(dp, Ca, Cb);
-    const PriorValue v = prior_value(dp, f);
+    const PriorValue v = prior_value<GEN>(dp, f);
     const double sw = sqrt(v.weight);
     const double* y = sv.step + (size_t)(f - 1) * 12; const double* sc = dp.scale_pose + (size_t)(f - 1) * 12;   // [prev | cur]
     double dr[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) dr[i] = 0.0;
     if (ratio_step != 0.0) prior_ratio_column(dp, f, dr);            // free ratio: its (scaled) step enters m = -J~ y too
-    for (int i = 0; i < 6; ++i) {
-      const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0);
-      const double x0 = sc[12 + i] * y[12 + i], x1 = sc[18 + i] * y[18 + i], x2 = sc[i] * y[i], x3 = sc[6 + i] * y[6 + i];
-      const double ma = -sw * (si * (Ca[0] * x0 + Ca[1] * x1 + Ca[2] * x2 + Ca[3] * x3) + dr[i] * ratio_step);
-      const double mb = -sw * (si * (Cb[0] * x0 + Cb[1] * x1 + Cb[2] * x2 + Cb[3] * x3) + dr[6 + i] * ratio_step);
-      acc += ma * (sw * v.r[i] + 0.5 * ma) + mb * (sw * v.r[6 + i] + 0.5 * mb);
+    if constexpr (GEN) {
+      // the whole corrector: t = J y, m = -sqrt(rho') (t - (alpha / s) r (r . t)), r~ = sqrt(rho') / (1 - alpha) r
+      const bool plain = v.w2 == 0.0;
+      const double alpha = plain ? 0.0 : 1.0 - sqrt(1.0 + v.s * v.w2 / v.weight);
+      const double as = plain ? 0.0 : alpha / v.s, rs = plain ? sw : sw / (1.0 - alpha);
+      double t[12], rt = 0.0;
+      for (int i = 0; i < 6; ++i) {
+        const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0);
+        const double x0 = sc[12 + i] * y[12 + i], x1 = sc[18 + i] * y[18 + i], x2 = sc[i] * y[i], x3 = sc[6 + i] * y[6 + i];
+        t[i] = si * (Ca[0] * x0 + Ca[1] * x1 + Ca[2] * x2 + Ca[3] * x3) + dr[i] * ratio_step;
+        t[6 + i] = si * (Cb[0] * x0 + Cb[1] * x1 + Cb[2] * x2 + Cb[3] * x3) + dr[6 + i] * ratio_step;
+        rt += v.r[i] * t[i] + v.r[6 + i] * t[6 + i];
+      }
+      for (int i = 0; i < 12; ++i) {
+        const double m = -sw * (t[i] - as * rt * v.r[i]);
+        acc += m * (rs * v.r[i] + 0.5 * m);
+      }
+    } else {
+      for (int i = 0; i < 6; ++i) {
+        const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0);
+        const double x0 = sc[12 + i] * y[12 + i], x1 = sc[18 + i] * y[18 + i], x2 = sc[i] * y[i], x3 = sc[6 + i] * y[6 + i];
+        const double ma = -sw * (si * (Ca[0] * x0 + Ca[1] * x1 + Ca[2] * x2 + Ca[3] * x3) + dr[i] * ratio_step);
+        const double mb = -sw * (si * (Cb[0] * x0 + Cb[1] * x1 + Cb[2] * x2 + Cb[3] * x3) + dr[6 + i] * ratio_step);
+        acc += ma * (sw * v.r[i] + 0.5 * ma) + mb * (sw * v.r[6 + i] + 0.5 * mb);
+      }
     }
   }
   acc = wsum64(acc);
@@ -200,6 +258,7 @@ __global__ __launch_bounds__(64) void prior_model_kernel(const DeviceProblem dp,
 // Free interFrameRatio: the column of the ratio in the normal equations.  border[t] = (J~_x^T J~_ratio) of camera
 // coordinate t (camera scales applied, the ratio's own scale is the host's), hg = {J~_ratio^T J~_ratio, J~_ratio^T r~}.
 // One thread per frame gathers the prior it heads and the one referring back to it; hg by the last-wave reduction.
+template <bool GEN>
 __global__ __launch_bounds__(64) void prior_border_kernel(const DeviceProblem dp, const SolverDev sv, double* __restrict__ border, double* __restrict__ hg) {
   if (lm_not_accepted(sv.ctl)) return;   // (device-side trust region: a rejected candidate is not linearised — every wave alike: the ticket stays armed)
   const int f = blockIdx.x * 64 + threadIdx.x;
@@ -212,7 +271,7 @@ __global__ __launch_bounds__(64) void prior_border_kernel(const DeviceProblem dp
 #pragma unroll
     for (int a = 0; a < 12; ++a) out[a] = 0.0;
     if (heads) {
-      const PriorValue v = prior_value(dp, f);
+      const PriorValue v = prior_value<GEN>(dp, f);
       double dr[12];
       prior_ratio_column(dp, f, dr);
       for (int i = 0; i < 6; ++i) {
@@ -221,14 +280,31 @@ __global__ __launch_bounds__(64) void prior_border_kernel(const DeviceProblem dp
         hh += v.weight * (dr[i] * dr[i] + dr[6 + i] * dr[6 + i]);
         gg += v.weight * (dr[i] * v.r[i] + dr[6 + i] * v.r[6 + i]);
       }
+      if constexpr (GEN) {
+        if (v.w2 != 0.0) {   // the rank-one term against the ratio's entry of J^T r
+          double w[12], wr = 0.0;
+          prior_jtr(dp, Ca, Cb, v, 0, w);
+          for (int i = 0; i < 12; ++i) wr += dr[i] * v.r[i];
+          for (int a = 0; a < 12; ++a) out[a] += v.w2 * w[a] * wr;
+          hh += v.w2 * wr * wr;
+        }
+      }
     }
     if (referred) {
-      const PriorValue v = prior_value(dp, f + 1);
+      const PriorValue v = prior_value<GEN>(dp, f + 1);
       double dr[12];
       prior_ratio_column(dp, f + 1, dr);
       for (int i = 0; i < 6; ++i) {
         const double si = dp.prior_scale * (i < 3 ? 0.01 : 1.0);
         for (int p = 0; p < 2; ++p) out[6 * p + i] += v.weight * si * (Ca[2 + p] * dr[i] + Cb[2 + p] * dr[6 + i]);
+      }
+      if constexpr (GEN) {
+        if (v.w2 != 0.0) {
+          double w[12], wr = 0.0;
+          prior_jtr(dp, Ca, Cb, v, 2, w);
+          for (int i = 0; i < 12; ++i) wr += dr[i] * v.r[i];
+          for (int a = 0; a < 12; ++a) out[a] += v.w2 * w[a] * wr;
+        }
       }
     }
     const double* sc = dp.scale_pose + (size_t)f * 12;
@@ -292,7 +368,8 @@ __global__ void ratio_candidate_kernel(double* rt, const double* ctl) {
 }  // namespace
 
 hipError_t launch_prior_border(const DeviceProblem& dp, const SolverDev& sv, double* border, double* hg, hipStream_t st) {
-  hipLaunchKernelGGL(prior_border_kernel, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, border, hg);
+  if (dp.loss_general) hipLaunchKernelGGL(prior_border_kernel<true>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, border, hg);
+  else hipLaunchKernelGGL(prior_border_kernel<false>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, border, hg);
   return hipGetLastError();
 }
 hipError_t launch_border_dots(const double* b, const double* u, const double* v, int64_t n, double* out2, hipStream_t st) {
@@ -321,15 +398,18 @@ hipError_t launch_ratio_candidate(double* rt, const double* ctl, hipStream_t st)
 }
 
 hipError_t launch_prior_blocks(const DeviceProblem& dp, const SolverDev& sv, double* ucross, hipStream_t st) {
-  hipLaunchKernelGGL(prior_blocks_kernel, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, ucross);
+  if (dp.loss_general) hipLaunchKernelGGL(prior_blocks_kernel<true>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, ucross);
+  else hipLaunchKernelGGL(prior_blocks_kernel<false>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, ucross);
   return hipGetLastError();
 }
 hipError_t launch_prior_cost(const DeviceProblem& dp, double* cost2, int invalid_blocks, hipStream_t st) {
-  hipLaunchKernelGGL(prior_cost_kernel, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, cost2, invalid_blocks);
+  if (dp.loss_general) hipLaunchKernelGGL(prior_cost_kernel<true>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, cost2, invalid_blocks);
+  else hipLaunchKernelGGL(prior_cost_kernel<false>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, cost2, invalid_blocks);
   return hipGetLastError();
 }
 hipError_t launch_prior_model(const DeviceProblem& dp, const SolverDev& sv, double* model_cost_change, double ratio_step, hipStream_t st, const double* ratio_step_ptr) {
-  hipLaunchKernelGGL(prior_model_kernel, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, model_cost_change, ratio_step, ratio_step_ptr);
+  if (dp.loss_general) hipLaunchKernelGGL(prior_model_kernel<true>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, model_cost_change, ratio_step, ratio_step_ptr);
+  else hipLaunchKernelGGL(prior_model_kernel<false>, dim3((dp.F + 63) / 64), dim3(64), 0, st, dp, sv, model_cost_change, ratio_step, ratio_step_ptr);
   return hipGetLastError();
 }
 

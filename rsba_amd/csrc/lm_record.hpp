@@ -16,7 +16,9 @@ namespace rsba {
 // pose / pose_scale: the frame's CD = 6 P doubles (any address space the caller staged them in).
 // Out: o.r, o.J scaled by sqrt(rho') and the column scales, zeros when the functor failed; half_rho = rho0 / 2 of the block
 // (0 when it failed), dropped = every parameter block of it is constant (its cost is the fixed cost then).
-template <bool CAL, int P>
+// GEN: the problem's loss is any of the set (dp.loss_type, possibly scaled) and the whole corrector applies, its rank-one term included
+// (rho'' > 0: TolerantLoss).  GEN = false is the code for no loss and Huber at scale 1, untouched: one more live value here costs occupancy.
+template <bool CAL, int P, bool GEN = false>
 __device__ __forceinline__ void lm_observation(const DeviceProblem& dp, int f, int j, double x, double y, const double* __restrict__ pose,
                                                const double* __restrict__ pose_scale, ObsOut<CAL, P>& o, double& half_rho, bool& dropped) {
   constexpr int CD = 6 * P;
@@ -34,7 +36,7 @@ __device__ __forceinline__ void lm_observation(const DeviceProblem& dp, int f, i
   // Ceres 1.9 ResidualBlock::Evaluate: cost = rho0/2 from the uncorrected residual
   const double s = o.r[0] * o.r[0] + o.r[1] * o.r[1];
   double rho[3] = {s, 1.0, 0.0};
-  if (dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
+  if (!GEN && dp.huber_a > 0.0) huber_rho(dp.huber_a, s, rho);
   half_rho = o.ok ? 0.5 * rho[0] : 0.0;
   double sc[K];
   if (!CAL) {
@@ -50,15 +52,40 @@ __device__ __forceinline__ void lm_observation(const DeviceProblem& dp, int f, i
   dropped = true;
 #pragma unroll
   for (int k = 0; k < K; ++k) dropped = dropped && (sc[k] == 0.0);
-  // Corrector (Ceres 1.9 corrector.cc) for rho'' <= 0, which always holds for Huber: residual
-  // and Jacobian rows are scaled by sqrt(rho').
-  const double sr1 = dp.huber_a > 0.0 ? sqrt(rho[1]) : 1.0;   // (without a loss rho' is exactly 1: the same bits, and no fp64 square root — thirty instructions — per observation)
-  o.r[0] *= sr1; o.r[1] *= sr1;
+  if constexpr (GEN) {
+    // Corrector (Ceres 1.9 corrector.cc), all of it: with s > 0 and rho'' > 0, D = 1 + 2 s rho'' / rho', alpha = 1 - sqrt(D),
+    // r~ = sqrt(rho') / (1 - alpha) r, J~ = sqrt(rho') (J - (alpha / s) r (r^T J)); otherwise rows scaled by sqrt(rho').
+    general_rho(dp.loss_type, dp.loss_a, dp.loss_b, dp.loss_c, dp.loss_scale, s, rho);
+    half_rho = o.ok ? 0.5 * rho[0] : 0.0;
+    const double sr1 = sqrt(rho[1]);
+    const bool plain = (s == 0.0) || (rho[2] <= 0.0);
+    const double alpha = plain ? 0.0 : 1.0 - sqrt(1.0 + 2.0 * s * rho[2] / rho[1]);
+    const double as = plain ? 0.0 : alpha / s, rs = plain ? sr1 : sr1 / (1.0 - alpha);
+    const double r0 = o.r[0], r1 = o.r[1];
 #pragma unroll
-  for (int k = 0; k < K; ++k) { const double c = sr1 * sc[k]; o.J[0][k] *= c; o.J[1][k] *= c; }
-  if (P == 2) {   // the unscaled pose block gets the loss correction only: its column scales are applied where the Schur partials are merged
+    for (int k = 0; k < K; ++k) {
+      const double c = sr1 * sc[k], t = as * (r0 * o.J[0][k] + r1 * o.J[1][k]);
+      o.J[0][k] = (o.J[0][k] - r0 * t) * c; o.J[1][k] = (o.J[1][k] - r1 * t) * c;
+    }
+    if (P == 2) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) { o.Jq[0][k] *= sr1; o.Jq[1][k] *= sr1; }
+      for (int k = 0; k < 6; ++k) {
+        const double t = as * (r0 * o.Jq[0][k] + r1 * o.Jq[1][k]);
+        o.Jq[0][k] = (o.Jq[0][k] - r0 * t) * sr1; o.Jq[1][k] = (o.Jq[1][k] - r1 * t) * sr1;
+      }
+    }
+    o.r[0] = r0 * rs; o.r[1] = r1 * rs;
+  } else {
+    // Corrector (Ceres 1.9 corrector.cc) for rho'' <= 0, which always holds for Huber: residual
+    // and Jacobian rows are scaled by sqrt(rho').
+    const double sr1 = dp.huber_a > 0.0 ? sqrt(rho[1]) : 1.0;   // (without a loss rho' is exactly 1: the same bits, and no fp64 square root — thirty instructions — per observation)
+    o.r[0] *= sr1; o.r[1] *= sr1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { const double c = sr1 * sc[k]; o.J[0][k] *= c; o.J[1][k] *= c; }
+    if (P == 2) {   // the unscaled pose block gets the loss correction only: its column scales are applied where the Schur partials are merged
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { o.Jq[0][k] *= sr1; o.Jq[1][k] *= sr1; }
+    }
   }
   // a failed block contributes zeros everywhere (record, camera blocks)
   if (!o.ok) {

@@ -206,4 +206,56 @@ __device__ __forceinline__ void huber_rho(double a, double s, double rho[3]) {
   } else { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }
 }
 
+// The other losses of Ceres-Solver 1.9.0 loss_function.cc (third-party; the rule as this library states it: include/rsba_amd.h, rsba_loss),
+// in its forms and order of operations.  b, c: the constants the constructors precompute (rsba_set_loss computes them on the host).
+constexpr double kLossMin = 2.2250738585072014e-308;   // std::numeric_limits<double>::min()
+// SoftLOneLoss(a): b = a^2, c = 1 / b
+__device__ __forceinline__ void soft_l_one_rho(double b, double c, double s, double rho[3]) {
+  const double sum = 1.0 + s * c;
+  const double tmp = sqrt(sum);
+  rho[0] = 2.0 * b * (tmp - 1.0);
+  rho[1] = fmax(kLossMin, 1.0 / tmp);
+  rho[2] = -(c * rho[1]) / (2.0 * sum);
+}
+// CauchyLoss(a): b = a^2, c = 1 / b
+__device__ __forceinline__ void cauchy_rho(double b, double c, double s, double rho[3]) {
+  const double sum = 1.0 + s * c;
+  const double inv = 1.0 / sum;
+  rho[0] = b * log(sum);
+  rho[1] = fmax(kLossMin, inv);
+  rho[2] = -c * (inv * inv);
+}
+// ArctanLoss(a): b = 1 / a^2
+__device__ __forceinline__ void arctan_rho(double a, double b, double s, double rho[3]) {
+  const double sum = 1.0 + s * s * b;
+  const double inv = 1.0 / sum;
+  rho[0] = a * atan2(s, a);
+  rho[1] = fmax(kLossMin, inv);
+  rho[2] = -2.0 * s * b * (inv * inv);
+}
+// TolerantLoss(a, b): c = b log(1 + exp(-a / b)); beyond x = 36.7 (2^53 ~ e^36.7) the loss is s - a - c to the last bit
+__device__ __forceinline__ void tolerant_rho(double a, double b, double c, double s, double rho[3]) {
+  const double x = (s - a) / b;
+  if (x > 36.7) { rho[0] = s - a - c; rho[1] = 1.0; rho[2] = 0.0; }
+  else {
+    const double e_x = exp(x);
+    rho[0] = b * log(1.0 + e_x) - c;
+    rho[1] = fmax(kLossMin, e_x / (1.0 + e_x));
+    rho[2] = 0.5 / (b * (1.0 + cosh(x)));
+  }
+}
+enum LossType : int { kLossTrivial = 0, kLossHuber = 1, kLossSoftLOne = 2, kLossCauchy = 3, kLossArctan = 4, kLossTolerant = 5 };   // RSBA_LOSS_*
+// any loss of the set, times ScaledLoss' factor: what the GENERAL instantiations of the kernels evaluate (lm_record.hpp)
+__device__ __forceinline__ void general_rho(int type, double a, double b, double c, double scale, double s, double rho[3]) {
+  switch (type) {
+    case kLossHuber: huber_rho(a, s, rho); break;
+    case kLossSoftLOne: soft_l_one_rho(b, c, s, rho); break;
+    case kLossCauchy: cauchy_rho(b, c, s, rho); break;
+    case kLossArctan: arctan_rho(a, b, s, rho); break;
+    case kLossTolerant: tolerant_rho(a, b, c, s, rho); break;
+    default: rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; break;
+  }
+  rho[0] *= scale; rho[1] *= scale; rho[2] *= scale;
+}
+
 }  // namespace rsba

@@ -135,6 +135,7 @@ struct Solver {
   double* border = nullptr, *ratio4 = nullptr;                       // free interFrameRatio: its column of S [npad]; its scalars on the device (solver_state.hpp: RatioSlot)
   PosePriorDev pp{};                                                  // per-pose priors: linearisation of the priorPoses coordinates
   double* merge_buf = nullptr;                                        // sharded solve: [4 M] owned point values | owner flags
+  size_t ucross_len = 0;                                              // its doubles (rsba_solver_loss_changed clears them)
   double* ucross = nullptr;                                           // [F][CD][CD] motion-prior blocks (f, f-1), behind sv.U's J^T J blocks
   // iterative reduced solve (rsba_set_linear_solver type 1; pcg.hpp): lists and vectors, made by the first solve that asks for them
   bool pcg_on = false; bool pcg_ready = false; PcgHostPlan pcg_hp; PcgDev pcg{};
@@ -1122,7 +1123,7 @@ int32_t build_solver_impl(rsba_handle* h) {
   }
   const size_t ucross_len = h->prior_frames.empty() ? 0 : (size_t)FR * CD * CD;
   if ((rc = s_alloc(s, &sv.U, (size_t)ucross_base + ucross_len))) return rc;
-  if (ucross_len) { s->ucross = sv.U + ucross_base; HIP_TRY(hipMemset(s->ucross, 0, ucross_len * sizeof(double))); }   // stays zero on the other ranks
+  if (ucross_len) { s->ucross = sv.U + ucross_base; s->ucross_len = ucross_len; HIP_TRY(hipMemset(s->ucross, 0, ucross_len * sizeof(double))); }   // stays zero on the other ranks
   if (ucross_len && h->prior_free) {   // the ratio is one more camera-side unknown: a 1-wide dense border of S, handled by a second solve
     if ((rc = s_alloc(s, &s->border, (size_t)sv.npad))) return rc;
     if ((rc = s_alloc(s, &s->ratio4, kRtSize))) return rc;
@@ -1637,6 +1638,15 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 void rsba_release_plan_scratch() {
   std::lock_guard<std::mutex> lk(g_plan_scratch_mutex);
   g_plan_scratch.reset();
+}
+
+// rsba_set_loss: the (f, f-1) blocks of the motion priors are dense under a general loss and 2 x 2 per coordinate otherwise — the kernel
+// of the second kind writes its own entries only, so what the first kind left elsewhere goes here
+int32_t rsba_solver_loss_changed(rsba_handle* h) {
+  if (!h || !h->solver || !h->solver->ucross) return RSBA_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemsetAsync(h->solver->ucross, 0, h->solver->ucross_len * sizeof(double), h->stream));
+  return RSBA_OK;
 }
 
 void rsba_destroy_solver(rsba_handle* h) {
