@@ -741,11 +741,16 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
   }
 }
 
-// ceres::Covariance for pose blocks (the use rsba makes of it, VideoSfMHandler.cc:602-621): Compute() takes pairs of
-// pose blocks of the problem, GetCovarianceBlock() returns the row-major 6 x 6 block between two poses of ONE
-// frame.  Each frame asked for costs one call of rsba_pose_covariance (CD solves through the device factorisation).
-// Compute() returns false — like Ceres — when J^T J is rank deficient, and for blocks outside the accelerated
-// path (points, intrinsics, poses of two different frames).
+// ceres::Covariance.  Compute() takes pairs of parameter blocks of the problem, GetCovarianceBlock() returns the row-major block
+// between the two.  Two paths:
+//   * a request of pose pairs of ONE frame each (the use rsba makes of it, VideoSfMHandler.cc:602-621) costs one call of
+//     rsba_pose_covariance per frame asked for (CD solves through the device factorisation), as it always has;
+//   * any other request goes through ONE rsba_covariance_compute (the selected inverse of the reduced camera system on the tile
+//     pattern of its factor) and its getters: (pose, pose) of any two frames whose tiles share a tile of the factor — co-visible
+//     frames, frames linked by a prior —, (point, point) of ONE point and (intrinsics, intrinsics) of one block.
+// Compute() returns false — like Ceres — when J^T J is rank deficient, and for what neither path serves: a pose against a point, two
+// different points, intrinsics with anything but itself, scalar and priorPoses blocks, pose pairs off the pattern.
+// GetCovarianceBlock(b, a) after a request for (a, b) returns the transpose, as Ceres does.
 class Covariance {
  public:
   struct Options { int device = 0; };
@@ -753,39 +758,90 @@ class Covariance {
   explicit Covariance(const Options& o) : options_(o) {}
 
   bool Compute(const std::vector<std::pair<const double*, const double*>>& blocks, Problem* problem) {
-    ready_.clear();
+    ready_.clear(); pair_.clear(); intr_.clear(); point_.clear(); index_.clear(); intr_index_.clear(); point_index_.clear();
     Problem::Flat f;
     if (!problem->flatten(&f, nullptr)) return false;
     const int P = f.desc.poses_per_frame, CD = 6 * P;
-    std::set<int> frames;
+    poses_per_frame_ = P;
+    std::set<int> frames, intr, points;
+    std::set<std::pair<int, int>> frame_pairs;
+    bool one_frame_each = true;
     for (const auto& b : blocks) {
       auto i0 = f.slot_of.find(const_cast<double*>(b.first)), i1 = f.slot_of.find(const_cast<double*>(b.second));
-      if (i0 == f.slot_of.end() || i1 == f.slot_of.end() || i0->second.kind != 0 || i1->second.kind != 0) return false;
-      if (i0->second.index / P != i1->second.index / P) return false;
-      frames.insert(i0->second.index / P);
+      if (i0 == f.slot_of.end() || i1 == f.slot_of.end() || i0->second.kind != i1->second.kind) return false;
+      if (i0->second.kind == 0) {
+        const int fa = i0->second.index / P, fb = i1->second.index / P;
+        one_frame_each = one_frame_each && fa == fb;
+        frames.insert(fa); frames.insert(fb); frame_pairs.insert(std::make_pair(fa, fb));
+      } else if (i0->second.kind == 2 && i0->second.index == i1->second.index) {
+        one_frame_each = false;
+        intr.insert(i0->second.index); intr_index_[b.first] = i0->second.index;
+      } else if (i0->second.kind == 1 && i0->second.index == i1->second.index) {
+        one_frame_each = false;
+        points.insert(i0->second.index); point_index_[b.first] = i0->second.index;
+      } else return false;
     }
     rsba_handle* h = nullptr;
     if (Problem::create_handle(f, options_.device, &h) != RSBA_OK) return false;
     bool ok = true;
-    for (int fr : frames) {
-      std::vector<double> cov((size_t)CD * CD);
-      if (rsba_pose_covariance(h, fr, cov.data()) != RSBA_OK) { ok = false; break; }
-      for (int q = 0; q < P; ++q) if (f.pose_ptr[(size_t)fr * P + q]) index_[f.pose_ptr[(size_t)fr * P + q]] = std::make_pair(fr, q);
-      ready_[fr] = std::move(cov);
+    for (int fr : frames) for (int q = 0; q < P; ++q) if (f.pose_ptr[(size_t)fr * P + q]) index_[f.pose_ptr[(size_t)fr * P + q]] = std::make_pair(fr, q);
+    if (one_frame_each) {
+      for (int fr : frames) {
+        std::vector<double> cov((size_t)CD * CD);
+        if (rsba_pose_covariance(h, fr, cov.data()) != RSBA_OK) { ok = false; break; }
+        ready_[fr] = std::move(cov);
+      }
+    } else {
+      ok = rsba_covariance_compute(h) == RSBA_OK;
+      std::vector<int32_t> fa, fb;
+      for (const auto& pr : frame_pairs) { fa.push_back(pr.first); fb.push_back(pr.second); }
+      std::vector<double> cov(fa.size() * (size_t)CD * CD);
+      ok = ok && rsba_covariance_frame_blocks(h, fa.data(), fb.data(), (int64_t)fa.size(), cov.data()) == RSBA_OK;
+      for (size_t k = 0; ok && k < fa.size(); ++k) pair_[std::make_pair((int)fa[k], (int)fb[k])].assign(cov.begin() + k * (size_t)CD * CD, cov.begin() + (k + 1) * (size_t)CD * CD);
+      for (int c : intr) {
+        std::vector<double> blk(81);
+        ok = ok && rsba_covariance_intrinsics_block(h, c, blk.data()) == RSBA_OK;
+        intr_[c] = std::move(blk);
+      }
+      if (ok && !points.empty()) {
+        const std::vector<int32_t> pts(points.begin(), points.end());
+        std::vector<double> blk(pts.size() * 9);
+        ok = rsba_covariance_point_blocks(h, pts.data(), (int64_t)pts.size(), blk.data()) == RSBA_OK;
+        for (size_t k = 0; ok && k < pts.size(); ++k) point_[pts[k]].assign(blk.begin() + 9 * k, blk.begin() + 9 * (k + 1));
+      }
     }
     rsba_destroy(h);
-    poses_per_frame_ = P;
-    if (!ok) ready_.clear();
+    if (!ok) { ready_.clear(); pair_.clear(); intr_.clear(); point_.clear(); }
     return ok;
   }
 
   bool GetCovarianceBlock(const double* p0, const double* p1, double* out) const {
+    auto c0 = intr_index_.find(p0), c1 = intr_index_.find(p1);
+    if (c0 != intr_index_.end() || c1 != intr_index_.end()) {
+      if (c0 == intr_index_.end() || c1 == intr_index_.end() || c0->second != c1->second) return false;
+      auto it = intr_.find(c0->second);
+      if (it == intr_.end()) return false;
+      std::copy(it->second.begin(), it->second.end(), out);
+      return true;
+    }
+    auto q0 = point_index_.find(p0), q1 = point_index_.find(p1);
+    if (q0 != point_index_.end() || q1 != point_index_.end()) {
+      if (q0 == point_index_.end() || q1 == point_index_.end() || q0->second != q1->second) return false;
+      auto it = point_.find(q0->second);
+      if (it == point_.end()) return false;
+      std::copy(it->second.begin(), it->second.end(), out);
+      return true;
+    }
     auto i0 = index_.find(p0), i1 = index_.find(p1);
-    if (i0 == index_.end() || i1 == index_.end() || i0->second.first != i1->second.first) return false;
-    auto it = ready_.find(i0->second.first);
-    if (it == ready_.end()) return false;
-    const int CD = 6 * poses_per_frame_, r0 = 6 * i0->second.second, c0 = 6 * i1->second.second;
-    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) out[a * 6 + b] = it->second[(size_t)(r0 + a) * CD + c0 + b];
+    if (i0 == index_.end() || i1 == index_.end()) return false;
+    const std::vector<double>* blk = nullptr;
+    bool transposed = false;
+    if (i0->second.first == i1->second.first) { auto it = ready_.find(i0->second.first); if (it != ready_.end()) blk = &it->second; }
+    if (!blk) { auto it = pair_.find(std::make_pair(i0->second.first, i1->second.first)); if (it != pair_.end()) blk = &it->second; }
+    if (!blk) { auto it = pair_.find(std::make_pair(i1->second.first, i0->second.first)); if (it != pair_.end()) { blk = &it->second; transposed = true; } }
+    if (!blk) return false;
+    const int CD = 6 * poses_per_frame_, r0 = 6 * i0->second.second, c0p = 6 * i1->second.second;
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) out[a * 6 + b] = transposed ? (*blk)[(size_t)(c0p + b) * CD + r0 + a] : (*blk)[(size_t)(r0 + a) * CD + c0p + b];
     return true;
   }
 
@@ -793,7 +849,12 @@ class Covariance {
   Options options_;
   int poses_per_frame_ = 1;
   std::map<const double*, std::pair<int, int>> index_;   // pose block -> (frame, pose within the frame)
-  std::map<int, std::vector<double>> ready_;             // frame -> [CD][CD]
+  std::map<const double*, int> intr_index_;              // intrinsics block -> its index
+  std::map<int, std::vector<double>> ready_;             // frame -> [CD][CD] (rsba_pose_covariance)
+  std::map<std::pair<int, int>, std::vector<double>> pair_;   // (frame a, frame b) -> [CD][CD] (rsba_covariance_frame_blocks)
+  std::map<int, std::vector<double>> intr_;              // intrinsics block -> [9][9]
+  std::map<const double*, int> point_index_;             // point block -> its index
+  std::map<int, std::vector<double>> point_;             // point -> [3][3] (rsba_covariance_point_blocks)
 };
 
 }  // namespace ceres

@@ -384,6 +384,38 @@ int32_t rsba_match_last_kernel_ms(float* ms);
  * zero rows / columns at fixed coordinates.  RSBA_ERR_UNSUPPORTED when J^T J is rank deficient (Compute returns false). */
 int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* cov);
 
+/* == the covariance of EVERY frame at once — and of pairs of frames, and of the intrinsics blocks — where rsba_pose_covariance
+ * returns one (frame, frame) block for CD solves through the factorisation.  rsba_covariance_compute linearises and factors exactly
+ * as rsba_pose_covariance does (same refusals: RSBA_ERR_UNSUPPORTED when J^T J is rank deficient, RSBA_ERR_EVALUATION_FAILED), then
+ * forms Sigma = S^-1 of the reduced camera system on the tile pattern of its Cholesky factor (48 x 48 tiles, after fill) by the
+ * Takahashi recurrence — about one more factorisation's worth of tile products — and keeps it on the device: two arrays of the
+ * factor's size, allocated by the first compute and given back by rsba_covariance_release or rsba_destroy.  A block of Sigma is the
+ * same block of (J^T J)^-1 (points, priorPoses blocks eliminated; the column of a free interFrameRatio added as the bordered inverse).
+ * One rank only: a handle with an exchange attached (rsba_set_exchange) is refused with RSBA_ERR_UNSUPPORTED.
+ *   rsba_covariance_frame_blocks: cov [n][CD][CD] row-major, block p = the (frame_a[p], frame_b[p]) block; (a, b) with a > b is the
+ *     transpose of (b, a) bit for bit; zero rows / columns at fixed coordinates, at the data slot of a one-pose frame and at
+ *     coordinates no residual touches.  Every (f, f) is available, and (f, g) where the two frames' tiles share a tile of the factor
+ *     (co-visible frames, frames linked by a prior, and whatever fill adds); any other pair: RSBA_ERR_UNSUPPORTED naming the pair,
+ *     nothing written, the handle and the computed covariance stay usable.
+ *   rsba_covariance_intrinsics_block: cov [9][9] of intrinsics parameter block `block` (uncalibrated problems), zeros where constant.
+ *   rsba_covariance_point_blocks: cov [n][3][3], block p = the (point, point) block of point points[p] (points == NULL: points 0 .. n - 1,
+ *     n <= num_points) — V^-1 + V^-1 (sum over the point's pairs of observations W_o^T Sigma W_o') V^-1, plus the border's term.  The
+ *     frames of one point always share tiles of the factor, so every point is available.  Exact zeros for a constant point and for a
+ *     point without observations; a point whose frames and intrinsics are all constant gives V^-1.
+ *   rsba_covariance_memory: the device memory the covariance holds on the handle at the moment (the two tile arrays, two vectors of the
+ *     camera-side length, and the lists of the recurrence, which stay with the plan after a release), in bytes.
+ * The getters return RSBA_ERR_INVALID_ARGUMENT ("no covariance computed") before the first compute, after rsba_covariance_release and
+ * after any call that moves the parameters or changes the problem: rsba_solve, rsba_upload_parameters, rsba_set_loss,
+ * rsba_set_linear_solver.  The calls leave the handle as they found it: a later rsba_solve or rsba_pose_covariance gives what it
+ * gives on a fresh handle, bit for bit.  Cross blocks of a pose and a point, or of two points, are not part of this interface. */
+int32_t rsba_covariance_compute(rsba_handle* h);
+int32_t rsba_covariance_frame_blocks(rsba_handle* h, const int32_t* frame_a, const int32_t* frame_b, int64_t n, double* cov);
+int32_t rsba_covariance_intrinsics_block(rsba_handle* h, int32_t block, double* cov);
+int32_t rsba_covariance_point_blocks(rsba_handle* h, const int32_t* points, int64_t n, double* cov);
+int32_t rsba_covariance_memory(rsba_handle* h, int64_t* bytes);
+int32_t rsba_covariance_times(rsba_handle* h, double* ms5);   /* HIP-event times, ms: G, OFF, DIAG launches of the last compute; the last point getter's kernel; the last gather's — taken in a process started with RSBA_COV_TIMES=1 only, zeros otherwise */
+int32_t rsba_covariance_release(rsba_handle* h);
+
 /* == the frame-to-frame motion priors CeresHandler::Add attaches to a rolling-shutter frame (CeresHandler.h:147-185;
  * SURVEY §8f row f1): one 12-residual block per listed frame f >= 1 over (f.poses[0], f.poses[1], f-1.poses[0],
  * f-1.poses[1]) — RsConstVeloPrior (kind 1, video_bundler_rs_inter.h:55-108) or RsConstAccelerationPrior (kind 2,

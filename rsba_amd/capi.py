@@ -29,6 +29,8 @@ EXPORTS = [
     "rsba_match_descriptors", "rsba_match_last_kernel_ms",
     "rsba_default_linear_solver_options", "rsba_set_linear_solver", "rsba_get_linear_solver_stats",
     "rsba_default_loss", "rsba_set_loss", "rsba_get_loss",
+    "rsba_covariance_compute", "rsba_covariance_frame_blocks", "rsba_covariance_intrinsics_block", "rsba_covariance_release",
+    "rsba_covariance_point_blocks", "rsba_covariance_memory", "rsba_covariance_times",
 ]
 LINEAR_SOLVER_EXACT, LINEAR_SOLVER_PCG = 0, 1   # rsba_amd.h: RSBA_LINEAR_SOLVER_*
 LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TOLERANT = range(6)   # rsba_amd.h: RSBA_LOSS_*
@@ -390,6 +392,56 @@ class DeviceProblem:
         finally:
             self._exchanged()
         return out
+
+    def covariance_compute(self):
+        """Sigma = S^-1 on the tile pattern of the factor, kept on the device (rsba_amd.h: rsba_covariance_compute)."""
+        try:
+            _check(lib().rsba_covariance_compute(self._h))
+        finally:
+            self._exchanged()
+
+    def covariance_frame_blocks(self, pairs) -> np.ndarray:
+        """The (a, b) covariance blocks of the computed covariance -> [n, CD, CD]; pairs: n x 2 frame indices."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        fa, fb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        cd = 6 * self.prob.poses_per_frame
+        out = np.zeros((len(pr), cd, cd))
+        _check(lib().rsba_covariance_frame_blocks(self._h, _ptr(fa), _ptr(fb), C.c_int64(len(pr)), _ptr(out)))
+        return out
+
+    def covariance_intrinsics_block(self, block: int) -> np.ndarray:
+        """The covariance of one intrinsics parameter block -> [9, 9]"""
+        out = np.zeros((9, 9))
+        _check(lib().rsba_covariance_intrinsics_block(self._h, C.c_int32(block), _ptr(out)))
+        return out
+
+    def covariance_point_blocks(self, points=None) -> np.ndarray:
+        """The (point, point) covariance blocks of the computed covariance -> [n, 3, 3]; points: indices, None = every point."""
+        if points is None:
+            n, ptr = int(self.prob.num_points), None
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+            n, ptr = len(pts), _ptr(pts)
+        out = np.zeros((n, 3, 3))
+        _check(lib().rsba_covariance_point_blocks(self._h, ptr, C.c_int64(n), _ptr(out)))
+        return out
+
+    def covariance_memory(self) -> int:
+        """Bytes of device memory the covariance holds on this handle at the moment."""
+        b = C.c_int64(0)
+        _check(lib().rsba_covariance_memory(self._h, C.byref(b)))
+        return int(b.value)
+
+    def covariance_times(self) -> dict:
+        """HIP-event times (ms) of the last compute's G / OFF / DIAG launches, the last point getter's kernel and the last gather's
+        (RSBA_COV_TIMES=1 in the environment before the library loads; zeros otherwise)."""
+        ms = np.zeros(5)
+        _check(lib().rsba_covariance_times(self._h, _ptr(ms)))
+        return dict(zip(("g_ms", "off_ms", "diag_ms", "point_ms", "gather_ms"), (float(v) for v in ms)))
+
+    def covariance_release(self):
+        """Gives the tile arrays of the computed covariance back; the getters refuse until the next compute."""
+        _check(lib().rsba_covariance_release(self._h))
 
     def set_exchange_rccl(self, comm, rank: int, world: int):
         """Native transport of the multi-GPU exchange: ncclAllReduce on the solver's stream (rsba_amd.h)."""

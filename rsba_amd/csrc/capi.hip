@@ -316,6 +316,7 @@ int32_t rsba_set_stream(rsba_handle* h, void* s) {
 int32_t rsba_upload_parameters(rsba_handle* h, const double* poses, const double* points, const double* intr) {
   if (!h) return fail(RSBA_ERR_INVALID_ARGUMENT, "null handle");
   HIP_TRY(hipSetDevice(h->device));
+  rsba_covariance_invalidate(h);
   const DeviceProblem& dp = h->dp;
   if (poses) HIP_TRY(hipMemcpyAsync(dp.poses, poses, (size_t)dp.F * dp.P * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (points) HIP_TRY(hipMemcpyAsync(dp.points, points, (size_t)dp.M * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -569,6 +570,7 @@ int32_t rsba_set_linear_solver(rsba_handle* h, const rsba_linear_solver_options*
   if (o->min_iterations < 0 || o->max_iterations < 1 || !(o->eta == o->eta) || !(o->r_tolerance == o->r_tolerance))
     return fail(RSBA_ERR_INVALID_ARGUMENT, "linear solver options: min_iterations >= 0, max_iterations >= 1, eta and r_tolerance numbers");
   h->lin_opt = *o;
+  rsba_covariance_invalidate(h);
   return RSBA_OK;
 }
 
@@ -591,6 +593,7 @@ int32_t rsba_set_loss(rsba_handle* h, const rsba_loss* l) {
   if (l->type == RSBA_LOSS_TOLERANT && !good(l->b)) return fail(RSBA_ERR_INVALID_ARGUMENT, "TOLERANT: loss parameter b must be positive and finite");
   if (!good(l->scale)) return fail(RSBA_ERR_INVALID_ARGUMENT, "loss scale must be positive and finite");
   DeviceProblem& dp = h->dp;
+  rsba_covariance_invalidate(h);
   const bool was_general = dp.loss_general != 0;
   const double a = l->type == RSBA_LOSS_TRIVIAL ? 0.0 : l->a;
   // none, and Huber at scale 1: the one number the kernels have always looked at — their instantiations of old, bit for bit

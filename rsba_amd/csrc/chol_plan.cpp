@@ -265,4 +265,42 @@ void chol_tasks(const CholTaskInput& in, CholHostPlan* hp) {
   for (uint8_t b : sep_level) s.separator_levels += b;
 }
 
+bool selinv_plan(const CholHostPlan& hp, SelinvHostPlan* sp, int* bad_i, int* bad_k) {
+  SelinvHostPlan& p = *sp;
+  p = SelinvHostPlan{};
+  const int nt = hp.nt, nlev = hp.nlev;
+  p.nlev = nlev;
+  std::vector<std::vector<int32_t>> lev_cols((size_t)nlev);
+  for (int j = 0; j < nt; ++j) lev_cols[hp.level[j]].push_back(j);
+  p.lev_g_ptr.assign(1, 0); p.lev_off_ptr.assign(1, 0); p.lev_diag_ptr.assign(1, 0);
+  p.off_ptr.assign(1, 0); p.diag_ptr.assign(1, 0);
+  for (int l = nlev - 1; l >= 0; --l) {
+    for (int32_t j : lev_cols[l]) {
+      const std::vector<int32_t>& J = hp.col[j];
+      const int32_t tile_j = hp.perm[j];
+      for (size_t u = 0; u < J.size(); ++u) { p.g_info.push_back(hp.slot_base[j] + 1 + (int32_t)u); p.g_info.push_back(tile_j); }
+      for (size_t a = 0; a < J.size(); ++a) {
+        const int32_t i = J[a];
+        p.off_info.push_back(hp.slot_base[j] + 1 + (int32_t)a); p.off_info.push_back(tile_j);
+        for (size_t u = 0; u < J.size(); ++u) {
+          const int32_t k = J[u];
+          const int32_t s = i >= k ? hp.slot_of(i, k) : hp.slot_of(k, i);
+          if (s < 0) { if (bad_i) *bad_i = i; if (bad_k) *bad_k = k; return false; }
+          p.off_list.push_back(s); p.off_list.push_back(i < k ? 1 : 0); p.off_list.push_back(hp.slot_base[j] + 1 + (int32_t)u);
+        }
+        p.off_ptr.push_back((int32_t)(p.off_list.size() / 3));
+      }
+      p.diag_info.push_back(hp.slot_base[j]); p.diag_info.push_back(tile_j);
+      for (size_t u = 0; u < J.size(); ++u) p.diag_list.push_back(hp.slot_base[j] + 1 + (int32_t)u);
+      p.diag_ptr.push_back((int32_t)p.diag_list.size());
+    }
+    p.lev_g_ptr.push_back((int32_t)(p.g_info.size() / 2));
+    p.lev_off_ptr.push_back((int32_t)(p.off_info.size() / 2));
+    p.lev_diag_ptr.push_back((int32_t)(p.diag_info.size() / 2));
+  }
+  const int64_t T3 = (int64_t)kTile * kTile * kTile;
+  p.flops = 2 * T3 * ((int64_t)(p.g_info.size() / 2) + (int64_t)(p.off_list.size() / 3) + (int64_t)(p.diag_info.size() / 2) + (int64_t)p.diag_list.size());
+  return true;
+}
+
 }  // namespace rsba

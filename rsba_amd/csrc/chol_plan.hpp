@@ -72,4 +72,25 @@ struct CholHostPlan {
 void chol_symbolic(int nt, const std::vector<std::vector<int32_t>>& adj, const TileOrder& order, CholHostPlan* hp);
 void chol_tasks(const CholTaskInput& in, CholHostPlan* hp);   // (hp: what chol_symbolic left)
 
+// The selected inverse: every tile of Sigma = S^-1 ON THE FACTOR'S OWN PATTERN from the factor (W_j = L_jj^-1 on the diagonal, L_ij
+// below), by the Takahashi recurrence — with J = col[j], the sub-diagonal row tiles of column j after fill:
+//   G    per tile (k, j), k in J:   G_kj     = L_kj W_j
+//   OFF  per tile (i, j), i in J:   Sigma_ij = - sum_{k in J} Sigma_ik G_kj      (Sigma_ik from slot (i, k) if i >= k, else slot (k, i) transposed)
+//   DIAG per column j:              Sigma_jj = W_j^T W_j - sum_{k in J} Sigma_kj^T G_kj      (then symmetrised)
+// Columns are taken level by level, DESCENDING: the columns of one level are not ancestors of each other, an OFF item reads Sigma
+// tiles of higher levels only, a DIAG item those and the OFF outputs of its own column — one launch per (level, kind), nobody waits
+// for anybody inside one (kernels_selinv.hip).  The sums run in the order of col[j]: fixed, so two runs agree bit for bit.
+// Position p of the lev_*_ptr tables is elimination level nlev - 1 - p.  Sigma and G tiles use the factor's packed slots.
+struct SelinvHostPlan {
+  int nlev = 0;
+  std::vector<int32_t> lev_g_ptr, lev_off_ptr, lev_diag_ptr;   // [nlev + 1] ranges of the G / OFF / DIAG items per position
+  std::vector<int32_t> g_info;                                 // per G item: {slot_kj (of L, and of G), old tile of j (W_j)}
+  std::vector<int32_t> off_info, off_ptr, off_list;            // per OFF item: {slot_ij, old tile of j}; terms {slot of Sigma_ik or Sigma_ki, 1 = read it transposed, slot_kj of G}
+  std::vector<int32_t> diag_info, diag_ptr, diag_list;         // per DIAG item: {slot_jj, old tile of j}; terms {slot_kj of Sigma and of G}
+  int64_t flops = 0;                                           // 2 T^3 per tile product
+};
+// false (and *bad_i, *bad_k = the new indices of the pair, when given) if some (i, k), i, k in col[j], has no slot: fill closure says
+// it has one, the plan checks instead of assuming it
+bool selinv_plan(const CholHostPlan& hp, SelinvHostPlan* sp, int* bad_i = nullptr, int* bad_k = nullptr);   // (hp: what chol_tasks left)
+
 }  // namespace rsba

@@ -57,4 +57,5 @@ int32_t rsba_set_error(int32_t code, const char* msg);
 int32_t rsba_gradient(rsba_handle* h, double* gradient_host);
 void rsba_destroy_solver(rsba_handle* h);
 int32_t rsba_solver_loss_changed(rsba_handle* h);   // solver.hip: rsba_set_loss replaced the loss of a handle that has a plan
+void rsba_covariance_invalidate(rsba_handle* h);   // solver.hip: the parameters or the problem changed — the getters of rsba_covariance_compute refuse until the next compute
 void rsba_release_plan_scratch();   // solver.hip: the symbolic phase's host scratch (kept across handles)

@@ -4,6 +4,7 @@
 // top separators of the nested dissection of its tile graph (tile_order.hpp).
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "handle.hpp"
@@ -111,9 +112,8 @@ extern "C" int32_t rsba_debug_partition_tiles(const rsba_problem_desc* d, int32_
 // ranks would build it: ordered as the solver orders it (the leaf size from RSBA_CHOL_LEAF), sharded when the graph can be cut into
 // `world` parts, every tile pair of the graph a tile pair of S.  emit(ctx, name, data, count) is called once per list — and once
 // with "meta" = {sharded, levels, partial tiles, packed slots}; the data does not outlive the call.
-extern "C" int32_t rsba_debug_chol_plan(int32_t nt, int32_t num_edges, const int32_t* edges, int32_t world, int32_t rank, int32_t two_rhs, int32_t chunk, int32_t tail,
-                                        int32_t fuse_last, void (*emit)(void* ctx, const char* name, const int32_t* data, int64_t count), void* ctx) {
-  if (nt < 1 || num_edges < 0 || (num_edges && !edges) || world < 1 || rank < 0 || rank >= world || tail < 1 || chunk < tail || !emit) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad plan arguments");
+namespace {
+int32_t debug_plan_of_graph(int32_t nt, int32_t num_edges, const int32_t* edges, int32_t world, int32_t rank, int32_t two_rhs, const CholPlanOptions& opt, CholHostPlan* out) {
   std::vector<std::vector<int32_t>> adj(nt);
   std::vector<int32_t> pair_I, pair_J;
   for (int t = 0; t < nt; ++t) { pair_I.push_back(t); pair_J.push_back(t); }
@@ -127,12 +127,23 @@ extern "C" int32_t rsba_debug_chol_plan(int32_t nt, int32_t num_edges, const int
     for (int32_t u : adj[t]) if (u < t) { pair_I.push_back(t); pair_J.push_back(u); }
   }
   const TileOrder ord = nested_dissection(nt, adj, plan_leaf_size(world, nt), world);
-  CholHostPlan hp;
+  CholHostPlan& hp = *out;
   chol_symbolic(nt, adj, ord, &hp);
   CholTaskInput in;
   in.order = &ord; in.sharded = world > 1 && ord.parts_ok; in.rank = rank; in.two_rhs = two_rhs != 0; in.pair_I = &pair_I; in.pair_J = &pair_J;
-  in.opt.chunk = chunk; in.opt.tail = tail; in.opt.fuse_last = fuse_last != 0;
+  in.opt = opt;
   chol_tasks(in, &hp);
+  return RSBA_OK;
+}
+}  // namespace
+
+extern "C" int32_t rsba_debug_chol_plan(int32_t nt, int32_t num_edges, const int32_t* edges, int32_t world, int32_t rank, int32_t two_rhs, int32_t chunk, int32_t tail,
+                                        int32_t fuse_last, void (*emit)(void* ctx, const char* name, const int32_t* data, int64_t count), void* ctx) {
+  if (nt < 1 || num_edges < 0 || (num_edges && !edges) || world < 1 || rank < 0 || rank >= world || tail < 1 || chunk < tail || !emit) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad plan arguments");
+  CholPlanOptions opt;
+  opt.chunk = chunk; opt.tail = tail; opt.fuse_last = fuse_last != 0;
+  CholHostPlan hp;
+  if (const int32_t rc = debug_plan_of_graph(nt, num_edges, edges, world, rank, two_rhs, opt, &hp)) return rc;
   const std::vector<int32_t> meta{hp.sharded, hp.nlev, hp.nparts, hp.nslots};
   emit(ctx, "meta", meta.data(), (int64_t)meta.size());
   auto bytes = [&](const char* name, const std::vector<uint8_t>& v) { const std::vector<int32_t> w(v.begin(), v.end()); emit(ctx, name, w.data(), (int64_t)w.size()); };
@@ -145,6 +156,26 @@ extern "C" int32_t rsba_debug_chol_plan(int32_t nt, int32_t num_edges, const int
   RSBA_EMIT(top_slots); RSBA_EMIT(top_info); RSBA_EMIT(asm_ptr); RSBA_EMIT(asm_list); RSBA_EMIT(top_tiles); RSBA_EMIT(top_fill);
 #undef RSBA_EMIT
   bytes("row_mine", hp.row_mine); bytes("row_check", hp.row_check); bytes("row_sep", hp.row_sep);
+  return RSBA_OK;
+}
+
+// ... and the selected-inverse plan (chol_plan.hpp: selinv_plan) over the replicated Cholesky plan of the same tile graph, one rank: the
+// lists by name, "meta" = {levels, packed slots, tiles}, and what a check needs of the Cholesky plan beside them (perm, slot_tiles, level).
+extern "C" int32_t rsba_debug_selinv_plan(int32_t nt, int32_t num_edges, const int32_t* edges,
+                                          void (*emit)(void* ctx, const char* name, const int32_t* data, int64_t count), void* ctx) {
+  if (nt < 1 || num_edges < 0 || (num_edges && !edges) || !emit) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad plan arguments");
+  CholHostPlan hp;
+  if (const int32_t rc = debug_plan_of_graph(nt, num_edges, edges, 1, 0, 0, CholPlanOptions{}, &hp)) return rc;
+  SelinvHostPlan sp;
+  int bi = -1, bk = -1;
+  if (!selinv_plan(hp, &sp, &bi, &bk)) return rsba_set_error(RSBA_ERR_UNSUPPORTED, ("selected inverse: tile (" + std::to_string(bi) + ", " + std::to_string(bk) + ") of the fill pattern has no slot").c_str());
+  const std::vector<int32_t> meta{sp.nlev, hp.nslots, hp.nt};
+  emit(ctx, "meta", meta.data(), (int64_t)meta.size());
+#define RSBA_EMIT(o, x) emit(ctx, #x, o.x.data(), (int64_t)o.x.size())
+  RSBA_EMIT(hp, perm); RSBA_EMIT(hp, slot_tiles); RSBA_EMIT(hp, level);
+  RSBA_EMIT(sp, lev_g_ptr); RSBA_EMIT(sp, lev_off_ptr); RSBA_EMIT(sp, lev_diag_ptr); RSBA_EMIT(sp, g_info);
+  RSBA_EMIT(sp, off_info); RSBA_EMIT(sp, off_ptr); RSBA_EMIT(sp, off_list); RSBA_EMIT(sp, diag_info); RSBA_EMIT(sp, diag_ptr); RSBA_EMIT(sp, diag_list);
+#undef RSBA_EMIT
   return RSBA_OK;
 }
 #endif

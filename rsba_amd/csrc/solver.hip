@@ -139,6 +139,19 @@ struct Solver {
   double* ucross = nullptr;                                           // [F][CD][CD] motion-prior blocks (f, f-1), behind sv.U's J^T J blocks
   // iterative reduced solve (rsba_set_linear_solver type 1; pcg.hpp): lists and vectors, made by the first solve that asks for them
   bool pcg_on = false; bool pcg_ready = false; PcgHostPlan pcg_hp; PcgDev pcg{};
+  // covariance of every frame (rsba_covariance_compute): the selected inverse of the undamped S on the factor's pattern (chol_plan.hpp:
+  // SelinvHostPlan; kernels_selinv.hip).  The lists and the tile map are uploaded by the first compute and live as long as the plan; the two
+  // tile arrays ([nslots] tiles each: Sigma and G = L W) and the two vectors ([npad] each: the unknowns' marks, the border's v) go back
+  // to the cache with rsba_covariance_release or the plan.  cov_bytes: what the first compute allocated for all of this.
+  bool sel_ready = false; SelinvHostPlan sel; SelinvPlan sel_dev{};
+  double *cov_sigma = nullptr, *cov_g = nullptr, *cov_live = nullptr, *cov_vdev = nullptr;
+  const int32_t* cov_tmap = nullptr;          // [nt][nt] 2 * slot + transposed of every tile pair (unpermuted tile indices) of Sigma, -1 = not on the pattern
+  const double2* cov_slot_xy = nullptr;       // observations in slot order where the plan keeps none (sv.slot_xy == null: problems that keep records)
+  int64_t cov_plan_bytes = 0;                 // lists, tile map, slot_xy: as long as the plan
+  double cov_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // HIP-event times of the last compute's G, OFF and DIAG launches, of the last point getter's kernel and the last gather's
+  bool cov_valid = false;                     // the getters answer; cleared by whatever changes parameters or the problem
+  std::vector<double> cov_v, cov_ud;          // free interFrameRatio: v = S^-1 b [npad]; diag(U) [F * CD] (zero: a coordinate no residual touches)
+  double cov_border_scale = 0.0;              // 1 / (h - b.v), 0 without the border
 };
 
 }  // namespace rsba
@@ -1668,6 +1681,7 @@ void rsba_destroy_solver(rsba_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);   // (the side streams above are idle too: the blocks go back to the cache, devmem.hpp)
   const double td2 = dbg ? now_s() : 0.0;
   for (void* p : h->solver->allocs) dev_free(p);
+  for (double* p : {h->solver->cov_sigma, h->solver->cov_g, h->solver->cov_live, h->solver->cov_vdev}) if (p) dev_free(p);
   const double td3 = dbg ? now_s() : 0.0;
   delete h->solver;
   if (dbg) std::fprintf(stderr, "[rsba destroy] plan: streams + events to the pool %.2f ms; stream sync %.2f ms; blocks to the cache %.2f ms; host state %.2f ms\n", 1e3 * (td1 - td0), 1e3 * (td2 - td1), 1e3 * (td3 - td2), 1e3 * (now_s() - td3));
@@ -1898,6 +1912,300 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
   return RSBA_OK;
 }
 
+// ---- covariance of every frame: the selected inverse of the undamped reduced camera system (kernels_selinv.hip) ----
+// rsba_covariance_compute linearises and factors exactly as rsba_pose_covariance does, then runs the Takahashi recurrence over the
+// factor's own tile pattern into a tile array of its own — every (f, f) block, every (f, g) block whose tile the factor has and the
+// intrinsics blocks are then one gather away (rsba_covariance_frame_blocks / rsba_covariance_intrinsics_block).
+void rsba_covariance_invalidate(rsba_handle* h) { if (h && h->solver) h->solver->cov_valid = false; }
+
+namespace {
+// RSBA_COV_TIMES=1: HIP events around the covariance kernels (rsba_covariance_times; tools/cov_time.py).  Off, no event is created.
+bool cov_times_on() { static const bool on = [] { const char* e = std::getenv("RSBA_COV_TIMES"); return e && e[0] == '1'; }(); return on; }
+// one kernel between two events, where the times are asked for
+struct CovStopwatch {
+  hipEvent_t t0 = nullptr, t1 = nullptr; bool on = cov_times_on();
+  ~CovStopwatch() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
+  hipError_t start(hipStream_t st) { if (!on) return hipSuccess; hipError_t e = hipEventCreate(&t0); if (e == hipSuccess) e = hipEventCreate(&t1); return e == hipSuccess ? hipEventRecord(t0, st) : e; }
+  hipError_t stop(hipStream_t st) { return on ? hipEventRecord(t1, st) : hipSuccess; }
+  void read(double* ms) { float f = 0.f; if (on && t0 && t1 && hipEventElapsedTime(&f, t0, t1) == hipSuccess) *ms = f; }   // (after the stream's synchronisation)
+};
+int32_t covariance_ready(rsba_handle* h) {
+  if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
+  if (!h->solver || !h->solver->cov_valid) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "no covariance computed (rsba_covariance_compute comes first, and again after anything that changes the parameters or the problem)");
+  return RSBA_OK;
+}
+// n blocks of dim x dim entries of Sigma: block p starts at camera-side scalar row row0[p], column col0[p] (a block may cross one tile
+// edge each way).  *missing = the first block that needs a tile the factor's pattern does not have (-1: none; nothing was gathered then)
+int32_t covariance_gather(rsba_handle* h, const std::vector<int64_t>& row0, const std::vector<int64_t>& col0, int dim, double* out, int64_t* missing) {
+  Solver* s = h->solver; hipStream_t st = h->stream;
+  const int64_t n = (int64_t)row0.size();
+  *missing = -1;
+  if (n == 0) return RSBA_OK;
+  std::vector<int32_t> desc(8 * (size_t)n, -1);
+  for (int64_t p = 0; p < n; ++p) {
+    int32_t* d = &desc[8 * (size_t)p];
+    d[0] = (int32_t)row0[p]; d[1] = (int32_t)col0[p];
+    const int tr0 = (int)(row0[p] / kTile), tc0 = (int)(col0[p] / kTile);
+    const int nr = (row0[p] % kTile + dim > kTile) ? 2 : 1, nc = (col0[p] % kTile + dim > kTile) ? 2 : 1;
+    for (int x = 0; x < nr; ++x) for (int y = 0; y < nc; ++y) {
+      const int pi = s->hp.iperm[tr0 + x], pj = s->hp.iperm[tc0 + y];
+      const int32_t slot = pi >= pj ? s->hp.slot_of(pi, pj) : s->hp.slot_of(pj, pi);
+      if (slot < 0) { *missing = p; return RSBA_OK; }
+      d[2 + 2 * x + y] = 2 * slot + (pi < pj ? 1 : 0);
+    }
+  }
+  void* d_desc = nullptr; void* d_out = nullptr;
+  const size_t out_bytes = (size_t)n * dim * dim * sizeof(double);
+  HIP_TRY(dev_malloc(&d_desc, desc.size() * sizeof(int32_t)));
+  hipError_t e = dev_malloc(&d_out, out_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  CovStopwatch watch;
+  if (e == hipSuccess) e = watch.start(st);
+  if (e == hipSuccess) e = launch_cov_gather(s->cov_sigma, static_cast<const int32_t*>(d_desc), n, dim, static_cast<double*>(d_out), st);
+  if (e == hipSuccess) e = watch.stop(st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);   // (also before the blocks go back to the cache)
+  if (e == hipSuccess && e2 == hipSuccess) watch.read(&s->cov_ms[4]);
+  dev_free(d_desc); if (d_out) dev_free(d_out);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return rsba_set_error(e == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, hipGetErrorString(e));
+  return RSBA_OK;
+}
+}  // namespace
+
+extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
+  if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
+  if (h->allreduce) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "rsba_covariance_compute does not take a handle with an exchange attached (one rank only)");
+  HIP_TRY(hipSetDevice(h->device));
+  int32_t rc = build_solver(h);
+  if (rc) return rc;
+  Solver* s = h->solver; SolverDev& sv = s->sv; hipStream_t st = h->stream; const int CD = sv.CD;
+  s->cov_valid = false;
+  if (!s->sel_ready) {
+    int bi = -1, bk = -1;
+    if (!selinv_plan(s->hp, &s->sel, &bi, &bk))
+      return rsba_set_error(RSBA_ERR_UNSUPPORTED, ("selected inverse: tile (" + std::to_string(bi) + ", " + std::to_string(bk) + ") of the factor's fill pattern has no slot").c_str());
+    SelinvPlan& d = s->sel_dev;
+    if ((rc = s_upload_const(s, &d.g_info, s->sel.g_info)) || (rc = s_upload_const(s, &d.off_info, s->sel.off_info)) || (rc = s_upload_const(s, &d.off_ptr, s->sel.off_ptr)) ||
+        (rc = s_upload_const(s, &d.off_list, s->sel.off_list)) || (rc = s_upload_const(s, &d.diag_info, s->sel.diag_info)) || (rc = s_upload_const(s, &d.diag_ptr, s->sel.diag_ptr)) ||
+        (rc = s_upload_const(s, &d.diag_list, s->sel.diag_list))) return rc;
+    // every tile pair of Sigma by unpermuted tile indices: the point blocks look entries up by camera-side coordinates
+    std::vector<int32_t> tmap((size_t)sv.nt * sv.nt, -1);
+    for (int a = 0; a < sv.nt; ++a) for (int b = 0; b < sv.nt; ++b) {
+      const int pi = s->hp.iperm[a], pj = s->hp.iperm[b];
+      const int32_t slot = pi >= pj ? s->hp.slot_of(pi, pj) : s->hp.slot_of(pj, pi);
+      if (slot >= 0) tmap[(size_t)a * sv.nt + b] = 2 * slot + (pi < pj ? 1 : 0);
+    }
+    if ((rc = s_upload_const(s, &s->cov_tmap, tmap))) return rc;
+    s->cov_plan_bytes = (int64_t)sizeof(int32_t) * (int64_t)(tmap.size() + s->sel.g_info.size() + s->sel.off_info.size() + s->sel.off_ptr.size() + s->sel.off_list.size() +
+                                                               s->sel.diag_info.size() + s->sel.diag_ptr.size() + s->sel.diag_list.size());
+    if (sv.slot_xy) s->cov_slot_xy = sv.slot_xy;
+    else {
+      double2* sxy = nullptr;
+      if ((rc = s_alloc(s, &sxy, (size_t)h->dp.N))) return rc;
+      HIP_TRY(launch_slot_xy(h->dp, sxy, st));
+      s->cov_slot_xy = sxy;
+      s->cov_plan_bytes += (int64_t)sizeof(double2) * h->dp.N;
+    }
+    s->sel_ready = true;
+  }
+  const size_t tile_bytes = (size_t)sv.nslots * kTile * kTile * sizeof(double);
+  for (double** p : {&s->cov_sigma, &s->cov_g}) if (!*p) { void* q = nullptr; HIP_TRY(dev_malloc(&q, tile_bytes)); *p = static_cast<double*>(q); }
+  for (double** p : {&s->cov_live, &s->cov_vdev}) if (!*p) { void* q = nullptr; HIP_TRY(dev_malloc(&q, (size_t)sv.npad * sizeof(double))); *p = static_cast<double*>(q); }
+  // the undamped, unscaled reduced system and its factor: as rsba_pose_covariance
+  if ((rc = reset_scales(h))) return rc;
+  if ((rc = linearize(h))) return rc;
+  HIP_TRY(launch_clamp_diagonal(h->dp, sv, 1e-6, 1e32, st));
+  HIP_TRY(launch_pose_prior_clamp(h->dp, s->pp, 1e-6, 1e32, st));
+  HIP_TRY(hipMemsetAsync(sv.chol_fail, 0, sizeof(int), st));
+  if ((rc = reduce_system(h, 1e300))) return rc;
+  if (s->hp.two_rhs) HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));
+  // the factorisation rides on one solve (the right-hand side reduce_system left: its result is only what the persistent driver's
+  // verification looks at), the border column of a free interFrameRatio on a second; a suspect result is redone on the level schedule
+  double hb[3] = {0.0, 0.0, 0.0};
+  int fail = 0, nfail = 0;
+  s->cov_v.clear();
+  {
+  struct LevelsGuard { Solver* s; bool was; ~LevelsGuard() { s->use_levels = was; } } levels_guard{s, s->use_levels};   // (whichever way the attempts end)
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    HIP_TRY(hipMemsetAsync(sv.scalars + kDagSuspect, 0, sizeof(double), st));
+    if ((rc = solve_reduced_system(h))) return rc;
+    if (s->border) {
+      const double* v = nullptr;
+      if ((rc = solve_again(h, s->border, &v))) return rc;
+      HIP_TRY(launch_border_dots(s->border, v, v, sv.npad, s->ratio4 + 2, st));
+      s->cov_v.resize((size_t)sv.npad);
+      HIP_TRY(hipMemcpyAsync(s->cov_v.data(), v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->cov_vdev, v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(hb, s->ratio4, sizeof hb, hipMemcpyDeviceToHost, st));     // {h, g, b.v}
+    }
+    double suspect = 0.0;
+    if ((rc = await_verification(h))) return rc;
+    // (the two failure flags and diag(U) ride on the synchronisation the verification needs anyway)
+    s->cov_ud.resize((size_t)h->dp.F * CD);
+    HIP_TRY(hipMemcpyAsync(&suspect, sv.scalars + kDagSuspect, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->cov_ud.data(), sv.udiag, s->cov_ud.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (suspect == 0.0 || s->use_levels) break;
+    s->use_levels = true; ++s->dag_fallbacks;
+  }
+  }
+  // a failed evaluation or a rank-deficient factor: nothing to invert, no launch
+  if (nfail) return rsba_set_error(RSBA_ERR_EVALUATION_FAILED, "residual and Jacobian evaluation failed");
+  if (fail) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "J^T J is rank deficient (fix the gauge): no covariance, as ceres::Covariance::Compute returns false");
+  // Sigma on the factor's pattern: every G tile at once (they only read the factor), then level after level, descending, OFF before DIAG
+  const SelinvHostPlan& sp = s->sel;
+  // (RSBA_COV_TIMES=1: an event between the launches, rsba_covariance_times splits the compute by kind; otherwise no event at all)
+  struct Marks {
+    bool on = cov_times_on(); std::vector<hipEvent_t> ev; std::vector<int> kind;
+    ~Marks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    hipError_t mark(int k, hipStream_t st) { if (!on) return hipSuccess; hipEvent_t e; hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; ev.push_back(e); kind.push_back(k); return hipEventRecord(e, st); }
+  } marks;
+  HIP_TRY(launch_cov_live(sv, h->d_mask_pose, s->cov_live, st));
+  HIP_TRY(marks.mark(0, st));
+  HIP_TRY(launch_selinv_g(sv, s->sel_dev, s->cov_live, s->cov_g, 0, (int)(sp.g_info.size() / 2), st));
+  for (int p = 0; p < sp.nlev; ++p) {
+    HIP_TRY(marks.mark(1, st));
+    HIP_TRY(launch_selinv_off(s->sel_dev, s->cov_sigma, s->cov_g, sp.lev_off_ptr[p], sp.lev_off_ptr[p + 1] - sp.lev_off_ptr[p], st));
+    HIP_TRY(marks.mark(2, st));
+    HIP_TRY(launch_selinv_diag(sv, s->sel_dev, s->cov_live, s->cov_sigma, s->cov_g, sp.lev_diag_ptr[p], sp.lev_diag_ptr[p + 1] - sp.lev_diag_ptr[p], st));
+  }
+  HIP_TRY(marks.mark(-1, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->cov_ms[0] = s->cov_ms[1] = s->cov_ms[2] = 0.0;
+  for (size_t k = 0; k + 1 < marks.ev.size(); ++k) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, marks.ev[k], marks.ev[k + 1])); s->cov_ms[marks.kind[k]] += ms; }
+  s->cov_border_scale = 0.0;
+  if (s->border) {
+    const double schur = hb[0] - hb[2];
+    if (!(schur > 0.0) || !std::isfinite(schur)) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "J^T J is rank deficient in the interFrameRatio: no covariance");
+    s->cov_border_scale = 1.0 / schur;
+  }
+  s->cov_valid = true;
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_covariance_frame_blocks(rsba_handle* h, const int32_t* frame_a, const int32_t* frame_b, int64_t n, double* cov) {
+  if (int32_t rc = covariance_ready(h)) return rc;
+  if (n < 0 || (n > 0 && (!frame_a || !frame_b || !cov))) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad covariance block arguments");
+  HIP_TRY(hipSetDevice(h->device));
+  Solver* s = h->solver; const int CD = s->sv.CD, F = h->dp.F;
+  std::vector<int64_t> row0((size_t)n), col0((size_t)n);
+  for (int64_t p = 0; p < n; ++p) {
+    if (frame_a[p] < 0 || frame_a[p] >= F || frame_b[p] < 0 || frame_b[p] >= F) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "frame out of range");
+    row0[p] = (int64_t)frame_a[p] * CD; col0[p] = (int64_t)frame_b[p] * CD;
+  }
+  int64_t missing = -1;
+  if (int32_t rc = covariance_gather(h, row0, col0, CD, cov, &missing)) return rc;
+  if (missing >= 0)
+    return rsba_set_error(RSBA_ERR_UNSUPPORTED, ("frames " + std::to_string(frame_a[missing]) + " and " + std::to_string(frame_b[missing]) +
+                                                 " share no tile of the factor's pattern: their covariance block is not part of the selected inverse").c_str());
+  const bool border = !s->cov_v.empty();
+  for (int64_t p = 0; p < n; ++p) {
+    const size_t ra = (size_t)frame_a[p] * CD, rb = (size_t)frame_b[p] * CD;
+    double* c = cov + (size_t)p * CD * CD;
+    for (int a = 0; a < CD; ++a) for (int b = 0; b < CD; ++b) {
+      // (fixed coordinates and coordinates no residual touches are no parameters of the program: exact zeros, as rsba_pose_covariance)
+      const bool live = s->cov_ud[ra + a] != 0.0 && h->mask_pose[ra + a] != 0.0 && s->cov_ud[rb + b] != 0.0 && h->mask_pose[rb + b] != 0.0;
+      c[a * CD + b] = live ? c[a * CD + b] + (border ? s->cov_v[ra + a] * s->cov_v[rb + b] * s->cov_border_scale : 0.0) : 0.0;
+    }
+  }
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_covariance_intrinsics_block(rsba_handle* h, int32_t block, double* cov) {
+  if (int32_t rc = covariance_ready(h)) return rc;
+  Solver* s = h->solver; const SolverDev& sv = s->sv;
+  if (!cov) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (block < 0 || block >= sv.NIB) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, sv.NIB ? "intrinsics block out of range" : "the problem has no intrinsics parameter blocks (calibrated)");
+  HIP_TRY(hipSetDevice(h->device));
+  // the 9 coordinates of block c sit at the front of its pseudo frames, behind the real frames
+  const int64_t r0 = ((int64_t)sv.F + (int64_t)block * sv.NPF) * sv.CD;
+  int64_t missing = -1;
+  if (int32_t rc = covariance_gather(h, {r0}, {r0}, 9, cov, &missing)) return rc;
+  if (missing >= 0) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "the intrinsics block crosses a tile edge whose off-diagonal tile the factor's pattern does not have");
+  const bool border = !s->cov_v.empty();
+  for (int a = 0; a < 9; ++a) for (int b = 0; b < 9; ++b) {
+    const bool live = h->mask_intr[(size_t)block * 9 + a] != 0.0 && h->mask_intr[(size_t)block * 9 + b] != 0.0;
+    cov[a * 9 + b] = live ? cov[a * 9 + b] + (border ? s->cov_v[(size_t)r0 + a] * s->cov_v[(size_t)r0 + b] * s->cov_border_scale : 0.0) : 0.0;
+  }
+  return RSBA_OK;
+}
+
+// The 3 x 3 block of every asked point (kernels_selinv.hip: cov_point_kernel).  A constant point and a point nobody sees are no unknowns:
+// exact zeros.
+extern "C" int32_t rsba_covariance_point_blocks(rsba_handle* h, const int32_t* points, int64_t n, double* cov) {
+  if (int32_t rc = covariance_ready(h)) return rc;
+  const int64_t M = h->dp.M;
+  if (n < 0 || (n > 0 && !cov) || (!points && n > M)) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad covariance block arguments");
+  if (points) for (int64_t p = 0; p < n; ++p) if (points[p] < 0 || points[p] >= M) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "point out of range");
+  if (n == 0) return RSBA_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  Solver* s = h->solver; hipStream_t st = h->stream;
+  void *d_pts = nullptr, *d_out = nullptr, *d_miss = nullptr;
+  const size_t out_bytes = (size_t)n * 9 * sizeof(double);
+  int missing = 0;
+  hipError_t e = dev_malloc(&d_out, out_bytes);
+  if (e == hipSuccess) e = dev_malloc(&d_miss, sizeof(int));
+  if (e == hipSuccess && points) e = dev_malloc(&d_pts, (size_t)n * sizeof(int32_t));
+  if (e == hipSuccess && points) e = hipMemcpyAsync(d_pts, points, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_miss, 0, sizeof(int), st);
+  CovStopwatch watch;
+  if (e == hipSuccess) e = watch.start(st);
+  if (e == hipSuccess) e = launch_cov_points(h->dp, s->sv, s->cov_sigma, s->cov_tmap, s->cov_v.empty() ? nullptr : s->cov_vdev, s->cov_border_scale, static_cast<const int32_t*>(d_pts), n,
+                                             s->cov_slot_xy, static_cast<double*>(d_out), static_cast<int*>(d_miss), st);
+  if (e == hipSuccess) e = watch.stop(st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cov, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&missing, d_miss, sizeof(int), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);   // (also before the blocks go back to the cache)
+  if (e == hipSuccess && e2 == hipSuccess) watch.read(&s->cov_ms[3]);
+  for (void* p : {d_pts, d_out, d_miss}) if (p) dev_free(p);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return rsba_set_error(e == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, hipGetErrorString(e));
+  if (missing) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "two frames of one point share no tile of the factor's pattern: the plan of the reduced system does not cover the point's pairs");
+  for (int64_t p = 0; p < n; ++p) {
+    const int64_t j = points ? points[p] : p;
+    if (h->mask_point[(size_t)j * 3] == 0.0) for (int k = 0; k < 9; ++k) cov[(size_t)p * 9 + k] = 0.0;
+  }
+  return RSBA_OK;
+}
+
+// Device memory the covariance holds on this handle right now: the tile arrays and vectors of a computed covariance (gone after
+// rsba_covariance_release) plus the lists the first compute uploaded (with the plan).
+extern "C" int32_t rsba_covariance_memory(rsba_handle* h, int64_t* bytes) {
+  if (!h || !bytes) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = 0;
+  if (!h->solver) return RSBA_OK;
+  const Solver* s = h->solver;
+  *bytes = s->cov_plan_bytes;
+  if (s->cov_sigma) *bytes += 2 * (int64_t)s->sv.nslots * kTile * kTile * (int64_t)sizeof(double);
+  if (s->cov_live) *bytes += 2 * (int64_t)s->sv.npad * (int64_t)sizeof(double);
+  return RSBA_OK;
+}
+
+// HIP-event times of the covariance kernels, ms: {G, OFF, DIAG launches of the last compute, the last point getter's kernel, the last gather's};
+// taken only in a process started with RSBA_COV_TIMES=1 (zeros otherwise: the calls create no events then)
+extern "C" int32_t rsba_covariance_times(rsba_handle* h, double* ms5) {
+  if (!h || !ms5) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  for (int k = 0; k < 5; ++k) ms5[k] = h->solver ? h->solver->cov_ms[k] : 0.0;
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_covariance_release(rsba_handle* h) {
+  if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
+  if (!h->solver) return RSBA_OK;
+  Solver* s = h->solver;
+  s->cov_valid = false;
+  if (s->cov_sigma || s->cov_g || s->cov_live || s->cov_vdev) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // nothing on the device touches the tiles any more: they go back to the cache (devmem.hpp)
+    for (double** p : {&s->cov_sigma, &s->cov_g, &s->cov_live, &s->cov_vdev}) if (*p) { dev_free(*p); *p = nullptr; }
+  }
+  s->cov_v.clear(); s->cov_v.shrink_to_fit(); s->cov_ud.clear(); s->cov_ud.shrink_to_fit();
+  return RSBA_OK;
+}
+
 extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rsba_solver_summary* sum, rsba_iteration* trace, int32_t trace_cap) {
   if (!h || !opt || !sum) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
@@ -1906,6 +2214,7 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver; SolverDev& sv = s->sv; DeviceProblem& dp = h->dp; hipStream_t st = h->stream;
+  s->cov_valid = false;   // (rsba_covariance_compute: the parameters move)
   // The iterative linear solver (rsba_set_linear_solver): what it does not take is refused before anything of the solve has run
   s->pcg_on = h->lin_opt.type == RSBA_LINEAR_SOLVER_PCG;
   h->lin_stats = rsba_linear_solver_stats{};

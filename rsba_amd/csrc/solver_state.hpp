@@ -204,6 +204,19 @@ hipError_t launch_chol_solve(const SolverDev& sv, const CholPlan& pl, const DagA
 hipError_t launch_chol_solve_level(const SolverDev& sv, const CholPlan& pl, bool backward, int first, int count, const double* b2, double* zy2, hipStream_t st);   // the same tasks, one launch per level
 hipError_t launch_chol_dag(const SolverDev& sv, const CholPlan& pl, const DagArgs* device_args, int workgroups, bool one_per_cu, hipStream_t st);   // one_per_cu: LDS request above half a CU's, so that two never share one
 
+// kernels_selinv.hip: the selected inverse on the factor's pattern (chol_plan.hpp: SelinvHostPlan — its lists, device pointers), one
+// launch per (level, kind), and the gather of n dim x dim blocks out of its tiles
+struct SelinvPlan { const int32_t *g_info, *off_info, *off_ptr, *off_list, *diag_info, *diag_ptr, *diag_list; };
+hipError_t launch_selinv_g(const SolverDev& sv, const SelinvPlan& pl, const double* live, double* G, int first, int count, hipStream_t st);
+hipError_t launch_selinv_off(const SelinvPlan& pl, double* Sigma, const double* G, int first, int count, hipStream_t st);
+hipError_t launch_selinv_diag(const SolverDev& sv, const SelinvPlan& pl, const double* live, double* Sigma, const double* G, int first, int count, hipStream_t st);
+hipError_t launch_cov_live(const SolverDev& sv, const double* mask_pose, double* live, hipStream_t st);   // live [npad]: 1 = the camera-side coordinate is an unknown of the program
+// the 3 x 3 covariance blocks of n points (points: their indices, null = 0 .. n - 1) -> out [n][9]; tmap [nt][nt]: 2 * slot + transposed of a tile pair of
+// Sigma, -1 = none (*missing is set when a pair of a point's frames has none); v, border_scale: the border of a free interFrameRatio (null, 0: none)
+hipError_t launch_cov_points(const DeviceProblem& dp, const SolverDev& sv, const double* Sigma, const int32_t* tmap, const double* v, double border_scale, const int32_t* points,
+                             int64_t n, const double2* slot_xy, double* out, int* missing, hipStream_t st);
+hipError_t launch_cov_gather(const double* Sigma, const int32_t* desc, int64_t n, int dim, double* out, hipStream_t st);   // desc [n][8]: kernels_selinv.hip
+
 // kernels_normal.hip
 hipError_t launch_camera_blocks(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st, bool take_candidate = false, bool padding_is_zero = false);   // take_candidate: launch_lm_take_candidate's copy rides along
 hipError_t launch_point_blocks(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st);
