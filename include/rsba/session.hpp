@@ -1,7 +1,7 @@
 // Host data model of one SfM session, field-for-field what rsba's Thrift IDL generates
 // (/root/reference/src/rsba/sfm.thrift:13-74, gen-cpp/sfm_types.h:51-66,133-146,259-272,332-348) minus
 // the RPC / serialisation machinery, plus the option fields the bundle-adjustment path reads
-// (/root/reference/src/rsba/SfmOptions.h:23-27,40-46,63-87).  Parameter blocks are the std::vector<double>
+// (/root/reference/src/rsba/SfmOptions.h:23-27,31-37,40-46,63-87).  Parameter blocks are the std::vector<double>
 // storage inside Frame::poses[i] / Track::pt / Session::cam — block identity is the address, exactly as in
 // the reference.
 #pragma once
@@ -66,6 +66,13 @@ struct SfmOptions {
     bool calibrated = true;
     bool constVelocity = false;
   } model;
+  struct ModelInit {                  // SfmOptions.h:31-37: how a new frame is localised (new_frame.hpp)
+    bool reuseLastPose = true;        // initialize next frame with last known pose
+    bool solveGsPnP = false;          // use the traditional PnP RANSAC to find next pose
+    bool solveRsPnP = true;           // use the rolling shutter PnP RANSAC to find next pose
+    unsigned minPnPfeatures = 6;      // minimal RS PnP RANSAC parameterization
+    bool refinePnP = false;           // BA frame after PnP to refine estimate; not necessary with solveRsPnP
+  } mod_init;
   struct Tracks {
     bool synthetic = false;           // SfmOptions.h:40; createTracks runs evalTracks instead (VideoSfMHandler.cc:285-288)
     double sqrdThreshold = 16.0;
@@ -87,6 +94,9 @@ struct SfmOptions {
     double interFrameRatio = 1;       // SfmOptions.h:75; 1 = a free, lower-bounded parameter block that Solve optimises (CeresHandler.h:161,172,175)
     double trustPriorCamPosition = 0;
     double trustPriorCamRotation = 0;
+    bool pnpNewFrame = false;            // SfmOptions.h:80-82: least squares PnP after every new frame (VideoSfMHandler.cc:427)
+    unsigned baIterationsOnNewFrame = 0; // BA iterations after every new frame
+    unsigned baWindowOnNewFrame = 0;     // BA window size after every new frame, 0 for fullBA
     bool revalidateReprojections = false;
   } ceres;
   struct Debug {

@@ -105,8 +105,8 @@ inline void smallest_eigenvector12(double a[12][12], double vec[12], double gap[
   for (int i = 1; i < 12; ++i) if (a[i][i] < a[best][best]) best = i;
   for (int k = 0; k < 12; ++k) vec[k] = v[k][best];
   if (gap) {   // the two smallest eigenvalues and the largest: is the null space ONE direction?
-    double second = -1.0, largest = 0.0;
-    for (int i = 0; i < 12; ++i) { if (i != best && (second < 0.0 || a[i][i] < second)) second = a[i][i]; largest = std::fmax(largest, a[i][i]); }
+    double second = 0.0, largest = 0.0; bool have_second = false;   // (a flag, not a negative sentinel: rounding can leave a zero eigenvalue slightly negative)
+    for (int i = 0; i < 12; ++i) { if (i != best && (!have_second || a[i][i] < second)) { second = a[i][i]; have_second = true; } largest = std::fmax(largest, a[i][i]); }
     gap[0] = a[best][best]; gap[1] = second; gap[2] = largest;
   }
 }
@@ -277,15 +277,38 @@ inline bool solveGsPnP(const float* opoints, const float* ipoints, int n, const 
 
 // cv::solvePnPRansac as the reference uses it at solveRSpnp.cpp:437-449: minimal subsets, a pose per subset, the pose with the most
 // points inside reprojectionError wins.  The subsets' DLT poses are refined and scored on the device in ONE launch.  Returns the
-// number of inliers of the winner (0: none found).
+// number of inliers of the winner (0: none found).  hypotheses_on_device: the subsets' DLT poses are computed on the device too
+// (rsba_pnp_gs_hypotheses) instead of by pnp_detail::dlt_pose here — the same subsets, the same rule for the winner.
 inline int solveGsPnPRansac(const float* opoints, const float* ipoints, int n, const double cam[NUM_CAM_PARAMS], double pose[6], int iterationsCount,
-                            float reprojectionError, int min_points_count = 6, uint64_t rng_state = 0x9e3779b97f4a7c15ULL, int device = 0) {
+                            float reprojectionError, int min_points_count = 6, uint64_t rng_state = 0x9e3779b97f4a7c15ULL, int device = 0,
+                            bool hypotheses_on_device = false) {
   const int m = min_points_count < 6 ? 6 : min_points_count;
   if (n < m || iterationsCount <= 0) return 0;
-  const std::vector<double> nrm = pnp_detail::normalised_points(cam, ipoints, n);
   pnp_detail::Rng gen(rng_state);
-  std::vector<int32_t> subsets; std::vector<double> inits;
   std::vector<int32_t> pick((size_t)m);
+  if (hypotheses_on_device) {   // the same subsets in the same order; normalisation, DLT, refinement and scoring in one call (rsba_pnp_gs_hypotheses)
+    std::vector<int32_t> all_subsets((size_t)iterationsCount * m);
+    for (int it = 0; it < iterationsCount; ++it) {
+      for (int k = 0; k < m;) {
+        const int c = gen.uniform(0, n); bool dup = false;
+        for (int j = 0; j < k; ++j) dup = dup || pick[(size_t)j] == c;
+        if (!dup) pick[(size_t)k++] = c;
+      }
+      for (int k = 0; k < m; ++k) all_subsets[(size_t)it * m + k] = pick[(size_t)k];
+    }
+    std::vector<double> poses((size_t)iterationsCount * 6);
+    std::vector<uint8_t> status((size_t)iterationsCount);
+    std::vector<int32_t> count((size_t)iterationsCount);
+    pnp_detail::check(rsba_pnp_gs_hypotheses(device, cam, opoints, ipoints, n, all_subsets.data(), m, iterationsCount, 5, reprojectionError, poses.data(),
+                                             status.data(), nullptr, count.data()));
+    int best = -1;
+    for (int t = 0; t < iterationsCount; ++t) if (status[(size_t)t] != 0 && (best < 0 || count[(size_t)t] > count[(size_t)best])) best = t;
+    if (best < 0) return 0;
+    for (int k = 0; k < 6; ++k) pose[k] = poses[(size_t)best * 6 + k];
+    return count[(size_t)best];
+  }
+  const std::vector<double> nrm = pnp_detail::normalised_points(cam, ipoints, n);
+  std::vector<int32_t> subsets; std::vector<double> inits;
   for (int it = 0; it < iterationsCount; ++it) {
     for (int k = 0; k < m;) {   // m distinct indices
       const int c = gen.uniform(0, n); bool dup = false;
@@ -336,7 +359,7 @@ inline bool solveRsPnP(const float* opoints, const float* ipoints, int n, const 
 inline void solveRsPnPRansac(const float* opoints, const float* ipoints, int n, const double cam[NUM_CAM_PARAMS], double rvec[3], double tvec[3],
                              double rvec2[3], double tvec2[3], const SHUTTER shutter, const int scanlines[2], int iterationsCount = 100,
                              float reprojectionError = 8.0f, int minInliersCount = 100, std::vector<int>* inliers = nullptr,
-                             int min_points_count = 6, uint64_t rng_state = 0xffffffffULL, int device = 0) {
+                             int min_points_count = 6, uint64_t rng_state = 0xffffffffULL, int device = 0, bool hypotheses_on_device = false) {
   double l1 = 0.0;
   for (int i = 0; i < 3; ++i) l1 += std::fabs(rvec[i]) + std::fabs(tvec[i]) + std::fabs(rvec2[i]) + std::fabs(tvec2[i]);
   double init[12];
@@ -344,7 +367,7 @@ inline void solveRsPnPRansac(const float* opoints, const float* ipoints, int n, 
   pnp_detail::to_pose(rvec2, tvec2, init + 6);
   if (l1 == 0.0) {   // GS Init (:437-449): global-shutter RANSAC at twice the threshold, taken when it finds more than four inliers
     double gs[6];
-    if (solveGsPnPRansac(opoints, ipoints, n, cam, gs, iterationsCount, reprojectionError * 2, min_points_count, rng_state ^ 0x9e3779b97f4a7c15ULL, device) > 4)
+    if (solveGsPnPRansac(opoints, ipoints, n, cam, gs, iterationsCount, reprojectionError * 2, min_points_count, rng_state ^ 0x9e3779b97f4a7c15ULL, device, hypotheses_on_device) > 4)
       for (int k = 0; k < 6; ++k) init[k] = init[6 + k] = gs[k];
   }
   if (minInliersCount <= 0) minInliersCount = n;                                        // :453-454

@@ -497,6 +497,23 @@ int32_t rsba_pnp_tasks(int32_t device, const double* cam, int32_t shutter, const
 int32_t rsba_pnp_inliers(int32_t device, const double* cam, int32_t shutter, const int32_t* scanlines, const float* object_points,
                          const float* image_points, int32_t n, const double* poses, float reprojection_error, uint8_t* inlier_mask);
 
+/* == the start poses of the global-shutter RANSAC hypotheses (include/rsba/solve_rs_pnp.hpp: solveGsPnPRansac, what cv::solvePnPRansac
+ * does at solveRSpnp.cpp:437-449 and VideoSfMHandler.cc:715-730): pnp_detail::dlt_pose for every subset, on the device.  The image points
+ * are undistorted and normalised once per call (pnp_detail::normalised_point), then one lane per subset runs the whole of dlt_pose: the
+ * collinear / planar tests on the 3 x 3 scatter, the homography of a planar target or the 12 x 12 Gram matrix with its two gap tests, the
+ * nearest rotation, the pose.  m >= 6.  poses_out are rsba's 6-vectors.
+ * status[t]: 0 declined (degenerate subset; poses_out[t] untouched), 1 general DLT, 2 planar branch. */
+int32_t rsba_pnp_dlt(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                     const int32_t* subsets, int32_t m, int32_t num_tasks, double* poses_out /* [num_tasks][6] */, uint8_t* status);
+
+/* the whole global-shutter hypothesis batch of solveGsPnPRansac in one call: normalise, DLT, the refinement of
+ * rsba_pnp_tasks with shutter GLOBAL from each subset's DLT pose (both pose slots the same), inlier counts.
+ * The start poses never leave the device. status[t]: 0 declined by the DLT, 1 refined and usable, 2 refinement
+ * unusable (poses_out[t] = the DLT pose). final_cost / num_inliers may be NULL. */
+int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                               const int32_t* subsets, int32_t m, int32_t num_tasks, int32_t max_num_iterations, float reprojection_error,
+                               double* poses_out /* [num_tasks][6] */, uint8_t* status, double* final_cost, int32_t* num_inliers);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

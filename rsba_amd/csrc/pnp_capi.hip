@@ -1,5 +1,5 @@
-// C-ABI of the RS-PnP hypothesis path (include/rsba_amd.h: rsba_pnp_tasks, rsba_pnp_inliers).  Host-side glue only:
-// staging of the caller's arrays and the launches; every number comes from kernels_pnp.hip.
+// C-ABI of the RS-PnP hypothesis path (include/rsba_amd.h: rsba_pnp_tasks, rsba_pnp_inliers, rsba_pnp_dlt, rsba_pnp_gs_hypotheses).
+// Host-side glue only: staging of the caller's arrays and the launches; every number comes from kernels_pnp.hip / kernels_pnp_dlt.hip.
 #include "../../include/rsba_amd.h"
 
 #include <string>
@@ -110,5 +110,114 @@ extern "C" int32_t rsba_pnp_inliers(int32_t device, const double* cam, int32_t s
   PNP_TRY(B.alloc(&d_mask, (size_t)n));
   PNP_TRY(launch_pnp_inliers(A, d_poses, d_mask, nullptr));
   PNP_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+  return RSBA_OK;
+}
+
+namespace {
+
+// the argument checks rsba_pnp_dlt and rsba_pnp_gs_hypotheses share (the codes rsba_pnp_tasks returns for the same mistakes)
+int32_t check_dlt_arguments(const double* cam, const float* object_points, const float* image_points, int32_t n, const int32_t* subsets, int32_t m,
+                            int32_t num_tasks, const double* poses_out, const uint8_t* status) {
+  if (!cam || !object_points || !image_points || !subsets || !poses_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n <= 0 || m < 6 || n < m || num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (a DLT subset has at least 6 points, n >= m)");
+  for (size_t k = 0; k < (size_t)num_tasks * m; ++k)
+    if (subsets[k] < 0 || subsets[k] >= n) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "subset index out of range");
+  return RSBA_OK;
+}
+
+// upload, normalise, DLT: D.poses_out / D.status stay on the device
+int32_t run_dlt(DeviceBuffers& B, PnpDltArgs& D, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                const int32_t* subsets, int32_t m, int32_t num_tasks) {
+  for (int k = 0; k < 9; ++k) D.cam[k] = cam[k];
+  D.n = n; D.m = m; D.num_tasks = num_tasks;
+  PNP_TRY(B.upload(&D.object_points, object_points, (size_t)n * 3));
+  PNP_TRY(B.upload(&D.image_points, image_points, (size_t)n * 2));
+  PNP_TRY(B.upload(&D.subsets, subsets, (size_t)num_tasks * m));
+  PNP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
+  PNP_TRY(B.alloc(&D.poses_out, (size_t)num_tasks * 6));
+  PNP_TRY(B.alloc(&D.status, (size_t)num_tasks));
+  PNP_TRY(hipMemset(D.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  PNP_TRY(launch_pnp_normalise(D, nullptr));
+  PNP_TRY(launch_pnp_dlt(D, nullptr));
+  return RSBA_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t rsba_pnp_dlt(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                                const int32_t* subsets, int32_t m, int32_t num_tasks, double* poses_out, uint8_t* status) {
+  int32_t rc = check_dlt_arguments(cam, object_points, image_points, n, subsets, m, num_tasks, poses_out, status);
+  if (rc) return rc;
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  PnpDltArgs D{};
+  if ((rc = run_dlt(B, D, cam, object_points, image_points, n, subsets, m, num_tasks))) return rc;
+  std::vector<double> poses((size_t)num_tasks * 6);
+  std::vector<uint8_t> st((size_t)num_tasks);
+  PNP_TRY(hipMemcpy(poses.data(), D.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+  PNP_TRY(hipMemcpy(st.data(), D.status, st.size(), hipMemcpyDeviceToHost));
+  for (int32_t t = 0; t < num_tasks; ++t) {
+    status[t] = st[(size_t)t];
+    if (st[(size_t)t]) for (int k = 0; k < 6; ++k) poses_out[(size_t)t * 6 + k] = poses[(size_t)t * 6 + k];
+  }
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                                          const int32_t* subsets, int32_t m, int32_t num_tasks, int32_t max_num_iterations, float reprojection_error,
+                                          double* poses_out, uint8_t* status, double* final_cost, int32_t* num_inliers) {
+  int32_t rc = check_dlt_arguments(cam, object_points, image_points, n, subsets, m, num_tasks, poses_out, status);
+  if (rc) return rc;
+  if (max_num_iterations < 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (max_num_iterations < 0)");
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  PnpDltArgs D{};
+  if ((rc = run_dlt(B, D, cam, object_points, image_points, n, subsets, m, num_tasks))) return rc;
+  // which subsets the DLT accepted: one byte per subset comes back; the poses stay where they are
+  std::vector<uint8_t> dlt_status((size_t)num_tasks);
+  PNP_TRY(hipMemcpy(dlt_status.data(), D.status, dlt_status.size(), hipMemcpyDeviceToHost));
+  std::vector<int32_t> map;
+  for (int32_t t = 0; t < num_tasks; ++t) if (dlt_status[(size_t)t]) map.push_back(t);
+  const int32_t count = (int32_t)map.size();
+  std::vector<double> poses((size_t)count * 12), cost((size_t)count);
+  std::vector<uint8_t> st((size_t)count);
+  std::vector<int32_t> inl((size_t)count);
+  if (count > 0) {
+    PnpArgs A{};
+    const int32_t scanlines[2] = {0, 1};
+    if ((rc = fill_camera(A, cam, 0 /* GLOBAL */, scanlines, reprojection_error))) return rc;
+    A.n = n; A.m = m; A.num_tasks = count; A.init_stride = 12; A.max_num_iterations = max_num_iterations; A.drop_coincident = 0;
+    A.object_points = D.object_points; A.image_points = D.image_points;
+    const int32_t* d_map = nullptr; int32_t* d_subsets = nullptr; double* d_init = nullptr;
+    PNP_TRY(B.upload(&d_map, map.data(), (size_t)count));
+    PNP_TRY(B.alloc(&d_subsets, (size_t)count * m));
+    PNP_TRY(B.alloc(&d_init, (size_t)count * 12));
+    PNP_TRY(launch_pnp_compact(d_map, count, m, D.subsets, D.poses_out, d_subsets, d_init, nullptr));
+    A.subsets = d_subsets; A.init_poses = d_init;
+    PNP_TRY(B.alloc(&A.poses_out, (size_t)count * 12));
+    PNP_TRY(B.alloc(&A.status, (size_t)count));
+    PNP_TRY(B.alloc(&A.final_cost, (size_t)count));
+    PNP_TRY(B.alloc(&A.num_inliers, (size_t)count));
+    PNP_TRY(hipMemset(A.poses_out, 0, (size_t)count * 12 * sizeof(double)));
+    PNP_TRY(hipMemset(A.final_cost, 0, (size_t)count * sizeof(double)));
+    PNP_TRY(hipMemset(A.num_inliers, 0, (size_t)count * sizeof(int32_t)));
+    PNP_TRY(launch_pnp_tasks(A, nullptr));
+    PNP_TRY(hipMemcpy(poses.data(), A.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+    PNP_TRY(hipMemcpy(st.data(), A.status, st.size(), hipMemcpyDeviceToHost));
+    PNP_TRY(hipMemcpy(cost.data(), A.final_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost));
+    PNP_TRY(hipMemcpy(inl.data(), A.num_inliers, inl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  for (int32_t t = 0; t < num_tasks; ++t) {
+    status[t] = 0;
+    if (final_cost) final_cost[t] = 0.0;
+    if (num_inliers) num_inliers[t] = 0;
+  }
+  for (int32_t j = 0; j < count; ++j) {
+    const size_t t = (size_t)map[(size_t)j];
+    for (int k = 0; k < 6; ++k) poses_out[t * 6 + k] = poses[(size_t)j * 12 + k];
+    status[t] = st[(size_t)j];
+    if (final_cost) final_cost[t] = cost[(size_t)j];
+    if (num_inliers) num_inliers[t] = inl[(size_t)j];
+  }
   return RSBA_OK;
 }

@@ -20,6 +20,23 @@ struct PnpArgs {
   int32_t* num_inliers;          // [num_tasks]
 };
 
+// Arguments of the DLT start-pose kernels (kernels_pnp_dlt.hip)
+struct PnpDltArgs {
+  double cam[9];
+  int n, m, num_tasks;
+  const float* object_points;    // [n][3]
+  const float* image_points;     // [n][2]
+  const int32_t* subsets;        // [num_tasks][m]
+  double* normalised;            // [n][2] undistorted, normalised image points: written by the normalise kernel, read by the DLT kernel
+  double* poses_out;             // [num_tasks][6]; declined slots are not written
+  uint8_t* status;               // [num_tasks] 0 declined, 1 general DLT, 2 planar branch
+};
+
+hipError_t launch_pnp_normalise(const PnpDltArgs& args, hipStream_t st);
+hipError_t launch_pnp_dlt(const PnpDltArgs& args, hipStream_t st);
+// subsets_out[j] = subsets[map[j]], init_out[j] = (dlt_poses[map[j]], dlt_poses[map[j]]) for j < count
+hipError_t launch_pnp_compact(const int32_t* map, int count, int m, const int32_t* subsets, const double* dlt_poses, int32_t* subsets_out,
+                              double* init_out, hipStream_t st);
 hipError_t launch_pnp_tasks(const PnpArgs& args, hipStream_t st);
 hipError_t launch_pnp_inliers(const PnpArgs& args, const double* poses, uint8_t* mask, hipStream_t st);
 
