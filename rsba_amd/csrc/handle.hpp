@@ -8,7 +8,7 @@
 #include "../../include/rsba_amd.h"
 #include "device_state.hpp"
 
-namespace rsba { struct Solver; }
+namespace rsba { struct Solver; }   // (solver.hpp)
 
 struct rsba_handle {
   int device = 0;
@@ -55,7 +55,7 @@ struct rsba_handle {
 // internal (not exported through the C header)
 int32_t rsba_set_error(int32_t code, const char* msg);
 int32_t rsba_gradient(rsba_handle* h, double* gradient_host);
-void rsba_destroy_solver(rsba_handle* h);
+void rsba_destroy_solver(rsba_handle* h);   // solver_plan.hip
 int32_t rsba_solver_loss_changed(rsba_handle* h);   // solver.hip: rsba_set_loss replaced the loss of a handle that has a plan
-void rsba_covariance_invalidate(rsba_handle* h);   // solver.hip: the parameters or the problem changed — the getters of rsba_covariance_compute refuse until the next compute
-void rsba_release_plan_scratch();   // solver.hip: the symbolic phase's host scratch (kept across handles)
+void rsba_covariance_invalidate(rsba_handle* h);   // solver_cov.hip: the parameters or the problem changed — the getters of rsba_covariance_compute refuse until the next compute
+void rsba_release_plan_scratch();   // solver_plan.hip: the symbolic phase's host scratch (kept across handles)

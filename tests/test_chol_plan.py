@@ -120,7 +120,7 @@ class Cells:
 
 
 def replay(p, cells, tasks, launch, two_rhs):
-    """launch: "all" (the replicated plan), "a" / "b" (the two launches of a sharded plan: plan_a / plan_b of solver.hip)."""
+    """launch: "all" (the replicated plan), "a" / "b" (the two launches of a sharded plan: plan_a / plan_b of solver.hpp, filled by solver_plan.hip)."""
     diag_info = p["diag_info_sh"] if launch == "b" else p["diag_info"]
     sub_info = p["sub_info_sh"] if launch == "b" else p["sub_info"]
     fwd = {"all": p["fwd_full"], "a": p["fwd_a"], "b": p["fwd_b"]}[launch]

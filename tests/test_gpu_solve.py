@@ -597,6 +597,7 @@ def test_the_large_problem_path_of_the_symbolic_phase_builds_the_same_plan(capi,
     as long as the list instead of 4 nt^2 bytes each).  RSBA_PLAN_LISTED_KEYS=1 takes that path at any size: same plan figures, and a
     solve whose every bit is the same."""
     out = {}
+    monkeypatch.setenv("RSBA_PLAN_DEVICE", "0")     # (the switch is read by the HOST entry passes only: a calibrated scene plans on the device otherwise)
     for mode in ("0", "1"):
         monkeypatch.delenv("RSBA_PLAN_LISTED_KEYS", raising=False)
         if mode == "1":
@@ -609,6 +610,53 @@ def test_the_large_problem_path_of_the_symbolic_phase_builds_the_same_plan(capi,
     assert out["0"][4] == out["1"][4]
     assert out["0"][0] == out["1"][0] and out["0"][1] == out["1"][1]
     assert np.array_equal(out["0"][2], out["1"][2]) and np.array_equal(out["0"][3], out["1"][3])
+
+
+_HOST_PLAN_ON_ONE_THREAD = {}   # scene -> the run on one thread, shared by the cases that compare against it
+
+
+@pytest.mark.parametrize("case", ["threads_4", "threads_4_listed_keys", "per_frame_intrinsics_threads_4"])
+def test_the_threaded_host_passes_of_the_symbolic_phase_build_the_same_plan(capi, monkeypatch, case):
+    """The host passes of the symbolic phase (solver_plan.hip: lists_on_host) run on several threads from N >= 200 000 observations (the
+    counting sort of the slots) and M >= 4 096 points (the group walk, the entry counters and cursors) on, and promise lists "exactly
+    as from one thread".  RSBA_PLAN_DEVICE=0 keeps the passes on the host; RSBA_PLAN_THREADS=1 against 4, and against 4 with the listed
+    tile pairs of the large-problem path: same plan figures, and a 5-iteration solve equal in every bit of cost trace, poses and
+    points.  The scene of 60 frames and 12 000 points has 211 052 observations — just above both thresholds.  Several intrinsics blocks
+    (per-frame f.cam) are the one problem class that always plans on the host: the layout of test_per_frame_intrinsics_blocks_in_the_solve
+    with 4 096 points, as many as the threaded group and entry passes ask for."""
+    def problem():
+        if not case.startswith("per_frame_intrinsics"):
+            p = small_scene(frames=60, points=12000, seed=4)
+            assert p.num_observations == 211052
+            return p
+        p = small_scene(frames=16, points=4096, seed=57, outlier_ratio=0.03)
+        p.calibrated = False
+        p.huber_a = 2.0
+        rng = np.random.default_rng(3)
+        ni = p.num_frames
+        p.intrinsics = np.tile(p.intrinsics[:1], (ni, 1)) * (1.0 + 1e-3 * rng.normal(size=(ni, 9)) * np.array([[1, 1, 20, 20, 10, 10, 10, 0.5, 0.5]]))
+        p.frame_intrinsics = np.arange(ni, dtype=np.int32)
+        return p
+    keys = ("tiles", "factor_tiles", "levels", "tasks", "schur_entries", "schur_chunks", "schur_block_products", "schur_groups", "schur_group_bytes", "schur_factored_groups", "schur_mfma_issued")
+    def run(threads, listed):
+        monkeypatch.setenv("RSBA_PLAN_DEVICE", "0")
+        monkeypatch.setenv("RSBA_PLAN_THREADS", threads)
+        monkeypatch.delenv("RSBA_PLAN_LISTED_KEYS", raising=False)
+        if listed:
+            monkeypatch.setenv("RSBA_PLAN_LISTED_KEYS", "1")
+        p = problem()
+        with capi.DeviceProblem(p) as dp:
+            s, tr = dp.solve(capi.default_options(max_num_iterations=5))
+            st = dp.plan_stats()
+        return (s.final_cost, s.num_residual_blocks_reduced, [t.cost for t in tr], p.poses.copy(), p.points.copy(), p.intrinsics.copy(), {k: st[k] for k in keys})
+    scene = "per_frame" if case.startswith("per_frame_intrinsics") else "calibrated"
+    if scene not in _HOST_PLAN_ON_ONE_THREAD:
+        _HOST_PLAN_ON_ONE_THREAD[scene] = run("1", False)
+    a, b = _HOST_PLAN_ON_ONE_THREAD[scene], run("4", case.endswith("listed_keys"))
+    assert len(a[2]) >= 2
+    assert a[6] == b[6], (a[6], b[6])
+    assert a[0] == b[0] and a[1] == b[1] and a[2] == b[2]
+    assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])
 
 
 def test_parameter_arrays_assigned_after_create_are_copied_into_the_bound_ones(capi):
