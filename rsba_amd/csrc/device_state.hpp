@@ -87,7 +87,7 @@ struct DeviceProblem {
   double loss_a, loss_b, loss_c, loss_scale;   // a; the constants b, c of the loss' form (TOLERANT: its parameter b, and c); ScaledLoss' factor
 };
 // Trust-region control on the device: the scalars of Ceres' TrustRegionMinimizer loop live in HBM, a single-thread
-// kernel takes its decisions (kernels_normal.hip: lm_decide_*), and the kernels of an iteration look at them instead of waiting for
+// kernel takes its decisions (kernels_lm.hip: lm_decide_*), and the kernels of an iteration look at them instead of waiting for
 // the host: the host enqueues iterations AHEAD and reads the state of each from a slot of host memory the last kernel of the iteration
 // writes it to (stamped with the iteration's sequence number: no event, no copy in the stream).
 enum LmCtlSlot : int {

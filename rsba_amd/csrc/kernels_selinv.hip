@@ -23,10 +23,8 @@
 // are restated (Acc: the same instruction, the same lane (r, g) -> rows g + 4 v of column r layout of the result) over two LDS tiles.
 //
 // cov_point_kernel: the 3 x 3 covariance block of a point from Sigma (see there).
-#include "solver_state.hpp"
-#include <type_traits>
-
-#include "lm_record.hpp"
+#include "pass_common.hpp"
+#include "slot_record.hpp"
 
 namespace rsba {
 
@@ -194,16 +192,12 @@ struct CovPointArgs {
   const double* Sigma; const int32_t* tmap; const double* v; double border_scale;
   const int32_t* points; const double2* slot_xy; double* out; int* missing;
 };
+// the record of slot s (slot_record.hpp: the point-side passes' own) and rows[]: where its camera-side columns sit in Sigma
 template <bool CAL, int P, bool GEN>
 __device__ __forceinline__ void cov_slot_record(const DeviceProblem& dp, const SolverDev& sv, const double2* slot_xy, int64_t s, ObsOut<CAL, P>& o, int rows[(CAL ? 0 : 9) + 6 * P]) {
   constexpr int CD = 6 * P, OP = CAL ? 0 : 9;
-  const int frame = sv.slot_frame[s], point = sv.slot_point[s];
-  const double2 xy = slot_xy[s];
-  double pose[CD], psc[CD];
-#pragma unroll
-  for (int k = 0; k < CD; ++k) { pose[k] = dp.poses[(size_t)frame * CD + k]; psc[k] = dp.scale_pose[(size_t)frame * CD + k]; }
-  double half_rho; bool dropped;
-  lm_observation<CAL, P, GEN>(dp, frame, point, xy.x, xy.y, pose, psc, o, half_rho, dropped);
+  int frame, point;
+  slot_record<CAL, P, GEN>(dp, sv, slot_xy, s, o, frame, point);
   if (!CAL) {
     const int r0 = (sv.F + (sv.NIB > 1 ? dp.frame_intr[frame] : 0) * sv.NPF) * CD;
 #pragma unroll
@@ -302,12 +296,9 @@ hipError_t launch_cov_points(const DeviceProblem& dp, const SolverDev& sv, const
                              int64_t n, const double2* slot_xy, double* out, int* missing, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const CovPointArgs a{Sigma, tmap, v, border_scale, points, slot_xy, out, missing};
-  auto go = [&](auto cal, auto two, auto gen) {
+  with_record_variant(dp, sv, [&](auto cal, auto two, auto gen) {
     hipLaunchKernelGGL((cov_point_kernel<decltype(cal)::value, decltype(two)::value ? 2 : 1, decltype(gen)::value>), dim3((unsigned)n), dim3(64), 0, st, dp, sv, a);
-  };
-  auto by_gen = [&](auto cal, auto two) { if (dp.loss_general) go(cal, two, std::true_type{}); else go(cal, two, std::false_type{}); };
-  auto by_p = [&](auto cal) { if (sv.CD == 12) by_gen(cal, std::true_type{}); else by_gen(cal, std::false_type{}); };
-  if (dp.calibrated) by_p(std::true_type{}); else by_p(std::false_type{});
+  });
   return hipGetLastError();
 }
 

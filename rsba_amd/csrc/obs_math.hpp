@@ -33,7 +33,7 @@ struct ObsOut {
   double J[2][K];
   bool ok;
   // P == 2, WANT_J: the block BEFORE the (1 - tau) / tau scaling — the 2 x 6 Jacobian with respect to the interpolated pose
-  // [d/dr | d/dt] — and tau itself: the factored P records of the point elimination (kernels_normal.hip, project_rc_kernel) store
+  // [d/dr | d/dt] — and tau itself: the factored P records of the point elimination (kernels_point.hip, project_rc_kernel) store
   // Jq^T Jp L^-T once per observation instead of its two scaled copies.  Dead code wherever nobody reads them.
   double Jq[2][6];
   double tau;

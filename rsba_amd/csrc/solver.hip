@@ -688,7 +688,7 @@ int32_t LmRun::initial_evaluation() {
 // kernels of an iteration read the radius there and skip themselves where the host form would not have launched them (a rejected
 // candidate is not linearised).  What the reference calls per frame — windowedBA over ~100 cameras (VideoSfMClient.cc:241-246) —
 // is where this counts: an iteration there is 0.5 ms, and the host form's 22 dependent launches, two read-backs and their gaps were
-// 0.09 ms of it.  Here an iteration is 13 launches on this stream (the small steps share launches: kernels_normal.hip) and no wait.
+// 0.09 ms of it.  Here an iteration is 13 launches on this stream (the small steps share launches: kernels_lm.hip) and no wait.
 // Every problem this call takes, on one rank or several (every rank takes the same form: settled with the problem-size exchange) — rounds 3 - 6
 // added them kind by kind: motion priors, a free interFrameRatio, GoodPosePrior blocks, the SphericalPrior, several intrinsics blocks (their
 // candidates' records go to a second set), GoodPosePrior blocks on several ranks.  What goes through the host form: phase timing, a rank that
@@ -702,7 +702,7 @@ bool LmRun::choose_device_loop() {
 }
 
 // One iteration of the device-side loop, enqueued: thirteen launches on this stream; the steps the host form spreads over twenty-two, in its
-// order: kernels_normal.hip, "the same steps in fewer launches".  The diagonal's clamp rides in the point factor's launch — after a rejected
+// order: kernels_lm.hip, "the same steps in fewer launches".  The diagonal's clamp rides in the point factor's launch — after a rejected
 // step it recomputes what is there.
 int32_t LmRun::enqueue_device_iteration(const LmRules& R, int cap, int enqueued) {
   int32_t rc;

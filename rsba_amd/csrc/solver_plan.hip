@@ -989,7 +989,7 @@ int32_t PlanBuild::uploads() {
   up->upload_const(&sv.tp_trans, tp_trans);
   up->upload_const(&sv.tp_add, tp_add);
   {
-    // one 64-byte line per pair for the merge kernel (kernels_normal.hip, PairDesc): what it used to collect from five arrays in two dependent rounds
+    // one 64-byte line per pair for the merge kernel (kernels_schur.hip, PairDesc): what it used to collect from five arrays in two dependent rounds
     std::vector<int32_t> tp_desc((size_t)ntp * 16, 0);
     for (int t = 0; t < ntp; ++t) {
       int32_t* d = tp_desc.data() + (size_t)t * 16;

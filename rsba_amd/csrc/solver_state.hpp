@@ -59,11 +59,11 @@ struct SolverDev {
   const double2* slot_xy;       // [N] observations in slot order — calibrated problems only: their point-side passes recompute the records (lm_record.hpp); null = records in dp.rec
   const uint32_t* slot_gpos;    // [N + virtual] where the slot's P record goes: element offset of its group in Pm (a multiple of 16) | position of its frame in the tile << 1 | kind of the group (bit 0: factored)
   int64_t ngroups;              // (point, tile, layer) groups: each owns one block of Pm — kGroupFull doubles ([3][kTile]) or, a two-pose frame tile of a problem that recomputes
-                                //   its records, kGroupFactored (the 6-row factor per frame + tau: see kernels_normal.hip) — one more, all zero, sits behind the last: padding entries of the Schur chunks
+                                //   its records, kGroupFactored (the 6-row factor per frame + tau: see kernels_point.hip, project_rc_kernel) — one more, all zero, sits behind the last: padding entries of the Schur chunks
   uint32_t zero_off;            // element offset of that all-zero group
   const uint8_t* tile_factored; // [nt] 1 = the groups of this frame tile are stored factored (null: none is)
-  int fused_sweep;              // 1 = the projection pass and the virtual-record sweep of the shared intrinsics block are ONE launch (kernels_normal.hip, virtual_project_rc_kernel)
-  int all_real_factored;        // 1 = every tile that holds a real frame is stored factored: the projection pass stages 19 doubles per slot instead of 36 (kernels_normal.hip, project_rc_kernel)
+  int fused_sweep;              // 1 = the projection pass and the virtual-record sweep of the shared intrinsics block are ONE launch (kernels_point.hip, virtual_project_rc_kernel)
+  int all_real_factored;        // 1 = every tile that holds a real frame is stored factored: the projection pass stages 19 doubles per slot instead of 36 (kernels_point.hip, project_rc_kernel)
   int lerp_rot;                 // interpolateRotation of a rolling-shutter model: the rotation rows of a factored group carry (1 - tau) / tau like the translation rows (else 1 / 0)
   const uint16_t* ent_mask;     // [nent] bit 3 I + J: block rows 16 I .. of the I-side group and 16 J .. of the J-side group both contain a frame that sees the point
   const int32_t* ent_pt;        // [nent] point index; top bit set = the entry carries the rhs term P z
@@ -75,7 +75,7 @@ struct SolverDev {
   const int64_t* chunk_e0;      // [nchunk] first entry of the chunk
   const int32_t* chunk_n;       // [nchunk] entries in the chunk (<= kSchurChunk)
   const int4* chunk_info;       // [nchunk] the same in ONE 16-byte read: {first entry (low, high word), entries, bit 0 = a tile paired with itself | bit 1 / 2 = I / J side stored factored}
-  unsigned* schur_next;         // [8][16] next list position of every XCD's eighth of the chunk list (the persistent form of the kernel: kernels_normal.hip) | [128] workgroups done
+  unsigned* schur_next;         // [8][16] next list position of every XCD's eighth of the chunk list (the persistent form of the kernel: kernels_schur.hip) | [128] workgroups done
   const int32_t* tp_chunk0;     // [ntp+1] range of each tile pair in tp_chunk_list
   const int32_t* tp_chunk_list; // chunk ids of each tile pair, in entry order (heads of pre-merged groups for very long lists)
   int npremerge;                // groups of chunks summed ahead of the merge
@@ -217,7 +217,9 @@ hipError_t launch_cov_points(const DeviceProblem& dp, const SolverDev& sv, const
                              int64_t n, const double2* slot_xy, double* out, int* missing, hipStream_t st);
 hipError_t launch_cov_gather(const double* Sigma, const int32_t* desc, int64_t n, int dim, double* out, hipStream_t st);   // desc [n][8]: kernels_selinv.hip
 
-// kernels_normal.hip
+// the normal equations, by pass: kernels_camera.hip (camera blocks, scales, diagonal, gradient maximum, point factors), kernels_point.hip
+// (point blocks, P records, virtual records, point steps), kernels_schur.hip (the reduced camera system), kernels_lm.hip (reductions, candidate,
+// trust-region control, pack / unpack of the linearisation), kernels_exchange.hip (sharded solve)
 hipError_t launch_camera_blocks(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st, bool take_candidate = false, bool padding_is_zero = false);   // take_candidate: launch_lm_take_candidate's copy rides along
 hipError_t launch_point_blocks(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st);
 hipError_t launch_slot_xy(const DeviceProblem& dp, double2* slot_xy, hipStream_t st);   // slot_xy[obs_slot[i]] = xy[i]
@@ -229,7 +231,7 @@ hipError_t launch_project(const DeviceProblem& dp, const SolverDev& sv, hipStrea
 bool project_covers_virtual_records(const DeviceProblem& dp, const SolverDev& sv);   // launch_project runs the fused sweep: launch_virtual_records has nothing left to do
 hipError_t launch_clear_system(const SolverDev& sv, hipStream_t st);   // S = 0 (fill tiles start from zero)
 hipError_t launch_schur_blocks(const DeviceProblem& dp, const SolverDev& sv, double radius, hipStream_t st);
-// sharded factorisation: the exchange between its two launches (kernels_normal.hip)
+// sharded factorisation: the exchange between its two launches (kernels_exchange.hip)
 hipError_t launch_top_assemble(const SolverDev& sv, const int32_t* slots, const int32_t* info, const int32_t* asm_ptr, const int32_t* asm_list, const int32_t* top_tiles, int ntop_slots, double* buf, hipStream_t st);
 hipError_t launch_top_unpack(const SolverDev& sv, const int32_t* slots, const int32_t* info, const int32_t* top_tiles, int ntop_slots, const double* buf, hipStream_t st);
 hipError_t launch_step_rows(const double* yv, const uint8_t* row_mine, int64_t npad, double* ybuf, hipStream_t st);
@@ -238,7 +240,7 @@ hipError_t launch_back_substitute(const DeviceProblem& dp, const SolverDev& sv, 
 hipError_t launch_model_cost_change(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st);      // -> scalars[kModelCostChange]
 hipError_t launch_candidate(const DeviceProblem& dp, const SolverDev& sv, hipStream_t st);              // trial params, |step|^2, |x|^2
 // trust-region control on the device: the two decisions of an iteration (after the candidate's evaluation; after an accepted step's
-// linearisation) and the hand-over of an accepted candidate (kernels_normal.hip)
+// linearisation) and the hand-over of an accepted candidate (kernels_lm.hip)
 struct LmRules { int32_t max_num_iterations, max_num_consecutive_invalid_steps; double max_trust_region_radius, min_trust_region_radius, min_relative_decrease, function_tolerance, gradient_tolerance, parameter_tolerance; };
 hipError_t launch_lm_decide_step(const SolverDev& sv, double* ctl, const LmRules& rules, rsba_iteration* trace, int trace_cap, hipStream_t st);
 hipError_t launch_lm_decide_gradient(const SolverDev& sv, double* ctl, const LmRules& rules, rsba_iteration* trace, int trace_cap, hipStream_t st);

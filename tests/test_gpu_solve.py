@@ -730,7 +730,7 @@ def test_the_symbolic_phase_on_the_device_builds_the_same_plan(capi, monkeypatch
 @pytest.mark.parametrize("case", ["c2", "small_intrinsics", "few_chunks"])
 def test_resident_schur_workgroups_leave_the_same_bits_as_a_workgroup_per_chunk(capi, monkeypatch, case):
     """The Schur kernel's default form keeps 512 workgroups resident; each takes chunk after chunk from per-XCD counters (another XCD's
-    when its own eighth of the list is done) with the next chunk's tables loaded under the epilogue (kernels_normal.hip,
+    when its own eighth of the list is done) with the next chunk's tables loaded under the epilogue (kernels_schur.hip,
     schur_tile_kernel).  RSBA_SCHUR_VARIANT=2 launches a workgroup per chunk, as rounds 2 - 4 did.  Which workgroup forms a chunk's
     partial tile must not show: same partial tiles, same merge order, every bit of the solve the same — with more chunks than resident
     workgroups (C2's 453 < 512 exercises the start-up map only; the blocked numbering of the second case makes thousands of small
@@ -766,7 +766,7 @@ def test_resident_schur_workgroups_leave_the_same_bits_as_a_workgroup_per_chunk(
 def test_the_fused_projection_and_virtual_record_sweep_leaves_the_same_bits(capi, monkeypatch, case):
     """A problem with ONE shared intrinsics block whose two-pose frames all sit in factored tiles evaluates every observation once for
     the projection pass (the slots' P records) and the virtual-record sweep of the intrinsics pseudo frames together
-    (kernels_normal.hip, virtual_project_rc_kernel); RSBA_NO_FUSED_SWEEP=1 keeps project_rc_kernel and virtual_records_rc_kernel
+    (kernels_point.hip, virtual_project_rc_kernel); RSBA_NO_FUSED_SWEEP=1 keeps project_rc_kernel and virtual_records_rc_kernel
     apart.  Same expressions in the same order: every bit of the solve the same."""
     def problem():
         p = small_scene(frames=48, points=4000, seed=41, rolling=True)

@@ -2,7 +2,7 @@
 // 2 x 2 block of tile pairs — 36 blocks of 16 x 16, 288 registers, ONE wave per SIMD — keep the fp64 matrix pipe busier than the
 // shipped loop (one tile pair per wave, 9 blocks, two waves per SIMD)?  Both loops here take FACTORED groups (80 doubles: the layout of
 // solver_state.hpp, kGroupFactored) from a buffer of the C4 size (585 k groups, 374 MB) through tables of group offsets staged in LDS,
-// form the operand rows in registers and issue every MFMA behind a scalar test of a mask bit, like kernels_normal.hip: schur_chunk.
+// form the operand rows in registers and issue every MFMA behind a scalar test of a mask bit, like kernels_schur.hip: schur_chunk.
 //   pair  form: per group of four entries 2 sides x 8 loaded doubles -> 27 MFMAs   (1.69 MFMAs per loaded double, 24 fp64 vector ops)
 //   block form: per group of four entries 4 sides x 8 loaded doubles -> 108 MFMAs  (3.38 MFMAs per loaded double, 48 fp64 vector ops)
 // The same number of MFMAs in total.  Prints time, TFLOP/s, cycles per MFMA of a wave and the shader clock inside the loop.
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256, kWaves) void loop_kernel(const double* __restr
     for (int d = 0; d < kDepth; ++d) {
       if (base + d < nq) {
         const unsigned long long m = mym[base + d];
-        // the nine bits of every tile pair once per coordinate: every MFMA tests a bit of its own (kernels_normal.hip: the same bit tested three times is kept as a lane mask)
+        // the nine bits of every tile pair once per coordinate: every MFMA tests a bit of its own (kernels_schur.hip: the same bit tested three times is kept as a lane mask)
         unsigned m27[NX][NX];
 #pragma unroll
         for (int x = 0; x < NX; ++x)
