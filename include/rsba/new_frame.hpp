@@ -9,10 +9,12 @@
 // Same names and argument meaning, with a plain Session& / SfmOptions where the reference takes a session key and its own _opt.  Not
 // here: the PLY dumps, printFrame and the progress lines, the RPC.
 // The global-shutter attempts of solveRsPnP (:713-733) are cv::solvePnPRansac in three flavours (ITERATIVE with the extrinsic guess, EPNP,
-// P3P).  OpenCV is not a dependency and EPnP / P3P are not restated (as solve_rs_pnp.hpp says for the GS half of the RANSAC): the three
-// collapse to two native attempts — the refinement of sampled subsets from the shared guess (rsba_pnp_tasks, shutter GLOBAL), then
-// hypotheses from the direct linear transform computed on the device (solveGsPnPRansac(..., hypotheses_on_device = true)).  This is
-// functionally the reference's, not bitwise.  The rolling-shutter RANSAC (:737-746) is solveRsPnPRansac as everywhere else.
+// P3P without a guess).  OpenCV is not a dependency; the three are three native attempts, each made when the one before found at most
+// four inliers: the refinement of sampled six-point subsets from the shared guess (rsba_pnp_tasks, shutter GLOBAL); hypotheses from the
+// direct linear transform of six points, in EPnP's place (solveGsPnPRansac(..., hypotheses_on_device = true)); hypotheses from the minimal
+// solver, three points and a fourth that chooses (solveGsPnPRansacP3P(..., hypotheses_on_device = true), :726-731).  The first two need six
+// correspondences, the third four: a frame with exactly five — which the reference accepts (:686) — is localised by the third alone.
+// This is functionally the reference's, not bitwise.  The rolling-shutter RANSAC (:737-746) is solveRsPnPRansac as everywhere else.
 // One more difference, on purpose: a frame's priorPoses are copied into its poses (:694-696) AND taken as the start of the solve; the
 // reference copies them and still starts from its epsilon vectors, so the copy never reaches the solver there.
 #pragma once
@@ -105,6 +107,11 @@ inline bool solveRsPnP(Session& sess, const SfmOptions& opt, const int32_t maxIt
     if (inliers <= 4) {                           // no extrinsic guess: hypotheses from the DLT, on the device
       double gs[6];
       const int found = solveGsPnPRansac(pts.data(), obs.data(), n, cam, gs, iterations, threshold, m, seed, device, true);
+      if (found > 4) { inliers = found; pnp_detail::from_pose(gs, rvec, tvec); }
+    }
+    if (inliers <= 4) {                           // :726-731, CV_P3P without a guess: hypotheses from the minimal solver, on the device
+      double gs[6];
+      const int found = solveGsPnPRansacP3P(pts.data(), obs.data(), n, cam, gs, iterations, threshold, seed, device, true);
       if (found > 4) { inliers = found; pnp_detail::from_pose(gs, rvec, tvec); }
     }
     two_starts = false;

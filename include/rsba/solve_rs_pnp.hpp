@@ -258,6 +258,207 @@ inline std::vector<double> normalised_points(const double cam[NUM_CAM_PARAMS], c
   return out;
 }
 
+// ---- the minimal solver of the global-shutter RANSAC (what cv::solvePnPRansac(..., CV_P3P) runs per sample): three points solved, a
+// fourth chooses among the solutions.  The rule is stated in rsba_amd.h (rsba_pnp_p3p); this is its definition and the host path.
+// Formulation: Grunert's ratio substitution.  With depths s1, s2, s3 along the unit bearings j1, j2, j3, sides a = |P2 P3|, b = |P1 P3|,
+// c = |P1 P2| and cos(alpha) = j2.j3, cos(beta) = j1.j3, cos(gamma) = j1.j2, put s2 = u s1, s3 = v s1.  The three cosine laws give
+//   u = N(v) / (2 D(v)),  N = (K - 1) v^2 - 2 K cos(beta) v + (K + 1),  D = cos(gamma) - v cos(alpha),  K = (a^2 - c^2) / b^2,
+// and the quartic F(v) = N^2 - 4 cos(gamma) N D + 4 D^2 (1 - (c^2 / b^2)(v^2 - 2 cos(beta) v + 1)) = 0, whose coefficients are formed by
+// polynomial arithmetic on N and D.  Positive depths mean v in (0, inf): the roots are looked for in t = v / (1 + v) in (0, 1), where
+// F becomes P(t) = sum_i A_i t^i (1 - t)^(4 - i).  Between the roots of P' (themselves isolated between the roots of P'', and those by the
+// root of P''') P is monotonic: each of the four intervals is bisected a fixed 40 times where P changes sign, then polished by two Newton
+// steps on P.  Roots come in ascending t (ascending s3 / s1): that is the root order of the tie rule.
+struct P3pProblem {
+  double P[3][3];       // the three world points
+  double j[3][3];       // their unit bearings
+  double a2, b2, c2;    // squared sides |P2 P3|^2, |P1 P3|^2, |P1 P2|^2
+  double cos_alpha, cos_beta, cos_gamma;   // j2 . j3, j1 . j3, j1 . j2
+  double b;             // |P1 P3|
+  double N[3], D[2];    // N(v) = N[0] + N[1] v + N[2] v^2, D(v) = D[0] + D[1] v
+  double c[5];          // P(t), power basis
+};
+inline void p3p_bearing(double x, double y, double j[3]) {
+  const double inv = 1.0 / std::sqrt(x * x + y * y + 1.0);
+  j[0] = x * inv; j[1] = y * inv; j[2] = inv;
+}
+template <int DEG>
+inline double p3p_eval(const double (&c)[DEG + 1], double t) {
+  double h = c[DEG];
+  for (int k = DEG - 1; k >= 0; --k) h = h * t + c[k];
+  return h;
+}
+// the root of a polynomial that is monotonic on [lo, hi], where it changes sign there; otherwise hi (which keeps breakpoints ordered)
+template <int DEG>
+inline bool p3p_bisect(const double (&c)[DEG + 1], double lo, double hi, double* root) {
+  *root = hi;
+  const bool plo = p3p_eval<DEG>(c, lo) > 0.0, phi = p3p_eval<DEG>(c, hi) > 0.0;
+  if (plo == phi) return false;
+  for (int it = 0; it < 40; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if ((p3p_eval<DEG>(c, mid) > 0.0) == plo) lo = mid; else hi = mid;
+  }
+  *root = 0.5 * (lo + hi);
+  return true;
+}
+// false: two of the three world points coincide, or the three are collinear (smaller singular value of the centred triple below 1e-4 of the
+// larger — on the eigenvalues of the scatter, their squares, that is 1e-8)
+inline bool p3p_setup(const double P[3][3], const double j[3][3], P3pProblem& S) {
+  for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) { S.P[i][k] = P[i][k]; S.j[i][k] = j[i][k]; }
+  const double d12[3] = {P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2]}, d13[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
+  const double d23[3] = {P[2][0] - P[1][0], P[2][1] - P[1][1], P[2][2] - P[1][2]};
+  const double a2 = d23[0] * d23[0] + d23[1] * d23[1] + d23[2] * d23[2], b2 = d13[0] * d13[0] + d13[1] * d13[1] + d13[2] * d13[2];
+  const double c2 = d12[0] * d12[0] + d12[1] * d12[1] + d12[2] * d12[2];
+  if (!(a2 > 0.0) || !(b2 > 0.0) || !(c2 > 0.0)) return false;
+  // the two non-zero eigenvalues of the centred triple's scatter: their sum is (a^2 + b^2 + c^2) / 3, their product |d12 x d13|^2 / 3
+  const double nx = d12[1] * d13[2] - d12[2] * d13[1], ny = d12[2] * d13[0] - d12[0] * d13[2], nz = d12[0] * d13[1] - d12[1] * d13[0];
+  const double tr = (a2 + b2 + c2) / 3.0, prod = (nx * nx + ny * ny + nz * nz) / 3.0;
+  const double big = 0.5 * (tr + std::sqrt(std::fmax(0.0, tr * tr - 4.0 * prod))), small = prod / big;
+  if (!(small > 1e-8 * big)) return false;
+  const double ca = j[1][0] * j[2][0] + j[1][1] * j[2][1] + j[1][2] * j[2][2], cb = j[0][0] * j[2][0] + j[0][1] * j[2][1] + j[0][2] * j[2][2];
+  const double cg = j[0][0] * j[1][0] + j[0][1] * j[1][1] + j[0][2] * j[1][2];
+  const double K = (a2 - c2) / b2, g = c2 / b2;
+  S.a2 = a2; S.b2 = b2; S.c2 = c2; S.cos_alpha = ca; S.cos_beta = cb; S.cos_gamma = cg; S.b = std::sqrt(b2);
+  S.N[0] = K + 1.0; S.N[1] = -2.0 * K * cb; S.N[2] = K - 1.0;
+  S.D[0] = cg; S.D[1] = -ca;
+  const double* n = S.N; const double* d = S.D;
+  const double nn[5] = {n[0] * n[0], 2.0 * n[0] * n[1], 2.0 * n[0] * n[2] + n[1] * n[1], 2.0 * n[1] * n[2], n[2] * n[2]};
+  const double nd[5] = {n[0] * d[0], n[0] * d[1] + n[1] * d[0], n[1] * d[1] + n[2] * d[0], n[2] * d[1], 0.0};
+  const double dd[3] = {d[0] * d[0], 2.0 * d[0] * d[1], d[1] * d[1]}, q[3] = {1.0 - g, 2.0 * g * cb, -g};
+  const double e[5] = {dd[0] * q[0], dd[0] * q[1] + dd[1] * q[0], dd[0] * q[2] + dd[1] * q[1] + dd[2] * q[0], dd[1] * q[2] + dd[2] * q[1], dd[2] * q[2]};
+  double A[5];
+  for (int k = 0; k < 5; ++k) A[k] = nn[k] - 4.0 * cg * nd[k] + 4.0 * e[k];
+  // P(t) = sum_i A_i t^i (1 - t)^(4 - i)
+  S.c[0] = A[0];
+  S.c[1] = A[1] - 4.0 * A[0];
+  S.c[2] = A[2] - 3.0 * A[1] + 6.0 * A[0];
+  S.c[3] = A[3] - 2.0 * A[2] + 3.0 * A[1] - 4.0 * A[0];
+  S.c[4] = A[4] - A[3] + A[2] - A[1] + A[0];
+  return true;
+}
+// the roots of P in (0, 1), ascending
+inline int p3p_roots(const P3pProblem& S, double roots[4]) {
+  const double (&c4)[5] = S.c;
+  const double c3[4] = {c4[1], 2.0 * c4[2], 3.0 * c4[3], 4.0 * c4[4]}, c2[3] = {c4[2], 3.0 * c4[3], 6.0 * c4[4]}, c1[2] = {c4[3], 4.0 * c4[4]};
+  double x1, x2[2], x3[3];
+  p3p_bisect<1>(c1, 0.0, 1.0, &x1);
+  p3p_bisect<2>(c2, 0.0, x1, &x2[0]); p3p_bisect<2>(c2, x1, 1.0, &x2[1]);
+  p3p_bisect<3>(c3, 0.0, x2[0], &x3[0]); p3p_bisect<3>(c3, x2[0], x2[1], &x3[1]); p3p_bisect<3>(c3, x2[1], 1.0, &x3[2]);
+  const double edge[5] = {0.0, x3[0], x3[1], x3[2], 1.0};
+  int count = 0;
+  for (int i = 0; i < 4; ++i) {
+    double t;
+    if (!p3p_bisect<4>(c4, edge[i], edge[i + 1], &t)) continue;
+    for (int it = 0; it < 2; ++it) {   // Newton on P, a step taken only while it stays inside (0, 1)
+      const double p = p3p_eval<4>(c4, t), dp = p3p_eval<3>(c3, t), tn = t - p / dp;
+      if (tn > 0.0 && tn < 1.0) t = tn;
+    }
+    roots[count++] = t;
+  }
+  return count;
+}
+// the depths of one root; false unless all three are positive — above 1e-9 b: a camera centre in a world point is no solution — and finite
+// (D = 0, where u = N / 2D is undefined, drops the root)
+inline bool p3p_depths(const P3pProblem& S, double t, double s[3]) {
+  const double r = 1.0 - t;
+  const double w = std::sqrt(r * r + t * t - 2.0 * t * r * S.cos_beta);
+  const double Nh = S.N[2] * t * t + S.N[1] * t * r + S.N[0] * r * r, Dh = S.D[1] * t + S.D[0] * r;
+  if (!(std::fabs(Dh) > 1e-12) || !(w > 0.0)) return false;
+  s[0] = S.b * r / w; s[1] = S.b * Nh / (2.0 * Dh * w); s[2] = S.b * t / w;
+  const double least = 1e-9 * S.b;
+  return s[0] > least && s[1] > least && s[2] > least && std::isfinite(s[0] + s[1] + s[2]);
+}
+// two Newton steps on the three cosine laws themselves, in the depths: the quartic's coefficients are formed with cancellation, the laws
+// are not, so this is what makes a solution as accurate as its conditioning allows.  false: no longer three positive depths.
+inline bool p3p_polish(const P3pProblem& S, double s[3]) {
+  for (int it = 0; it < 2; ++it) {
+    const double F[3] = {s[1] * s[1] + s[2] * s[2] - 2.0 * s[1] * s[2] * S.cos_alpha - S.a2, s[0] * s[0] + s[2] * s[2] - 2.0 * s[0] * s[2] * S.cos_beta - S.b2,
+                         s[0] * s[0] + s[1] * s[1] - 2.0 * s[0] * s[1] * S.cos_gamma - S.c2};
+    // Jacobian rows (0, p, q), (r, 0, w), (x, y, 0), halved
+    const double p = s[1] - s[2] * S.cos_alpha, q = s[2] - s[1] * S.cos_alpha, r = s[0] - s[2] * S.cos_beta, w = s[2] - s[0] * S.cos_beta;
+    const double x = s[0] - s[1] * S.cos_gamma, y = s[1] - s[0] * S.cos_gamma;
+    const double det = 2.0 * (p * w * x + q * r * y);
+    if (!(std::fabs(det) > 0.0)) break;
+    s[0] -= (-w * y * F[0] + q * y * F[1] + p * w * F[2]) / det;
+    s[1] -= (w * x * F[0] - q * x * F[1] + q * r * F[2]) / det;
+    s[2] -= (r * y * F[0] + p * x * F[1] - p * r * F[2]) / det;
+  }
+  const double least = 1e-9 * S.b;
+  return s[0] > least && s[1] > least && s[2] > least && std::isfinite(s[0] + s[1] + s[2]);
+}
+// the rigid motion that takes P_i onto s_i j_i, through the orthonormal triad of each triangle: x_cam = R X + tvec
+inline void p3p_triad(const double A[3], const double B[3], const double C[3], double e[3][3]) {
+  const double u[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, v[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  const double iu = 1.0 / std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for (int k = 0; k < 3; ++k) e[0][k] = u[k] * iu;
+  const double n[3] = {e[0][1] * v[2] - e[0][2] * v[1], e[0][2] * v[0] - e[0][0] * v[2], e[0][0] * v[1] - e[0][1] * v[0]};
+  const double in = 1.0 / std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  for (int k = 0; k < 3; ++k) e[2][k] = n[k] * in;
+  e[1][0] = e[2][1] * e[0][2] - e[2][2] * e[0][1]; e[1][1] = e[2][2] * e[0][0] - e[2][0] * e[0][2]; e[1][2] = e[2][0] * e[0][1] - e[2][1] * e[0][0];
+}
+inline void p3p_rt(const P3pProblem& S, const double s[3], double R[9], double tvec[3]) {
+  double Q[3][3], e[3][3], f[3][3];
+  for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) Q[i][k] = s[i] * S.j[i][k];
+  p3p_triad(S.P[0], S.P[1], S.P[2], e);
+  p3p_triad(Q[0], Q[1], Q[2], f);
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) R[3 * r + k] = f[0][r] * e[0][k] + f[1][r] * e[1][k] + f[2][r] * e[2][k];
+  for (int r = 0; r < 3; ++r) {
+    const double pc[3] = {(S.P[0][0] + S.P[1][0] + S.P[2][0]) / 3.0, (S.P[0][1] + S.P[1][1] + S.P[2][1]) / 3.0, (S.P[0][2] + S.P[1][2] + S.P[2][2]) / 3.0};
+    tvec[r] = (Q[0][r] + Q[1][r] + Q[2][r]) / 3.0 - (R[3 * r] * pc[0] + R[3 * r + 1] * pc[1] + R[3 * r + 2] * pc[2]);
+  }
+}
+// squared distance between the projection of X and the normalised image point (x, y); false: X is not in front of the camera
+inline bool p3p_fourth(const double R[9], const double tvec[3], const double X[3], double x, double y, double* dist2) {
+  const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + tvec[2];
+  if (!(z > 0.0)) return false;
+  const double dx = (R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + tvec[0]) / z - x, dy = (R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + tvec[1]) / z - y;
+  *dist2 = dx * dx + dy * dy;
+  return std::isfinite(*dist2);
+}
+// rsba pose from the correspondences idx[0..3), chosen by idx[3].  false: declined (pose untouched).  num_solutions (may be null): the
+// admissible solutions — three positive depths and the fourth point in front of the camera.
+inline bool p3p_pose(const float* opoints, const double* normalised, const int32_t idx[4], double pose[6], int* num_solutions = nullptr) {
+  if (num_solutions) *num_solutions = 0;
+  for (int i = 0; i < 4; ++i) for (int k = i + 1; k < 4; ++k) if (idx[i] == idx[k]) return false;
+  double P[3][3], j[3][3];
+  for (int i = 0; i < 3; ++i) {
+    for (int k = 0; k < 3; ++k) P[i][k] = opoints[3 * (size_t)idx[i] + k];
+    p3p_bearing(normalised[2 * (size_t)idx[i]], normalised[2 * (size_t)idx[i] + 1], j[i]);
+  }
+  P3pProblem S;
+  if (!p3p_setup(P, j, S)) return false;
+  const double X4[3] = {opoints[3 * (size_t)idx[3]], opoints[3 * (size_t)idx[3] + 1], opoints[3 * (size_t)idx[3] + 2]};
+  double roots[4], bestR[9], bestT[3], best = 0.0;
+  const int count = p3p_roots(S, roots);
+  int found = 0;
+  for (int i = 0; i < count; ++i) {
+    double s[3], R[9], tvec[3], d2;
+    if (!p3p_depths(S, roots[i], s) || !p3p_polish(S, s)) continue;
+    p3p_rt(S, s, R, tvec);
+    if (!p3p_fourth(R, tvec, X4, normalised[2 * (size_t)idx[3]], normalised[2 * (size_t)idx[3] + 1], &d2)) continue;
+    if (found == 0 || d2 < best) { best = d2; for (int k = 0; k < 9; ++k) bestR[k] = R[k]; for (int k = 0; k < 3; ++k) bestT[k] = tvec[k]; }
+    ++found;
+  }
+  if (found == 0) return false;
+  double out[6];
+  if (!pose_from_rt(bestR, bestT, out)) return false;   // (num_solutions stays 0: a declined subset reports none)
+  for (int k = 0; k < 6; ++k) pose[k] = out[k];
+  if (num_solutions) *num_solutions = found;
+  return true;
+}
+
+// the subsets of solveGsPnPRansac and solveGsPnPRansacP3P: m distinct indices per iteration, from cv::RNG's generator
+inline std::vector<int32_t> distinct_subsets(int n, int m, int iterations, uint64_t rng_state) {
+  Rng gen(rng_state);
+  std::vector<int32_t> out((size_t)iterations * m);
+  for (int it = 0; it < iterations; ++it)
+    for (int k = 0; k < m;) {
+      const int c = gen.uniform(0, n); bool dup = false;
+      for (int j = 0; j < k; ++j) dup = dup || out[(size_t)it * m + j] == c;
+      if (!dup) out[(size_t)it * m + k++] = c;
+    }
+  return out;
+}
+
 }  // namespace pnp_detail
 
 // cv::solvePnP(..., SOLVEPNP_ITERATIVE) as the reference uses it at solveRSpnp.cpp:111-117: DLT over all points, then a
@@ -318,6 +519,51 @@ inline int solveGsPnPRansac(const float* opoints, const float* ipoints, int n, c
     double p[6];
     if (!pnp_detail::dlt_pose(opoints, nrm.data(), pick.data(), m, p)) continue;
     subsets.insert(subsets.end(), pick.begin(), pick.end());
+    inits.insert(inits.end(), p, p + 6); inits.insert(inits.end(), p, p + 6);
+  }
+  const int tasks = (int)(inits.size() / 12);
+  if (tasks == 0) return 0;
+  std::vector<double> poses((size_t)tasks * 12), cost((size_t)tasks);
+  std::vector<uint8_t> status((size_t)tasks);
+  std::vector<int32_t> count((size_t)tasks);
+  const int32_t sl[2] = {0, 1};
+  pnp_detail::check(rsba_pnp_tasks(device, cam, (int32_t)GLOBAL, sl, opoints, ipoints, n, subsets.data(), m, tasks, inits.data(), 12, 5, 0, reprojectionError,
+                                   poses.data(), status.data(), cost.data(), count.data()));
+  int best = -1;
+  for (int t = 0; t < tasks; ++t) if (status[(size_t)t] != 0 && (best < 0 || count[(size_t)t] > count[(size_t)best])) best = t;
+  if (best < 0) return 0;
+  for (int k = 0; k < 6; ++k) pose[k] = poses[(size_t)best * 12 + k];
+  return count[(size_t)best];
+}
+
+// cv::solvePnPRansac(..., CV_P3P) as the reference uses it without a guess at VideoSfMHandler.cc:726-731: four-point samples from the same
+// generator and the same distinct-index sampling as solveGsPnPRansac, the minimal solver's pose per sample (pnp_detail::p3p_pose: three
+// points solved, the fourth chooses), refined and scored like the DLT hypotheses (rsba_pnp_tasks, GLOBAL, 5 iterations, m = 4), the same rule
+// for the winner.  Returns the winner's inliers (0: none found).  hypotheses_on_device: the whole batch in one call (rsba_pnp_gs_hypotheses_p3p).
+inline int solveGsPnPRansacP3P(const float* opoints, const float* ipoints, int n, const double cam[NUM_CAM_PARAMS], double pose[6], int iterationsCount,
+                               float reprojectionError, uint64_t rng_state = 0x9e3779b97f4a7c15ULL, int device = 0, bool hypotheses_on_device = false) {
+  const int m = 4;
+  if (n < m || iterationsCount <= 0) return 0;
+  const std::vector<int32_t> all_subsets = pnp_detail::distinct_subsets(n, m, iterationsCount, rng_state);
+  if (hypotheses_on_device) {
+    std::vector<double> poses((size_t)iterationsCount * 6);
+    std::vector<uint8_t> status((size_t)iterationsCount);
+    std::vector<int32_t> count((size_t)iterationsCount);
+    pnp_detail::check(rsba_pnp_gs_hypotheses_p3p(device, cam, opoints, ipoints, n, all_subsets.data(), iterationsCount, 5, reprojectionError, poses.data(),
+                                                 status.data(), nullptr, count.data()));
+    int best = -1;
+    for (int t = 0; t < iterationsCount; ++t) if (status[(size_t)t] != 0 && (best < 0 || count[(size_t)t] > count[(size_t)best])) best = t;
+    if (best < 0) return 0;
+    for (int k = 0; k < 6; ++k) pose[k] = poses[(size_t)best * 6 + k];
+    return count[(size_t)best];
+  }
+  const std::vector<double> nrm = pnp_detail::normalised_points(cam, ipoints, n);
+  std::vector<int32_t> subsets; std::vector<double> inits;
+  for (int it = 0; it < iterationsCount; ++it) {
+    const int32_t* pick = &all_subsets[(size_t)it * m];
+    double p[6];
+    if (!pnp_detail::p3p_pose(opoints, nrm.data(), pick, p)) continue;
+    subsets.insert(subsets.end(), pick, pick + m);
     inits.insert(inits.end(), p, p + 6); inits.insert(inits.end(), p, p + 6);
   }
   const int tasks = (int)(inits.size() / 12);

@@ -514,6 +514,44 @@ int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* o
                                const int32_t* subsets, int32_t m, int32_t num_tasks, int32_t max_num_iterations, float reprojection_error,
                                double* poses_out /* [num_tasks][6] */, uint8_t* status, double* final_cost, int32_t* num_inliers);
 
+/* == the minimal solver of the global-shutter RANSAC (what cv::solvePnPRansac(..., CV_P3P) runs per sample, VideoSfMHandler.cc:726-731;
+ * OpenCV is not in the reference tree, so this text is the definition; include/rsba/solve_rs_pnp.hpp: pnp_detail::p3p_pose is its host form).
+ * A subset has four indices: the first three are solved, the fourth chooses among the solutions.
+ *   Inputs.  Image points undistorted and normalised as pnp_detail::normalised_point does; bearings j_i = (x, y, 1) / |(x, y, 1)|.
+ *   Solve.  Grunert's formulation: with depths s_i along j_i, sides a = |P2 P3|, b = |P1 P3|, c = |P1 P2| and the cosines of the angles
+ *     between the bearings, s2 = u s1, s3 = v s1 turn the three cosine laws into u = N(v) / (2 D(v)), D(v) = j1.j2 - v j2.j3, and a
+ *     quartic in v.  All of its roots with three positive depths are looked for, in t = v / (1 + v) in (0, 1): the four intervals between
+ *     the roots of the derivative (found the same way from the second and third derivatives) are bisected 40 times each where the
+ *     quartic changes sign, every root is polished by two Newton steps.  Every loop has a fixed bound.
+ *     The quartic loses its leading coefficient when the angle under which the camera sees P2 P3 equals the triangle's angle at P1 or its
+ *     supplement (the camera centre on the surface the circumcircle sweeps when turned about P2 P3): the lost root is v = infinity,
+ *     s1 = 0 — the camera centre in P1, not a solution with positive depths.  In t that root is t = 1, outside the open interval, and
+ *     nothing is divided by the leading coefficient: the remaining roots are found as everywhere else.
+ *     u divides by D(v), which vanishes where s1 j1.j2 = s3 j2.j3 (P1 and P3 project onto the second ray at the same point); a root
+ *     with |D| <= 1e-12 (in units of s1 + s3) is dropped.
+ *   Pose per solution.  The rigid motion that takes the three world points onto s_i j_i: the two triangles are congruent, so it is
+ *     F E^T for their orthonormal triads (first edge, normal, their cross product) and maps centroid to centroid; converted to
+ *     rsba's 6-vector by pnp_detail::pose_from_rt.
+ *   Choice.  A solution is admissible when its three depths are positive (above 1e-9 b: the camera centre in a world point, where the
+ *     lost root ends up under rounding, is no solution) and it puts the fourth point in front of the camera (z > 0).
+ *     Among the admissible ones the smallest distance between the fourth point's projection and its normalised image point wins; ties go to
+ *     the solution found first, roots in ascending t (ascending s3 / s1).
+ *   Declined (status 0, poses_out[t] untouched, num_solutions[t] = 0): two of the four indices coincide, or two of the three world points;
+ *     the three world points are collinear (the smaller singular value of the centred triple not above 1e-4 of the larger: the number
+ *     of the DLT's line test, which applies it to the scatter's eigenvalues); no admissible solution; a pose that is not finite.
+ * subsets [num_tasks][4], n >= 4.  status[t]: 0 declined, 1 solved.  num_solutions (may be NULL) [num_tasks]: admissible solutions, 0..4.
+ * One lane per subset, fp64, all in registers; a subset's result does not depend on where it sits in the call. */
+int32_t rsba_pnp_p3p(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                     const int32_t* subsets /* [num_tasks][4] */, int32_t num_tasks, double* poses_out /* [num_tasks][6] */, uint8_t* status,
+                     int32_t* num_solutions);
+
+/* rsba_pnp_gs_hypotheses with the minimal solver in the DLT's place (solveGsPnPRansacP3P in one call): normalise, P3P, the refinement of
+ * rsba_pnp_tasks with shutter GLOBAL and m = 4 from each subset's pose, inlier counts.  The start poses never leave the device.
+ * status[t]: 0 declined by the minimal solver, 1 refined and usable, 2 refinement unusable (poses_out[t] = the P3P pose). */
+int32_t rsba_pnp_gs_hypotheses_p3p(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
+                                   const int32_t* subsets /* [num_tasks][4] */, int32_t num_tasks, int32_t max_num_iterations, float reprojection_error,
+                                   double* poses_out /* [num_tasks][6] */, uint8_t* status, double* final_cost, int32_t* num_inliers);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

@@ -22,7 +22,7 @@ EXPORTS = [
     "rsba_get_device_view", "rsba_time_evaluate", "rsba_default_solver_options", "rsba_solve", "rsba_normal_equations",
     "rsba_set_exchange", "rsba_get_block_structure", "rsba_set_block_structure",
     "rsba_validate_observations", "rsba_reproject", "rsba_pose_covariance", "rsba_set_motion_priors",
-    "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
+    "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
@@ -664,6 +664,33 @@ def pnp_gs_hypotheses(cam, object_points, image_points, subsets, max_num_iterati
     poses = np.zeros((H, 6)); status = np.zeros(H, dtype=np.uint8); cost = np.zeros(H); inl = np.zeros(H, dtype=np.int32)
     _check(lib().rsba_pnp_gs_hypotheses(C.c_int32(device), _ptr(cam), _ptr(op), _ptr(ip), C.c_int32(len(op)), _ptr(sub), C.c_int32(m), C.c_int32(H),
                                         C.c_int32(int(max_num_iterations)), C.c_float(float(reprojection_error)), _ptr(poses), _ptr(status), _ptr(cost), _ptr(inl)))
+    return dict(poses=poses, status=status, final_cost=cost, num_inliers=inl)
+
+
+def pnp_p3p(cam, object_points, image_points, subsets, poses_out=None, device=0):
+    """The minimal solver for every four-point subset, on the device (rsba_amd.h: rsba_pnp_p3p): three points solved, the fourth chooses.
+    -> dict(poses [H,6] (declined rows keep what poses_out held, zeros without it), status [H]: 0 declined, 1 solved; num_solutions [H]: 0..4)"""
+    cam = np.ascontiguousarray(cam, dtype=np.float64)
+    op = np.ascontiguousarray(object_points, dtype=np.float32).reshape(-1, 3); ip = np.ascontiguousarray(image_points, dtype=np.float32).reshape(-1, 2)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    assert m == 4
+    poses = np.zeros((H, 6)) if poses_out is None else poses_out
+    assert poses.dtype == np.float64 and poses.shape == (H, 6) and poses.flags.c_contiguous
+    status = np.zeros(H, dtype=np.uint8); nsol = np.zeros(H, dtype=np.int32)
+    _check(lib().rsba_pnp_p3p(C.c_int32(device), _ptr(cam), _ptr(op), _ptr(ip), C.c_int32(len(op)), _ptr(sub), C.c_int32(H), _ptr(poses), _ptr(status), _ptr(nsol)))
+    return dict(poses=poses, status=status, num_solutions=nsol)
+
+
+def pnp_gs_hypotheses_p3p(cam, object_points, image_points, subsets, max_num_iterations=5, reprojection_error=8.0, device=0):
+    """The global-shutter hypothesis batch of solveGsPnPRansacP3P in one call (rsba_amd.h: rsba_pnp_gs_hypotheses_p3p).
+    -> dict(poses [H,6], status [H]: 0 declined by the minimal solver, 1 usable, 2 refinement unusable; final_cost [H], num_inliers [H])"""
+    cam = np.ascontiguousarray(cam, dtype=np.float64)
+    op = np.ascontiguousarray(object_points, dtype=np.float32).reshape(-1, 3); ip = np.ascontiguousarray(image_points, dtype=np.float32).reshape(-1, 2)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    assert m == 4
+    poses = np.zeros((H, 6)); status = np.zeros(H, dtype=np.uint8); cost = np.zeros(H); inl = np.zeros(H, dtype=np.int32)
+    _check(lib().rsba_pnp_gs_hypotheses_p3p(C.c_int32(device), _ptr(cam), _ptr(op), _ptr(ip), C.c_int32(len(op)), _ptr(sub), C.c_int32(H),
+                                            C.c_int32(int(max_num_iterations)), C.c_float(float(reprojection_error)), _ptr(poses), _ptr(status), _ptr(cost), _ptr(inl)))
     return dict(poses=poses, status=status, final_cost=cost, num_inliers=inl)
 
 

@@ -32,7 +32,19 @@ struct PnpDltArgs {
   uint8_t* status;               // [num_tasks] 0 declined, 1 general DLT, 2 planar branch
 };
 
+// Arguments of the minimal-solver kernel (kernels_pnp_p3p.hip)
+struct PnpP3pArgs {
+  int n, num_tasks;
+  const float* object_points;    // [n][3]
+  const double* normalised;      // [n][2], from the normalise kernel
+  const int32_t* subsets;        // [num_tasks][4]: three solved points, the fourth chooses among the solutions
+  double* poses_out;             // [num_tasks][6]; declined slots are not written
+  uint8_t* status;               // [num_tasks] 0 declined, 1 solved
+  int32_t* num_solutions;        // [num_tasks] admissible solutions, 0..4
+};
+
 hipError_t launch_pnp_normalise(const PnpDltArgs& args, hipStream_t st);
+hipError_t launch_pnp_p3p(const PnpP3pArgs& args, hipStream_t st);
 hipError_t launch_pnp_dlt(const PnpDltArgs& args, hipStream_t st);
 // subsets_out[j] = subsets[map[j]], init_out[j] = (dlt_poses[map[j]], dlt_poses[map[j]]) for j < count
 hipError_t launch_pnp_compact(const int32_t* map, int count, int m, const int32_t* subsets, const double* dlt_poses, int32_t* subsets_out,
