@@ -148,7 +148,7 @@ void chol_tasks(const CholTaskInput& in, CholHostPlan* hp) {
       for (int32_t k : rj) { s.diag_list.push_back(slot_of(j, k)); s.diag_list.push_back(perm[k]); klev.push_back(level[k]); }
       s.diag_ptr.push_back((int32_t)(s.diag_list.size() / 2));
       {
-        // the contributors a second right-hand side's forward task sums over (FWD2 / FWD2P, cholesky.hip): all of them; in a sharded plan a
+        // the contributors a second right-hand side's forward task sums over (FWD2 / FWD2P, chol_tasks.hpp): all of them; in a sharded plan a
         // separator column takes THIS rank's part in launch A (its share travels) and the separators' own columns in launch B
         const int32_t dp1 = (int32_t)(s.diag_list.size() / 2);
         s.fwd_full.push_back(dp0); s.fwd_full.push_back(dp1);
@@ -190,7 +190,7 @@ void chol_tasks(const CholTaskInput& in, CholHostPlan* hp) {
   s.nparts = parts;
   // A free interFrameRatio brings a second right-hand side (its column of the normal equations): z2 = L^-1 b is formed by FWD2 tasks
   // right behind the DIAG tasks of their columns — light tasks for workgroups the factorisation leaves idle — and ONE ETA task between
-  // the forward and the backward phase turns both forward solves into the ratio's step (solver_state.hpp; cholesky.hip)
+  // the forward and the backward phase turns both forward solves into the ratio's step (solver_state.hpp; chol_tasks.hpp: task_eta)
   auto push = [](std::vector<int32_t>& t, int kind, int item) { t.push_back(kind); t.push_back(item); };
   for (int l = 0; l < nlev; ++l) {
     for (int32_t u : upd_by_level[l]) push(s.tasks, kTaskUpdate, u);

@@ -1,5 +1,5 @@
 // The tile Cholesky of the reduced camera system as the HOST plans it: the symbolic factorisation of the ordered tile graph and the
-// task graph the device runs over it (cholesky.hip) — which UPDATE / DIAG / SUB / BACK / FWD2 / ETA items exist, who owns them, in
+// task graph the device runs over it (cholesky.hip, chol_tasks.hpp) — which UPDATE / DIAG / SUB / BACK / FWD2 / ETA items exist, who owns them, in
 // what ticket order, which contributors are chunked or fused.  Index arithmetic only: no device, no handle, no environment — the
 // caller (solver_plan.hip) reads the switches and passes values in, and the lists can be checked without a GPU (tests/test_chol_plan.py).
 //

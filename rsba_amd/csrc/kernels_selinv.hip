@@ -6,7 +6,7 @@
 //   DIAG  Sigma_jj = W_j^T W_j - sum_{k in col[j]} Sigma_kj^T G_kj,  stored as (X + X^T) / 2
 // One 256-thread workgroup per output tile; both operands of a product are staged in LDS (a transposed operand is transposed on the way
 // in), the 48 x 48 x 48 product runs on the fp64 matrix cores (v_mfma_f64_16x16x4_f64: the nine 16 x 16 blocks of the result dealt to
-// the four waves, twelve steps of k each) in the register layout of cholesky.hip (lane (r, g): rows g + 4v of column r).  The terms of
+// the four waves, twelve steps of k each) in the register layout of chol_tasks.hpp (lane (r, g): rows g + 4v of column r).  The terms of
 // a sum are taken in list order by one workgroup, so two runs agree bit for bit.  No workgroup waits for another: the host launches
 // level after level, descending (solver.hip), OFF before DIAG.
 //
@@ -17,7 +17,7 @@
 // of rsba_pose_covariance — and row and column c of W_j are zeroed everywhere else before G and DIAG use it.  The factor's rows and
 // columns are exactly zero off the diagonal there, so Sigma gets exact zeros in these rows and columns, by induction over the recurrence.
 //
-// The products.  cholesky.hip's accumulate() / times_inverse_transposed are written for its persistent driver: one operand comes out of
+// The products.  chol_tasks.hpp's accumulate() / times_inverse_transposed are written for its persistent driver: one operand comes out of
 // the write-once cells with the driver's acquire loads and the other is pinned to the register image of the task before, and both
 // assume the task's own LDS map.  Here every operand is a finished tile in HBM and a third of them is read transposed, so the products
 // are restated (Acc: the same instruction, the same lane (r, g) -> rows g + 4 v of column r layout of the result) over two LDS tiles.

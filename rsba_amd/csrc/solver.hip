@@ -335,7 +335,7 @@ static int32_t solve_reduced_pcg(rsba_handle* h) {
 // ratio (free interFrameRatio only): in {h_s + D/radius, g_s, scale of the ratio}, out the ratio's scaled step eta.
 // The ratio's column b of the damped normal equations is a 1-wide dense border of S.  With S = L L^T, z = L^-1 g, z2 = L^-1 b:
 //   eta = (g_s - s z2.z) / (h_s + D - s^2 z2.z2),   L^T y = z - (s eta) z2
-// — both forward solves inside the factorisation's own launch (FWD2 tasks beside the DIAG tasks, cholesky.hip), the ETA task between
+// — both forward solves inside the factorisation's own launch (FWD2 tasks beside the DIAG tasks, chol_tasks.hpp), the ETA task between
 // the phases, ONE backward solve.  (Until round 4 the second right-hand side took a launch of its own: S u = g, S v = b, y = u - s eta v.)
 // ratio == nullptr with a two-column plan: the device-side loop — the ratio's scalars are on the device already (ratio_prepare_ctl).
 int32_t factor_and_solve(rsba_handle* h, double radius, RatioStep* ratio) {

@@ -1169,7 +1169,7 @@ int32_t PlanBuild::allocations() {
   // One persistent workgroup per CU — or two, for a WIDE task graph.  Claimed tasks that wait for their inputs hold a workgroup and the
   // schedule is short of them (192 instead of 256 workgroups cost 5 % at C4); the kernel is built so that two fit a CU (78 KB of LDS,
   // <= 256 registers per lane).  Through round 4 two per CU slowed the solve down by orders of magnitude: twice the waves polling AND every
-  // operand load going to the memory side.  With the operand tiles looked ahead at through L2 (cholesky.hip, Frag::load) that is gone:
+  // operand load going to the memory side.  With the operand tiles looked ahead at through L2 (chol_tasks.hpp, Frag::load) that is gone:
   // 512 workgroups are stable (C5 7.54 - 7.64 ms per LM iteration in six runs against 7.86 - 7.96 with 256, 384 in between) where a level of
   // the elimination tree holds more tasks than there are CUs (C5: 380 per level), and change nothing where the chain dominates (C4: 116 per
   // level, 1.62 ms either way).  RSBA_CHOL_WGS overrides, capped at two per CU.

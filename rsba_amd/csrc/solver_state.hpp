@@ -156,7 +156,7 @@ hipError_t allow_dynamic_lds_impl(const void* kernel, size_t bytes);   // capi.h
 template <class K>
 inline hipError_t allow_dynamic_lds(K kernel, size_t bytes) { return allow_dynamic_lds_impl(reinterpret_cast<const void*>(kernel), bytes); }
 
-// Cholesky task plan (cholesky.hip): the work lists of chol_plan.hpp, device pointers
+// Cholesky task plan (cholesky.hip, chol_tasks.hpp): the work lists of chol_plan.hpp, device pointers
 struct CholPlan {
   const int32_t *upd, *diag_info, *diag_ptr, *diag_list, *sub_info, *sub_ptr, *sub_list, *sub_col, *diag_own, *sub_own, *back_info, *back_ptr, *back_list;
   const int32_t* diag_fuse;  // per DIAG item: the SUB item of its last contributor, whose product with W the DIAG task forms itself (-1: none)
@@ -192,13 +192,14 @@ hipError_t launch_pose_prior_take(const DeviceProblem& dp, const SolverDev& sv, 
 hipError_t launch_pose_prior_reduce(const DeviceProblem& dp, const SolverDev& sv, const PosePriorDev& pp, double radius, hipStream_t st);
 hipError_t launch_pose_prior_step(const DeviceProblem& dp, const SolverDev& sv, const PosePriorDev& pp, double radius, hipStream_t st);
 
-// cholesky.hip
-hipError_t launch_chol_level(const SolverDev& sv, const CholPlan& pl, int kind, int first, int count, hipStream_t st);
-// res = rhs - S y with den = |rhs| + |S||y| over the packed tiles; *flag = 1 when |res| > tol * den somewhere, left alone otherwise (sticky; cholesky.hip)
+// kernels_chol_verify.hip: the check of what the persistent Cholesky driver returned
+// res = rhs - S y with den = |rhs| + |S||y| over the packed tiles; *flag = 1 when |res| > tol * den somewhere, left alone otherwise (sticky)
 // slot_tiles [nslots][2] = {row tile, column tile} (unpermuted tile indices) of every packed tile
 // b_rhs: the right-hand side the system was solved for (a private copy: the caller overwrites sv.rhs with the step while the check runs on its own stream)
 // row_mine (may be null): [nt] 1 = the rows of this tile are checked (sharded factorisation: the rows whose tiles are all on this rank)
 hipError_t launch_chol_verify(const SolverDev& sv, const int32_t* slot_tiles, const double* b_rhs, double* res, double* den, double tol, double* flag, hipStream_t st, const uint8_t* row_mine = nullptr);
+// cholesky.hip: the drivers of the tile tasks
+hipError_t launch_chol_level(const SolverDev& sv, const CholPlan& pl, int kind, int first, int count, hipStream_t st);
 struct DagArgs { SolverDev sv; CholPlan pl; };   // device copy the persistent kernel reads its state through (uploaded once per plan)
 hipError_t launch_chol_solve(const SolverDev& sv, const CholPlan& pl, const DagArgs* device_args, const double* b2, double* zy2, unsigned int* ticket, int workgroups, hipStream_t st);   // one more right-hand side through the factor of the last launch_chol_dag / level run
 hipError_t launch_chol_solve_level(const SolverDev& sv, const CholPlan& pl, bool backward, int first, int count, const double* b2, double* zy2, hipStream_t st);   // the same tasks, one launch per level

@@ -3,7 +3,7 @@
 
 The device runs the items under a persistent kernel whose tasks wait on write-once cells: a list that names a cell nobody writes, or
 a ticket order that is not topological, is a hang there.  Here the ticket orders are replayed with one "written" flag per cell —
-what every task kind reads and writes is restated below from cholesky.hip, by cell, without any arithmetic."""
+what every task kind reads and writes is restated below from the task bodies of chol_tasks.hpp, by cell, without any arithmetic."""
 import ctypes as C
 import os
 import sys

@@ -1,5 +1,5 @@
 """What the persistent Cholesky kernel reads coherently (from the memory side), by kind, per launch — the counters of the INSTRUMENTED library
-(rsba_amd/_lib/librsba_amd_hooks.so: cholesky.hip, CHOL_COUNT), to set beside the kernel's fabric reads from a rocprofv3 --pmc pass
+(rsba_amd/_lib/librsba_amd_hooks.so: chol_cells.hpp, CHOL_COUNT), to set beside the kernel's fabric reads from a rocprofv3 --pmc pass
 (TCC_EA0_RDREQ: profiles/r06/pmc_l2_*.csv).  usage: RSBA_AMD_LIB=rsba_amd/_lib/librsba_amd_hooks.so python tools/chol_poll_split.py [C4] [iters]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

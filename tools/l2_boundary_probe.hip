@@ -1,6 +1,6 @@
 // Does a kernel that starts AFTER another stream's writes (ordered by an event) ever read a stale line out of its XCD's L2?
 //
-// cholesky.hip's look-ahead loads (Frag::load, times_inverse_transposed: round 5 / 6) read the write-once cells with ordinary cached loads and
+// The Cholesky's look-ahead loads (chol_tasks.hpp: Frag::load, times_inverse_transposed; the scheme: chol_cells.hpp) read the write-once cells with ordinary cached loads and
 // fall back on a coherent read only where a double still looks empty.  A FILLED value that is stale — left in some XCD's L2 by the solve
 // that used the same set of cells two solves ago, while the cells were re-armed by a memset on another stream — would be taken for this
 // solve's.  What rules it out is that every kernel dispatch begins with an acquire that invalidates its XCDs' L2 lines of memory another

@@ -1,4 +1,4 @@
-// What one pivot of the MFMA-pivot LDL^T step (rsba_amd/csrc/cholesky.hip, ldl16_eliminate / ldl16_follow) costs, piece by piece:
+// What one pivot of the MFMA-pivot LDL^T step (rsba_amd/csrc/tile_factor.hpp: ldl16_eliminate; tools/tile_factor_baselines.hpp: ldl16_follow, the MFMA second wave) costs, piece by piece:
 // one wave, 16 pivots, variants with parts of the per-pivot work switched off (fp64 MFMA and fp64 vector time add up), then the
 // step split over two waves that talk through LDS.  Prints clock64 ticks and wall_clock64 (100 MHz) time
 // per 16-pivot block.   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ldl_probe.hip -o tools/ldl_probe
@@ -77,7 +77,7 @@ void run(const char* name, const double* din, double* dout, long long* dt) {
   std::printf("%-58s %7.1f clock64 ticks / pivot, %6.1f ns / pivot, %6.3f us / 16-pivot block\n", name, h[0] / (16.0 * reps), h[1] * 10.0 / (16.0 * reps), h[1] * 0.01 / reps);
 }
 
-// ---- two waves: leader eliminates and posts messages in LDS, follower applies them (cholesky.hip ldl16_eliminate / ldl16_follow)
+// ---- two waves: leader eliminates and posts messages in LDS, follower applies them (tile_factor.hpp ldl16_eliminate / tile_factor_baselines.hpp ldl16_follow)
 constexpr int kMsg = 66;
 __device__ __forceinline__ bool filled(double v) { return __double_as_longlong(v) != -1ll; }
 typedef __attribute__((address_space(3))) double* lds_ptr;

@@ -1,4 +1,4 @@
-// Do fp64 MFMAs of one wave and fp64 vector instructions of ANOTHER wave on the same SIMD overlap?  (cholesky.hip's ldl_probe shows that
+// Do fp64 MFMAs of one wave and fp64 vector instructions of ANOTHER wave on the same SIMD overlap?  (tools/ldl_probe.hip shows that
 // inside one wave their times add up; the Schur kernel runs two waves per SIMD, one of which is usually in its MFMAs while the other forms
 // operands.)  256 workgroups x 512 threads = two waves per SIMD; waves 0-3 of a workgroup (one per SIMD) issue MFMAs, waves 4-7 (the second wave of every SIMD)
 // dependent-free v_fma_f64 — mix = 0: everyone MFMAs, 1: everyone FMAs, 2: half and half.  Times per wave-instruction at the clock the kernel ran at.

@@ -1,19 +1,19 @@
 // NOTE (end of round 3): this file times the code as the compiler lays it out for THESE kernels; inside the solver's persistent kernel
 // the same source is laid out, allocated and fetched differently (tools/chol_trace.py is the measurement that counts): the rolled
 // three-block loop of factor_invert_tile made the tile 0.9 us faster there (8.3 -> 7.4 us) and 1.2 us slower here.
-// Micro-benchmark + check of the serial core of the tile Cholesky (rsba_amd/csrc/cholesky.hip): W = chol(D)^-1 of one
+// Micro-benchmark + check of the serial core of the tile Cholesky (rsba_amd/csrc/tile_factor.hpp): W = chol(D)^-1 of one
 // 48 x 48 tile by ONE 256-thread workgroup — the step that sits 42 times on the critical path of a 1k-camera solve.
-// Variants: the lane-per-row blocked potrf + blocked triangular inverse (round 1) and the MFMA-pivot LDL^T form.
+// Variants: the library's MFMA-pivot LDL^T form, and the earlier forms of tools/tile_factor_baselines.hpp (the lane-per-row blocked
+// potrf + blocked triangular inverse of round 1, round 2's second wave).
 // Checks |W D W^T - I| and |W - W_ref| against a host factorisation, prints microseconds per tile (wall_clock64, 100 MHz).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics tools/tile_factor_bench.hip -o tools/tile_factor_bench
-#include "../rsba_amd/csrc/cholesky.hip"
+#include "tile_factor_baselines.hpp"
 
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
 namespace rsba {
-hipError_t allow_dynamic_lds_impl(const void* kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }   // (capi.hip's, for the launchers pulled in above)
 namespace {
 
 template <int VARIANT>
@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256, 2) void tile_kernel(const double* __restrict__
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x;
   double* D = smem; double* Wl = smem + kBuf; double* Tm = smem + 2 * kBuf; double* Lp = smem + 3 * kBuf;
-  double* dinv = smem + kVecOff + 5 * T;
+  double* dinv = smem + kSpareVec;
   long long total = 0;
   for (int it = 0; it < reps; ++it) {
     for (int e = tid; e < T * T; e += 256) { const int r = e / T, c = e % T; D[r * TP + c] = (c <= r) ? Din[e] : 0.0; }
@@ -35,8 +35,8 @@ __global__ __launch_bounds__(256, 2) void tile_kernel(const double* __restrict__
       invert_lower_blocked(D, dinv, Wl, Tm, tid);
     } else {
       if (VARIANT == 2) factor_invert_tile<true>(D, Wl, Tm, Lp, tid, stamps);   // 2: with phase stamps (every repetition: warm code)
-      else if (VARIANT == 3) factor_invert_tile<false, true>(D, Wl, Tm, Lp, tid);   // 3: round 2's second wave (rank-1 MFMAs on the identity)
-      else if (VARIANT == 4) factor_invert_tile<false, false, true>(D, Wl, Tm, Lp, tid, nullptr, Wout + T * T);   // 4: as the persistent driver runs it — W published to write-once cells by row blocks
+      else if (VARIANT == 3) factor_invert_tile<false, false, FollowMfma>(D, Wl, Tm, Lp, tid);   // 3: round 2's second wave (rank-1 MFMAs on the identity)
+      else if (VARIANT == 4) factor_invert_tile<false, true>(D, Wl, Tm, Lp, tid, nullptr, Wout + T * T);   // 4: as the persistent driver runs it — W published to write-once cells by row blocks
       else factor_invert_tile(D, Wl, Tm, Lp, tid);
     }
     const long long t1 = wall_clock64();
@@ -62,14 +62,14 @@ __global__ __launch_bounds__(256) void paced_kernel(const double* __restrict__ D
   double* saved = smem + 4 * kBuf + 64;   // [16][64] the messages of a real elimination (behind the task's buffers)
   for (int e = tid; e < T * T; e += 256) { const int r = e / T, c = e % T; D[r * TP + c] = (c <= r) ? Din[e] : 0.0; }
   __syncthreads();
-  const dbl4_t d0 = load_sym16(D, 0, lane);
+  const dbl4 d0 = load_sym16(D, 0, lane);
   arm_pivot_messages(smem, tid);
   __syncthreads();
   if (wave == 0) ldl16_eliminate(d0, msg, lane);
   __syncthreads();
   if (wave == 0) for (int jj = 0; jj < 16; ++jj) saved[jj * 64 + lane] = msg[msg_off(jj) + lane];
   __syncthreads();
-  dbl4_t acc = {0, 0, 0, 0}, dummy = d0;
+  dbl4 acc = {0, 0, 0, 0}, dummy = d0;
   long long lead = 0, foll = 0, total = 0;
   for (int it = 0; it < reps; ++it) {
     arm_pivot_messages(smem, tid);
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* __restrict__ Di
   double* D = smem; double* msg = smem;
   for (int e = tid; e < T * T; e += 256) { const int r = e / T, c = e % T; D[r * TP + c] = (c <= r) ? Din[e] : 0.0; }
   __syncthreads();
-  const dbl4_t d0 = load_sym16(D, 0, lane);
-  dbl4_t acc = {0, 0, 0, 0};
+  const dbl4 d0 = load_sym16(D, 0, lane);
+  dbl4 acc = {0, 0, 0, 0};
   long long lead = 0, foll = 0, total = 0;
   for (int it = 0; it < reps; ++it) {
     if (MODE != 2 || it == 0) arm_pivot_messages(smem, tid);
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* __restrict__ Di
     const long long c0 = clock64();
     const bool last = stamps && it == reps - 1;
     if (last && tid == 0) stamps[0] = c0;
-    if (wave == 0 && MODE != 2) { dbl4_t d = d0; asm volatile("" : "+v"(d)); const bool ok = ldl16_eliminate(d, msg, lane, last ? stamps + 1 : nullptr); acc[0] += ok; lead += clock64() - c0; }
+    if (wave == 0 && MODE != 2) { dbl4 d = d0; asm volatile("" : "+v"(d)); const bool ok = ldl16_eliminate(d, msg, lane, last ? stamps + 1 : nullptr); acc[0] += ok; lead += clock64() - c0; }
     if (wave == FW && MODE != 1) {
       if (ROWS) { ldl16_follow_rows(msg, smem + kBuf, 0, lane, last ? stamps + 17 : nullptr); acc[0] += smem[kBuf + lane]; } else acc += ldl16_follow(msg, lane);
       foll += clock64() - c0;
@@ -225,8 +225,6 @@ int main() {
   long long hs[64]; hipMemcpy(hs, dS, sizeof hs, hipMemcpyDeviceToHost);
   std::printf("phases of the last MFMA-pivot tile (clock64 ticks since entry; pairs = before / after each barrier):");
   for (int k = 1; k < 13; ++k) std::printf(" %lld", hs[k] - hs[0]);
-  std::printf("\nfollower wave: pivot message k seen at tick (since entry):");
-  for (int k = 0; k < 16; ++k) std::printf(" %lld", hs[16 + k] - hs[0]);
   std::printf("\n");
   return 0;
 }

@@ -1,4 +1,4 @@
-// How long does a tile take from one workgroup to another through the write-once cells of the Cholesky (rsba_amd/csrc/cholesky.hip),
+// How long does a tile take from one workgroup to another through the write-once cells of the Cholesky (rsba_amd/csrc/chol_cells.hpp),
 // when both sit on the SAME XCD and the consumer reads at workgroup scope (sc0: served by the XCD's L2) instead of agent scope (sc1: from
 // the memory side)?  One producer stores 48 x 48 doubles (agent-scope atomic stores: write-through, what every other XCD needs) after
 // a delay; consumers poll the whole tile (36 loads per lane, like the DIAG tasks) and stamp when it is complete.
