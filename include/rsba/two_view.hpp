@@ -1,0 +1,374 @@
+// Two-view bootstrap: the relative pose of two frames from their 2-D / 2-D correspondences alone — what gives the first two frames of a
+// video their poses, so that createTracks, processFrame and BA (create_tracks.hpp, new_frame.hpp) have something to start from.  The
+// reference has no such step (its initialize() is a BA over frames that already carry 3-D points), so this text and rsba_amd.h
+// (rsba_epipolar_*) are the definition; epi_detail below is its host form, which the device kernels (rsba_amd/csrc/kernels_epipolar.hip)
+// restate and the tests hold both to.
+//
+// Conventions.  a = (xa, ya, 1), b = (xb, yb, 1) are the undistorted, normalised image points of one correspondence in frame A and frame B
+// (pnp_detail::normalised_point).  E is row-major with b^T E a = 0.  Camera A is the origin; camera B sees x_B = R x_A + t, E = [t]x R, and
+// the pose of B in A's frame is pnp_detail::pose_from_rt(R, t) with |t| = 1: the length of the baseline is the unit of the reconstruction.
+//
+// eight_point.  Hartley normalisation of each side's m points (centroid, mean distance scaled to sqrt 2), the 9 x 9 Gram matrix of the rows
+// (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1), its smallest eigenvector by pnp_detail::smallest_eigenvector12 with three idle unknowns
+// at twice the trace (as planar_pose does; zero off-diagonals are skipped, so the rotations are those of a 9 x 9 sweep) under the DLT's two
+// gap tests, the normalisation undone, then the projection onto the essential manifold: V and the singular values s1 >= s2 from eigen3 of
+// E^T E, u_i = E v_i / s_i for the two largest, u3 = u1 x u2, v3 = v1 x v2 (so det U = det V = +1), result u1 v1^T + u2 v2^T.
+// Declined: m < 8, a repeated index, a Hartley scale that is not positive, a second null direction (coplanar scene points, a pure rotation),
+// s2 not above 1e-6 s1, a result that is not finite.
+// Sign rule: the entry of E with the largest magnitude (the first such entry, row-major) is positive.  Flipping E swaps the two rotations
+// below and leaves the set of candidates, and so the chosen pose, as it is; comparisons of E are made up to sign.
+//
+// Pose recovery.  From the same decomposition of a given E: R1 = U W V^T, R2 = U W^T V^T (W a quarter turn about z), t = u3 / |u3|; the
+// candidates in the fixed order (R1, +t), (R1, -t), (R2, +t), (R2, -t) — the pair (v1, v2) taken the way round that makes the largest
+// component of v3 positive, since s1 = s2 leaves that to rounding.  A correspondence is in front for a candidate when the least-squares
+// depths of z_a R a + t = z_b b are both positive (2 x 2 normal equations, closed form).  The candidate with the most INLIERS in front wins,
+// ties go to the first.
+// Inlier rule.  Sampson distance in normalised coordinates, fp64: d^2 = (b^T E a)^2 / ((E a)_x^2 + (E a)_y^2 + (E^T b)_x^2 + (E^T b)_y^2);
+// inlier iff d^2 f^2 <= threshold_px^2 with f = (fx_a + fy_a + fx_b + fy_b) / 4.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "ceres_handler.hpp"
+#include "create_tracks.hpp"
+#include "solve_rs_pnp.hpp"
+
+namespace rsba_amd {
+
+namespace epi_detail {
+
+using pnp_detail::eigen3;
+using pnp_detail::pose_from_rt;
+
+// V (columns v1 v2 v3, singular values descending), U (columns u1 u2 u3) and s1, s2 of a 3 x 3 matrix that has rank two (or nearly);
+// false: s2 is not above 1e-6 s1
+inline bool essential_svd(const double E[9], double U[3][3] /* [column][row] */, double V[3][3] /* [column][row] */, double s[2]) {
+  double sym[6] = {0, 0, 0, 0, 0, 0};   // E^T E: xx xy xz yy yz zz
+  for (int r = 0; r < 3; ++r) {
+    sym[0] += E[3 * r] * E[3 * r]; sym[1] += E[3 * r] * E[3 * r + 1]; sym[2] += E[3 * r] * E[3 * r + 2];
+    sym[3] += E[3 * r + 1] * E[3 * r + 1]; sym[4] += E[3 * r + 1] * E[3 * r + 2]; sym[5] += E[3 * r + 2] * E[3 * r + 2];
+  }
+  double val[3], vec[3][3];
+  eigen3(sym, val, vec);
+  s[0] = std::sqrt(std::fmax(0.0, val[2])); s[1] = std::sqrt(std::fmax(0.0, val[1]));
+  if (!(s[1] > 1e-6 * s[0])) return false;
+  for (int k = 0; k < 3; ++k) { V[0][k] = vec[2][k]; V[1][k] = vec[1][k]; }
+  for (int c = 0; c < 2; ++c)
+    for (int r = 0; r < 3; ++r) U[c][r] = (E[3 * r] * V[c][0] + E[3 * r + 1] * V[c][1] + E[3 * r + 2] * V[c][2]) / s[c];
+  U[2][0] = U[0][1] * U[1][2] - U[0][2] * U[1][1]; U[2][1] = U[0][2] * U[1][0] - U[0][0] * U[1][2]; U[2][2] = U[0][0] * U[1][1] - U[0][1] * U[1][0];
+  V[2][0] = V[0][1] * V[1][2] - V[0][2] * V[1][1]; V[2][1] = V[0][2] * V[1][0] - V[0][0] * V[1][2]; V[2][2] = V[0][0] * V[1][1] - V[0][1] * V[1][0];
+  // s1 = s2 for an essential matrix, so (v1, v2) is any orthonormal pair of their plane and rounding alone decides which way round it
+  // runs — which swaps (R1, +t) with (R2, -t).  Fixed here: the component of v3 with the largest magnitude (the first such) is positive.
+  int lead = 0;
+  for (int k = 1; k < 3; ++k) if (std::fabs(V[2][k]) > std::fabs(V[2][lead])) lead = k;
+  if (V[2][lead] < 0) for (int k = 0; k < 3; ++k) { V[1][k] = -V[1][k]; U[1][k] = -U[1][k]; V[2][k] = -V[2][k]; U[2][k] = -U[2][k]; }
+  return true;
+}
+
+// the pieces of eight_point, apart so that the tests can seed errors between them
+struct Hartley { double ca[2], cb[2], sa, sb; };   // x' = (x - c) / s per side
+inline bool hartley(const double* na, const double* nb, const int32_t* idx, int m, Hartley& H) {
+  H.ca[0] = H.ca[1] = H.cb[0] = H.cb[1] = 0.0; H.sa = H.sb = 0.0;
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)idx[i];
+    H.ca[0] += na[j] / m; H.ca[1] += na[j + 1] / m; H.cb[0] += nb[j] / m; H.cb[1] += nb[j + 1] / m;
+  }
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)idx[i];
+    H.sa += std::hypot(na[j] - H.ca[0], na[j + 1] - H.ca[1]) / m; H.sb += std::hypot(nb[j] - H.cb[0], nb[j + 1] - H.cb[1]) / m;
+  }
+  if (!(H.sa > 0.0) || !(H.sb > 0.0)) return false;
+  H.sa /= 1.4142135623730951; H.sb /= 1.4142135623730951;
+  return true;
+}
+// the null direction of the m epipolar constraints in the coordinates of H, taken back to the normalised image coordinates; false: ambiguous
+inline bool null_matrix(const double* na, const double* nb, const int32_t* idx, int m, const Hartley& H, double F[9]) {
+  double ata[12][12] = {};
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)idx[i];
+    const double xa = (na[j] - H.ca[0]) / H.sa, ya = (na[j + 1] - H.ca[1]) / H.sa, xb = (nb[j] - H.cb[0]) / H.sb, yb = (nb[j + 1] - H.cb[1]) / H.sb;
+    const double r[9] = {xb * xa, xb * ya, xb, yb * xa, yb * ya, yb, xa, ya, 1.0};
+    for (int a = 0; a < 9; ++a) for (int b = 0; b < 9; ++b) ata[a][b] += r[a] * r[b];
+  }
+  double big = 0.0;
+  for (int a = 0; a < 9; ++a) big += ata[a][a];
+  if (!(big > 0.0)) return false;
+  for (int a = 9; a < 12; ++a) ata[a][a] = 2.0 * big;   // three idle unknowns far from the null space
+  double ev[12], gap[3];
+  pnp_detail::smallest_eigenvector12(ata, ev, gap);
+  if (!(gap[1] > 1e-9 * gap[2]) || !(gap[0] < 0.05 * gap[1])) return false;   // a second null direction: a plane, or no baseline
+  // undo the normalisation: F = Tb^T Fn Ta, T = [[1/s 0 -cx/s] [0 1/s -cy/s] [0 0 1]]
+  double M[9];
+  for (int r = 0; r < 3; ++r) {
+    M[3 * r] = ev[3 * r] / H.sa; M[3 * r + 1] = ev[3 * r + 1] / H.sa;
+    M[3 * r + 2] = ev[3 * r + 2] - (H.ca[0] * ev[3 * r] + H.ca[1] * ev[3 * r + 1]) / H.sa;
+  }
+  for (int k = 0; k < 3; ++k) {
+    F[k] = M[k] / H.sb; F[3 + k] = M[3 + k] / H.sb;
+    F[6 + k] = M[6 + k] - (H.cb[0] * M[k] + H.cb[1] * M[3 + k]) / H.sb;
+  }
+  return true;
+}
+// the nearest matrix with singular values (1, 1, 0)
+inline bool project_essential(const double F[9], double out[9]) {
+  double U[3][3], V[3][3], s[2];
+  if (!essential_svd(F, U, V, s)) return false;
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) out[3 * r + k] = U[0][r] * V[0][k] + U[1][r] * V[1][k];
+  return true;
+}
+// the sign rule, and the last reason to decline
+inline bool signed_finite(double out[9]) {
+  int lead = 0;
+  for (int k = 1; k < 9; ++k) if (std::fabs(out[k]) > std::fabs(out[lead])) lead = k;
+  if (out[lead] < 0) for (int k = 0; k < 9; ++k) out[k] = -out[k];
+  for (int k = 0; k < 9; ++k) if (!std::isfinite(out[k])) return false;
+  return true;
+}
+// the essential matrix of the correspondences idx[0..m) of the normalised points na, nb [.][2]; false: declined (E untouched)
+inline bool eight_point(const double* na, const double* nb, const int32_t* idx, int m, double E[9]) {
+  if (m < 8) return false;
+  for (int i = 0; i < m; ++i) for (int k = i + 1; k < m; ++k) if (idx[i] == idx[k]) return false;
+  Hartley H;
+  double F[9], out[9];
+  if (!hartley(na, nb, idx, m, H) || !null_matrix(na, nb, idx, m, H, F) || !project_essential(F, out) || !signed_finite(out)) return false;
+  for (int k = 0; k < 9; ++k) E[k] = out[k];
+  return true;
+}
+
+// the two rotations and the baseline direction of E; false: declined
+struct Candidates { double R[2][9]; double t[3]; };
+inline bool decompose(const double E[9], Candidates& C) {
+  double U[3][3], V[3][3], s[2];
+  if (!essential_svd(E, U, V, s)) return false;
+  const double nt = std::sqrt(U[2][0] * U[2][0] + U[2][1] * U[2][1] + U[2][2] * U[2][2]);
+  if (!(nt > 0.0)) return false;
+  for (int k = 0; k < 3; ++k) C.t[k] = U[2][k] / nt;
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) {
+    const double w = U[1][r] * V[0][k] - U[0][r] * V[1][k], z = U[2][r] * V[2][k];   // U W V^T = u2 v1^T - u1 v2^T + u3 v3^T
+    C.R[0][3 * r + k] = w + z; C.R[1][3 * r + k] = z - w;
+  }
+  for (int c = 0; c < 2; ++c) for (int k = 0; k < 9; ++k) if (!std::isfinite(C.R[c][k])) return false;
+  return std::isfinite(C.t[0] + C.t[1] + C.t[2]);
+}
+
+// the two deciding comparisons: the device evaluates these operations in this order (kernels_epipolar.hip, contraction off)
+inline bool sampson_inlier(const double E[9], double xa, double ya, double xb, double yb, double f2, double thr2, double* d2_out = nullptr) {
+  const double l0 = E[0] * xa + E[1] * ya + E[2], l1 = E[3] * xa + E[4] * ya + E[5], l2 = E[6] * xa + E[7] * ya + E[8];
+  const double m0 = E[0] * xb + E[3] * yb + E[6], m1 = E[1] * xb + E[4] * yb + E[7];
+  const double r = xb * l0 + yb * l1 + l2;
+  const double den = l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1;
+  const double d2 = (r * r) / den;
+  if (d2_out) *d2_out = d2;
+  return d2 * f2 <= thr2;
+}
+inline bool in_front(const double R[9], const double t[3], double sign, double xa, double ya, double xb, double yb) {
+  const double p0 = R[0] * xa + R[1] * ya + R[2], p1 = R[3] * xa + R[4] * ya + R[5], p2 = R[6] * xa + R[7] * ya + R[8];
+  const double t0 = sign * t[0], t1 = sign * t[1], t2 = sign * t[2];
+  const double pp = p0 * p0 + p1 * p1 + p2 * p2, qq = xb * xb + yb * yb + 1.0, pq = p0 * xb + p1 * yb + p2;
+  const double pt = p0 * t0 + p1 * t1 + p2 * t2, qt = xb * t0 + yb * t1 + t2;
+  const double det = pp * qq - pq * pq;
+  const double za = (pq * qt - qq * pt) / det, zb = (pp * qt - pq * pt) / det;
+  return za > 0.0 && zb > 0.0;
+}
+
+inline double mean_focal2(const double cam_a[NUM_CAM_PARAMS], const double cam_b[NUM_CAM_PARAMS]) {
+  const double f = (cam_a[0] + cam_a[1] + cam_b[0] + cam_b[1]) / 4.0;
+  return f * f;
+}
+
+// counts of one E over all n correspondences, the winning candidate and its pose; false: declined (nothing written but zero counts)
+inline bool score(const double* na, const double* nb, int n, const double E[9], double f2, double thr2, int32_t* num_inliers, int32_t num_front[4],
+                  double pose[6], int* winner = nullptr, uint8_t* mask = nullptr) {
+  *num_inliers = 0;
+  for (int c = 0; c < 4; ++c) num_front[c] = 0;
+  Candidates C;
+  if (!decompose(E, C)) return false;
+  int32_t inl = 0, front[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const double xa = na[2 * (size_t)i], ya = na[2 * (size_t)i + 1], xb = nb[2 * (size_t)i], yb = nb[2 * (size_t)i + 1];
+    const bool in = sampson_inlier(E, xa, ya, xb, yb, f2, thr2);
+    if (mask) mask[i] = in ? 1 : 0;
+    if (!in) continue;
+    ++inl;
+    for (int c = 0; c < 4; ++c) if (in_front(C.R[c >> 1], C.t, (c & 1) ? -1.0 : 1.0, xa, ya, xb, yb)) ++front[c];
+  }
+  int best = 0;
+  for (int c = 1; c < 4; ++c) if (front[c] > front[best]) best = c;
+  const double tb[3] = {(best & 1) ? -C.t[0] : C.t[0], (best & 1) ? -C.t[1] : C.t[1], (best & 1) ? -C.t[2] : C.t[2]};
+  double out[6];
+  if (!pose_from_rt(C.R[best >> 1], tb, out)) return false;
+  for (int k = 0; k < 6; ++k) pose[k] = out[k];
+  *num_inliers = inl;
+  for (int c = 0; c < 4; ++c) num_front[c] = front[c];
+  if (winner) *winner = best;
+  return true;
+}
+
+}  // namespace epi_detail
+
+struct TwoViewOptions {
+  int iterations = 1000;
+  double threshold_px = 4.0;
+  int refits = 3;
+  int min_inliers = 16;
+  uint64_t rng_state = 0x9e3779b97f4a7c15ULL;
+  bool hypotheses_on_device = true;   // false: the same loop from the host definitions above (what the tests compare with; no session-level code takes it)
+};
+
+struct TwoViewResult {
+  bool ok = false;
+  double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double pose_b[6] = {0, 0, 0, 0, 0, 0};   // camera B in A's frame, unit baseline
+  int num_inliers = 0;                     // Sampson inliers of E
+  int num_front = 0;                       // those of them in front of both cameras for the chosen candidate
+  int winner_task = -1, refits_adopted = 0;
+  std::vector<uint8_t> inliers;            // [n]
+};
+
+namespace epi_detail {
+// The RANSAC loop over a backend: hypotheses(subsets, m, tasks, E, poses, status, num_inliers, num_front) fills the arrays of `tasks` tasks,
+// inlier_mask(E, mask) the flags [n] of one matrix.
+template <class Hypotheses, class InlierMask>
+inline TwoViewResult ransac(int n, const TwoViewOptions& opt, Hypotheses&& hypotheses, InlierMask&& inlier_mask) {
+  TwoViewResult res;
+  res.inliers.assign((size_t)(n > 0 ? n : 0), 0);
+  if (n < 8 || opt.iterations <= 0) return res;
+  const int T = opt.iterations;
+  const std::vector<int32_t> subsets = pnp_detail::distinct_subsets(n, 8, T, opt.rng_state);
+  std::vector<double> E((size_t)T * 9), poses((size_t)T * 6);
+  std::vector<uint8_t> status((size_t)T);
+  std::vector<int32_t> inl((size_t)T), front((size_t)T * 4);
+  hypotheses(subsets.data(), 8, T, E.data(), poses.data(), status.data(), inl.data(), front.data());
+  int best = -1;
+  for (int t = 0; t < T; ++t) if (status[(size_t)t] != 0 && (best < 0 || inl[(size_t)t] > inl[(size_t)best])) best = t;
+  if (best < 0) return res;
+  res.winner_task = best;
+  int32_t cur_inl = inl[(size_t)best], cur_front[4];
+  for (int k = 0; k < 9; ++k) res.E[k] = E[(size_t)best * 9 + k];
+  for (int k = 0; k < 6; ++k) res.pose_b[k] = poses[(size_t)best * 6 + k];
+  for (int c = 0; c < 4; ++c) cur_front[c] = front[(size_t)best * 4 + c];
+  inlier_mask(res.E, res.inliers.data());
+  for (int round = 0; round < opt.refits; ++round) {
+    std::vector<int32_t> idx;
+    for (int i = 0; i < n; ++i) if (res.inliers[(size_t)i]) idx.push_back(i);
+    if (idx.size() < 8) break;
+    double e2[9], p2[6]; uint8_t st = 0; int32_t inl2 = 0, front2[4] = {0, 0, 0, 0};
+    hypotheses(idx.data(), (int)idx.size(), 1, e2, p2, &st, &inl2, front2);
+    if (!st || inl2 < cur_inl) break;   // not adopted: the next round would refit the same set
+    cur_inl = inl2;
+    for (int k = 0; k < 9; ++k) res.E[k] = e2[k];
+    for (int k = 0; k < 6; ++k) res.pose_b[k] = p2[k];
+    for (int c = 0; c < 4; ++c) cur_front[c] = front2[c];
+    inlier_mask(res.E, res.inliers.data());
+    ++res.refits_adopted;
+  }
+  int cand = 0;
+  for (int c = 1; c < 4; ++c) if (cur_front[c] > cur_front[cand]) cand = c;
+  res.num_inliers = cur_inl;
+  res.num_front = cur_front[cand];
+  res.ok = res.num_front >= opt.min_inliers;
+  return res;
+}
+
+// the loop from the host definitions alone: what the device path is compared with
+inline TwoViewResult host_ransac(const float* xy_a, const float* xy_b, int n, const double cam_a[NUM_CAM_PARAMS], const double cam_b[NUM_CAM_PARAMS],
+                                 const TwoViewOptions& opt) {
+  if (n < 8) return ransac(n, opt, [](auto&&...) {}, [](auto&&...) {});
+  const std::vector<double> na = pnp_detail::normalised_points(cam_a, xy_a, n), nb = pnp_detail::normalised_points(cam_b, xy_b, n);
+  const double f2 = mean_focal2(cam_a, cam_b), thr2 = opt.threshold_px * opt.threshold_px;
+  return ransac(n, opt,
+    [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
+      for (int t = 0; t < tasks; ++t) {
+        double e[9];
+        status[t] = eight_point(na.data(), nb.data(), sub + (size_t)t * m, m, e) &&
+                    score(na.data(), nb.data(), n, e, f2, thr2, &inl[t], &front[4 * (size_t)t], poses + 6 * (size_t)t) ? 1 : 0;
+        if (status[t]) for (int k = 0; k < 9; ++k) E[9 * (size_t)t + k] = e[k];
+        else { inl[t] = 0; for (int c = 0; c < 4; ++c) front[4 * (size_t)t + c] = 0; }
+      }
+    },
+    [&](const double E[9], uint8_t* mask) {
+      for (int i = 0; i < n; ++i)
+        mask[i] = sampson_inlier(E, na[2 * (size_t)i], na[2 * (size_t)i + 1], nb[2 * (size_t)i], nb[2 * (size_t)i + 1], f2, thr2) ? 1 : 0;
+    });
+}
+}  // namespace epi_detail
+
+// RANSAC over eight-point hypotheses: `iterations` subsets from pnp_detail::distinct_subsets(n, 8, ...), all scored in one device call
+// (rsba_epipolar_hypotheses); the most inliers win, ties go to the lowest task.  Then up to `refits` rounds of "eight-point over the current
+// inliers (one task, m = their number), recount", a refit adopted only when its count is not lower.  ok iff the final inliers in front of
+// both cameras number at least min_inliers.  xy_a / xy_b [n][2] are pixel coordinates (float, as everywhere in solve_rs_pnp.hpp).
+inline TwoViewResult findEssentialRansac(const float* xy_a, const float* xy_b, int n, const double cam_a[NUM_CAM_PARAMS], const double cam_b[NUM_CAM_PARAMS],
+                                         const TwoViewOptions& opt = TwoViewOptions(), int device = 0) {
+  if (!opt.hypotheses_on_device) return epi_detail::host_ransac(xy_a, xy_b, n, cam_a, cam_b, opt);
+  return epi_detail::ransac(n, opt,
+    [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
+      pnp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
+    },
+    [&](const double E[9], uint8_t* mask) { pnp_detail::check(rsba_epipolar_inliers(device, cam_a, cam_b, xy_a, xy_b, n, E, opt.threshold_px, mask)); });
+}
+
+namespace epi_detail {
+// the pose of a camera that sees x = R_rel x_A + t_rel, where camera A has pose_a: x = R_rel R_A (X - c_A) + t_rel
+inline bool compose_pose(const double pose_a[6], const double rel[6], double out[6]) {
+  double rvec[3], tvec[3], R[9];
+  pnp_detail::from_pose(rel, rvec, tvec);
+  for (int k = 0; k < 3; ++k) {
+    const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+    double ra[3], rb[3];
+    pnp_detail::rotate(pose_a, e, ra);
+    pnp_detail::rotate(rvec, ra, rb);
+    for (int r = 0; r < 3; ++r) R[3 * r + k] = rb[r];
+  }
+  for (int r = 0; r < 3; ++r) tvec[r] -= R[3 * r] * pose_a[3] + R[3 * r + 1] * pose_a[4] + R[3 * r + 2] * pose_a[5];
+  return pose_from_rt(R, tvec, out);
+}
+}  // namespace epi_detail
+
+// Poses for two frames that have none (frame A may have them already): the essential-matrix RANSAC over the matches of frame B that
+// reach frame A, frame A at the origin (zero poses: two in a rolling-shutter session, else one, as CeresHandler::Add starts frame 0) or
+// where it is, frame B at the recovered relative pose composed onto A's poses[0] — both pose slots the same in a rolling-shutter session,
+// the global-shutter approximation the GS PnP attempts of new_frame.hpp also start from.  Then createTracks(frameB) and, for neighbouring
+// frames and baIterations > 0, BA(frameA, frameB, reproject), whose verdict (a usable solution) is then the return value.  false otherwise:
+// fewer than 8 correspondences or no accepted geometry — the session is left untouched.  Requires frameA < frameB (matches live on the later frame) and a frame B without poses.
+// createTracks refuses a match into a frame without poses, as the reference does: every frame that frame B's matches reach must have poses
+// by then, so match a bootstrap pair against each other (and against frames that are already posed) only.
+struct TwoViewReport { int correspondences = 0, num_inliers = 0, num_front = 0; };
+inline bool initializeTwoView(Session& sess, const int32_t frameA, const int32_t frameB, const SfmOptions& opt, const TwoViewOptions& tv = TwoViewOptions(),
+                              int device = 0, bool progress = true, const int32_t baIterations = 20, TwoViewReport* report = nullptr) {
+  if (frameA < 0 || frameA >= frameB || (size_t)frameB >= sess.frames.size()) throw std::invalid_argument("initializeTwoView: 0 <= frameA < frameB < frames");
+  Frame& fa = sess.frames[(size_t)frameA];
+  Frame& fb = sess.frames[(size_t)frameB];
+  if (fb.__isset.poses && !fb.poses.empty()) throw std::invalid_argument("initializeTwoView: frame B has poses");
+  std::vector<float> xa, xb;
+  for (const Observation& o : fb.obs)
+    for (const ObservationRef& ref : o.matches) {
+      if (ref.frame != frameA) continue;
+      const Observation& o2 = fa.obs[(size_t)ref.obs];
+      xa.push_back((float)o2.x); xa.push_back((float)o2.y); xb.push_back((float)o.x); xb.push_back((float)o.y);
+      break;
+    }
+  const int n = (int)(xa.size() / 2);
+  if (report) { *report = TwoViewReport(); report->correspondences = n; }
+  if (n < 8) return false;
+  const double* cam_a = fa.__isset.cam ? fa.cam.data() : sess.cam.data();
+  const double* cam_b = fb.__isset.cam ? fb.cam.data() : sess.cam.data();
+  const TwoViewResult res = findEssentialRansac(xa.data(), xb.data(), n, cam_a, cam_b, tv, device);
+  if (report) { report->num_inliers = res.num_inliers; report->num_front = res.num_front; }
+  if (!res.ok) return false;
+  const size_t slots = opt.model.rolling_shutter ? 2 : 1;
+  std::vector<double> pose(res.pose_b, res.pose_b + NUM_POSE_PARAMS);
+  if (fa.__isset.poses && !fa.poses.empty()) {
+    if (!epi_detail::compose_pose(fa.poses[0].data(), res.pose_b, pose.data())) return false;
+  } else {
+    fa.poses.assign(slots, std::vector<double>(NUM_POSE_PARAMS, 0.0));
+    fa.__isset.poses = true;
+  }
+  fb.poses.assign(slots, pose);
+  fb.__isset.poses = true;
+  createTracks(sess, (size_t)frameB, opt, device);
+  if (baIterations > 0 && frameB == frameA + 1) return BA(sess, frameA, frameB, opt, baIterations, nullptr, progress, nullptr, true);
+  return true;
+}
+
+}  // namespace rsba_amd

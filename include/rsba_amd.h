@@ -552,6 +552,49 @@ int32_t rsba_pnp_gs_hypotheses_p3p(int32_t device, const double* cam, const floa
                                    const int32_t* subsets /* [num_tasks][4] */, int32_t num_tasks, int32_t max_num_iterations, float reprojection_error,
                                    double* poses_out /* [num_tasks][6] */, uint8_t* status, double* final_cost, int32_t* num_inliers);
 
+/* == the two-view bootstrap: essential-matrix hypotheses from 2-D / 2-D correspondences, for the first two frames of a video, which have no
+ * poses for createTracks / PnP to start from.  The reference has no such step, so this text is the definition; include/rsba/two_view.hpp
+ * (epi_detail::eight_point, decompose, score) is its host form and findEssentialRansac / initializeTwoView the callers.
+ *   Inputs.  xy_a, xy_b [n][2] float: pixel coordinates of correspondence i in frame A and frame B; cam_a, cam_b the 9 sfm intrinsics of the two
+ *     frames.  Both sides are undistorted and normalised once per call (pnp_detail::normalised_point): a = (xa, ya, 1), b = (xb, yb, 1).
+ *     E is row-major, b^T E a = 0; camera A is the origin, camera B sees x_B = R x_A + t, E = [t]x R.
+ *   Eight-point (m >= 8 indices per subset).  Hartley normalisation of each side's m points (centroid; mean distance scaled to sqrt 2); the
+ *     9 x 9 Gram matrix of the rows (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1); its smallest eigenvector by cyclic Jacobi (60 sweeps at
+ *     most) under the DLT's two gap tests — second-smallest eigenvalue above 1e-9 of the largest (where the largest counts the host form's
+ *     idle unknowns, twice the trace), smallest below 0.05 of the second; the normalisation undone; the projection onto the essential
+ *     manifold: V and the singular values s1 >= s2 from the Jacobi eigen-decomposition of E^T E, u_i = E v_i / s_i for the two largest,
+ *     result u1 v1^T + u2 v2^T.  Sign: the entry of largest magnitude (the first such, row-major) is positive.
+ *     Declined (status 0, E_out[t] untouched): a repeated index; a Hartley scale that is not positive (coincident points); a second null
+ *     direction (coplanar scene points, a pure rotation); s2 not above 1e-6 s1; a result that is not finite.
+ *   Pose recovery (of any given E).  With u3 = u1 x u2, v3 = v1 x v2: R1 = U W V^T, R2 = U W^T V^T (W the quarter turn about z), t = u3 / |u3|;
+ *     candidates in the fixed order (R1, +t), (R1, -t), (R2, +t), (R2, -t).  s1 = s2 leaves the way round (v1, v2) runs in their plane to
+ *     rounding, and the other way round swaps (R1, +t) with (R2, -t): the pair is taken so that the largest component of v3 is positive.  A correspondence is in front for a candidate when the
+ *     least-squares depths of z_a R a + t = z_b b (2 x 2 normal equations, closed form) are both positive.
+ *   Inlier rule.  Sampson distance in normalised coordinates, fp64: d^2 = (b^T E a)^2 / ((E a)_x^2 + (E a)_y^2 + (E^T b)_x^2 + (E^T b)_y^2);
+ *     inlier iff d^2 f^2 <= threshold_px^2, f = (fx_a + fy_a + fx_b + fy_b) / 4.  Both deciding comparisons are evaluated with the host form's
+ *     operations in the host form's order, every product and sum rounded on its own.
+ *   Score.  num_inliers[t]; num_front[t][c] = the inliers in front for candidate c; the candidate with the most wins, ties go to the first;
+ *     poses_out[t] = pnp_detail::pose_from_rt(R, t) of the winner — camera B in A's frame, rsba's 6-vector, unit baseline.
+ *     Declined (status 0; the counts are zero, poses_out[t] untouched): s2 not above 1e-6 s1, or a pose that is not finite.
+ * rsba_epipolar_eight_point: one lane per subset, fp64; a subset's result does not depend on where it sits in the call.
+ * rsba_epipolar_score: scores the given matrices E [num_tasks][9], one wave per matrix; the counts are integer sums.
+ * rsba_epipolar_hypotheses: the chain — normalise, eight-point, score; E never leaves the device between the two kernels.  status[t] 1: solved
+ *   and scored; 0: declined by either step (zero counts, E_out[t] and poses_out[t] untouched).
+ * rsba_epipolar_inliers: the inlier flags [n] of one E.
+ * n >= 8, m >= 8, n >= m.  All pointers are host arrays. */
+int32_t rsba_epipolar_eight_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                  const int32_t* subsets /* [num_tasks][m] */, int32_t m, int32_t num_tasks, double* E_out /* [num_tasks][9] */,
+                                  uint8_t* status);
+int32_t rsba_epipolar_score(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                            const double* E /* [num_tasks][9] */, int32_t num_tasks, double threshold_px, int32_t* num_inliers,
+                            int32_t* num_front /* [num_tasks][4] */, double* poses_out /* [num_tasks][6] */, uint8_t* status);
+int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                 const int32_t* subsets /* [num_tasks][m] */, int32_t m, int32_t num_tasks, double threshold_px,
+                                 double* E_out /* [num_tasks][9] */, double* poses_out /* [num_tasks][6] */, uint8_t* status, int32_t* num_inliers,
+                                 int32_t* num_front /* [num_tasks][4] */);
+int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                              const double* E /* [9] */, double threshold_px, uint8_t* inlier_mask /* [n] */);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

@@ -22,7 +22,8 @@ EXPORTS = [
     "rsba_get_device_view", "rsba_time_evaluate", "rsba_default_solver_options", "rsba_solve", "rsba_normal_equations",
     "rsba_set_exchange", "rsba_get_block_structure", "rsba_set_block_structure",
     "rsba_validate_observations", "rsba_reproject", "rsba_pose_covariance", "rsba_set_motion_priors",
-    "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
+    "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p",
+    "rsba_epipolar_eight_point", "rsba_epipolar_score", "rsba_epipolar_hypotheses", "rsba_epipolar_inliers", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
@@ -692,6 +693,63 @@ def pnp_gs_hypotheses_p3p(cam, object_points, image_points, subsets, max_num_ite
     _check(lib().rsba_pnp_gs_hypotheses_p3p(C.c_int32(device), _ptr(cam), _ptr(op), _ptr(ip), C.c_int32(len(op)), _ptr(sub), C.c_int32(H),
                                             C.c_int32(int(max_num_iterations)), C.c_float(float(reprojection_error)), _ptr(poses), _ptr(status), _ptr(cost), _ptr(inl)))
     return dict(poses=poses, status=status, final_cost=cost, num_inliers=inl)
+
+
+def _two_view_inputs(cam_a, cam_b, xy_a, xy_b):
+    ca = np.ascontiguousarray(cam_a, dtype=np.float64); cb = np.ascontiguousarray(cam_b, dtype=np.float64)
+    a = np.ascontiguousarray(xy_a, dtype=np.float32).reshape(-1, 2); b = np.ascontiguousarray(xy_b, dtype=np.float32).reshape(-1, 2)
+    assert len(a) == len(b)
+    return ca, cb, a, b
+
+
+def epipolar_eight_point(cam_a, cam_b, xy_a, xy_b, subsets, E_out=None, device=0):
+    """The essential matrix of every subset of m >= 8 correspondences, on the device (rsba_amd.h: rsba_epipolar_eight_point).
+    -> dict(E [H,9] row-major, b^T E a = 0 (declined rows keep what E_out held, zeros without it), status [H]: 0 declined, 1 solved)"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    E = np.zeros((H, 9)) if E_out is None else E_out
+    assert E.dtype == np.float64 and E.shape == (H, 9) and E.flags.c_contiguous
+    status = np.zeros(H, dtype=np.uint8)
+    _check(lib().rsba_epipolar_eight_point(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(sub), C.c_int32(m), C.c_int32(H),
+                                           _ptr(E), _ptr(status)))
+    return dict(E=E, status=status)
+
+
+def epipolar_score(cam_a, cam_b, xy_a, xy_b, E, threshold_px=4.0, poses_out=None, device=0):
+    """Inlier counts, the four cheirality counts and the winning candidate's pose of every given E (rsba_amd.h: rsba_epipolar_score).
+    -> dict(num_inliers [H], num_front [H,4], poses [H,6] (declined rows keep what poses_out held), status [H]: 0 declined, 1 scored)"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    E = np.ascontiguousarray(E, dtype=np.float64).reshape(-1, 9); H = len(E)
+    poses = np.zeros((H, 6)) if poses_out is None else poses_out
+    assert poses.dtype == np.float64 and poses.shape == (H, 6) and poses.flags.c_contiguous
+    inl = np.zeros(H, dtype=np.int32); front = np.zeros((H, 4), dtype=np.int32); status = np.zeros(H, dtype=np.uint8)
+    _check(lib().rsba_epipolar_score(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(E), C.c_int32(H),
+                                     C.c_double(float(threshold_px)), _ptr(inl), _ptr(front), _ptr(poses), _ptr(status)))
+    return dict(num_inliers=inl, num_front=front, poses=poses, status=status)
+
+
+def epipolar_hypotheses(cam_a, cam_b, xy_a, xy_b, subsets, threshold_px=4.0, E_out=None, poses_out=None, device=0):
+    """Eight-point and score in one call, E staying on the device between them (rsba_amd.h: rsba_epipolar_hypotheses).
+    -> dict(E [H,9], poses [H,6], status [H]: 0 declined by either step, 1 solved and scored; num_inliers [H], num_front [H,4])"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    E = np.zeros((H, 9)) if E_out is None else E_out
+    poses = np.zeros((H, 6)) if poses_out is None else poses_out
+    assert E.dtype == np.float64 and E.shape == (H, 9) and E.flags.c_contiguous
+    assert poses.dtype == np.float64 and poses.shape == (H, 6) and poses.flags.c_contiguous
+    inl = np.zeros(H, dtype=np.int32); front = np.zeros((H, 4), dtype=np.int32); status = np.zeros(H, dtype=np.uint8)
+    _check(lib().rsba_epipolar_hypotheses(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(sub), C.c_int32(m), C.c_int32(H),
+                                          C.c_double(float(threshold_px)), _ptr(E), _ptr(poses), _ptr(status), _ptr(inl), _ptr(front)))
+    return dict(E=E, poses=poses, status=status, num_inliers=inl, num_front=front)
+
+
+def epipolar_inliers(cam_a, cam_b, xy_a, xy_b, E, threshold_px=4.0, device=0):
+    """Inlier flags [n] of one essential matrix (rsba_amd.h: rsba_epipolar_inliers)."""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    E = np.ascontiguousarray(E, dtype=np.float64).reshape(9)
+    mask = np.zeros(len(a), dtype=np.uint8)
+    _check(lib().rsba_epipolar_inliers(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(E), C.c_double(float(threshold_px)), _ptr(mask)))
+    return mask.astype(bool)
 
 
 def default_options(**kw) -> SolverOptions:

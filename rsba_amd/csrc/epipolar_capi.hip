@@ -1,0 +1,210 @@
+// C-ABI of the two-view bootstrap (include/rsba_amd.h: rsba_epipolar_eight_point, rsba_epipolar_score, rsba_epipolar_hypotheses,
+// rsba_epipolar_inliers).  Host-side glue only: argument checks (the codes rsba_pnp_dlt returns for the same mistakes), staging of the
+// caller's arrays and the launches; every number comes from kernels_epipolar.hip and pnp_normalise_kernel (kernels_pnp_dlt.hip).
+#include "../../include/rsba_amd.h"
+
+#include <string>
+#include <vector>
+
+#include "epipolar_state.hpp"
+#include "handle.hpp"
+#include "pnp_state.hpp"
+
+using namespace rsba;
+
+namespace {
+
+struct DeviceBuffers {
+  std::vector<void*> ptrs;
+  ~DeviceBuffers() { for (void* p : ptrs) (void)hipFree(p); }
+  template <class T> hipError_t upload(const T** out, const T* src, size_t count) {
+    T* p = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), (count ? count : 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    ptrs.push_back(p);
+    *out = p;
+    return count ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+  }
+  template <class T> hipError_t alloc(T** out, size_t count) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(out), (count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) ptrs.push_back(*out);
+    return e;
+  }
+};
+
+#define EPI_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
+                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
+  } while (0)
+
+int32_t select_device(int32_t device) {
+  int32_t ndev = 0;
+  int32_t rc = rsba_device_count(&ndev);
+  if (rc) return rc;
+  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+  EPI_TRY(hipSetDevice(device));
+  return RSBA_OK;
+}
+
+int32_t check_points(const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
+  if (!cam_a || !cam_b || !xy_a || !xy_b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 8) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (an essential matrix takes at least 8 correspondences)");
+  return RSBA_OK;
+}
+int32_t check_subsets(int32_t n, const int32_t* subsets, int32_t m, int32_t num_tasks) {
+  if (!subsets) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (m < 8 || n < m || num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (an eight-point subset has at least 8 correspondences, n >= m)");
+  for (size_t k = 0; k < (size_t)num_tasks * m; ++k)
+    if (subsets[k] < 0 || subsets[k] >= n) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "subset index out of range");
+  return RSBA_OK;
+}
+
+// both frames' points uploaded, undistorted and normalised (pnp_normalise_kernel, once per side)
+struct Normalised { double* na = nullptr; double* nb = nullptr; };
+int32_t normalise_both(DeviceBuffers& B, Normalised& N, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
+  const double* cams[2] = {cam_a, cam_b};
+  const float* xy[2] = {xy_a, xy_b};
+  double** out[2] = {&N.na, &N.nb};
+  for (int side = 0; side < 2; ++side) {
+    PnpDltArgs D{};
+    for (int k = 0; k < 9; ++k) D.cam[k] = cams[side][k];
+    D.n = n;
+    EPI_TRY(B.upload(&D.image_points, xy[side], (size_t)n * 2));
+    EPI_TRY(B.alloc(&D.normalised, (size_t)n * 2));
+    EPI_TRY(launch_pnp_normalise(D, nullptr));
+    *out[side] = D.normalised;
+  }
+  return RSBA_OK;
+}
+
+double mean_focal2(const double* cam_a, const double* cam_b) {
+  const double f = (cam_a[0] + cam_a[1] + cam_b[0] + cam_b[1]) / 4.0;
+  return f * f;
+}
+
+int32_t run_eight_point(DeviceBuffers& B, EpiEightArgs& A, const Normalised& N, int32_t n, const int32_t* subsets, int32_t m, int32_t num_tasks) {
+  A.n = n; A.m = m; A.num_tasks = num_tasks; A.na = N.na; A.nb = N.nb;
+  EPI_TRY(B.upload(&A.subsets, subsets, (size_t)num_tasks * m));
+  EPI_TRY(B.alloc(&A.E_out, (size_t)num_tasks * 9));
+  EPI_TRY(B.alloc(&A.status, (size_t)num_tasks));
+  EPI_TRY(hipMemset(A.E_out, 0, (size_t)num_tasks * 9 * sizeof(double)));
+  EPI_TRY(launch_epipolar_eight_point(A, nullptr));
+  return RSBA_OK;
+}
+
+// S.E / S.status_in set by the caller; the outputs are allocated here and stay on the device
+int32_t run_score(DeviceBuffers& B, EpiScoreArgs& S, const Normalised& N, const double* cam_a, const double* cam_b, int32_t n, int32_t num_tasks, double threshold_px) {
+  S.n = n; S.num_tasks = num_tasks; S.na = N.na; S.nb = N.nb;
+  S.f2 = mean_focal2(cam_a, cam_b); S.thr2 = threshold_px * threshold_px;
+  EPI_TRY(B.alloc(&S.num_inliers, (size_t)num_tasks));
+  EPI_TRY(B.alloc(&S.num_front, (size_t)num_tasks * 4));
+  EPI_TRY(B.alloc(&S.poses_out, (size_t)num_tasks * 6));
+  EPI_TRY(B.alloc(&S.status, (size_t)num_tasks));
+  EPI_TRY(hipMemset(S.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  EPI_TRY(launch_epipolar_score(S, nullptr));
+  return RSBA_OK;
+}
+
+// counts, status and the accepted tasks' poses to the caller's arrays (declined pose slots are left as they are)
+int32_t download_score(const EpiScoreArgs& S, int32_t num_tasks, int32_t* num_inliers, int32_t* num_front, double* poses_out, uint8_t* status, std::vector<uint8_t>& st) {
+  std::vector<double> poses((size_t)num_tasks * 6);
+  st.resize((size_t)num_tasks);
+  EPI_TRY(hipMemcpy(poses.data(), S.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+  EPI_TRY(hipMemcpy(st.data(), S.status, st.size(), hipMemcpyDeviceToHost));
+  EPI_TRY(hipMemcpy(num_inliers, S.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  EPI_TRY(hipMemcpy(num_front, S.num_front, (size_t)num_tasks * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int32_t t = 0; t < num_tasks; ++t) {
+    status[t] = st[(size_t)t];
+    if (st[(size_t)t]) for (int k = 0; k < 6; ++k) poses_out[(size_t)t * 6 + k] = poses[(size_t)t * 6 + k];
+  }
+  return RSBA_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t rsba_epipolar_eight_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                             const int32_t* subsets, int32_t m, int32_t num_tasks, double* E_out, uint8_t* status) {
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiEightArgs A{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  if ((rc = run_eight_point(B, A, N, n, subsets, m, num_tasks))) return rc;
+  std::vector<double> E((size_t)num_tasks * 9);
+  std::vector<uint8_t> st((size_t)num_tasks);
+  EPI_TRY(hipMemcpy(E.data(), A.E_out, E.size() * sizeof(double), hipMemcpyDeviceToHost));
+  EPI_TRY(hipMemcpy(st.data(), A.status, st.size(), hipMemcpyDeviceToHost));
+  for (int32_t t = 0; t < num_tasks; ++t) {
+    status[t] = st[(size_t)t];
+    if (st[(size_t)t]) for (int k = 0; k < 9; ++k) E_out[(size_t)t * 9 + k] = E[(size_t)t * 9 + k];
+  }
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_epipolar_score(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                       const double* E, int32_t num_tasks, double threshold_px, int32_t* num_inliers, int32_t* num_front,
+                                       double* poses_out, uint8_t* status) {
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E || !num_inliers || !num_front || !poses_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_tasks <= 0)");
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiScoreArgs S{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  EPI_TRY(B.upload(&S.E, E, (size_t)num_tasks * 9));
+  if ((rc = run_score(B, S, N, cam_a, cam_b, n, num_tasks, threshold_px))) return rc;
+  std::vector<uint8_t> st;
+  return download_score(S, num_tasks, num_inliers, num_front, poses_out, status, st);
+}
+
+extern "C" int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                            const int32_t* subsets, int32_t m, int32_t num_tasks, double threshold_px, double* E_out, double* poses_out,
+                                            uint8_t* status, int32_t* num_inliers, int32_t* num_front) {
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E_out || !poses_out || !status || !num_inliers || !num_front) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiEightArgs A{};
+  EpiScoreArgs S{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  if ((rc = run_eight_point(B, A, N, n, subsets, m, num_tasks))) return rc;
+  S.E = A.E_out; S.status_in = A.status;   // E stays on the device between the two kernels
+  if ((rc = run_score(B, S, N, cam_a, cam_b, n, num_tasks, threshold_px))) return rc;
+  std::vector<uint8_t> st;
+  if ((rc = download_score(S, num_tasks, num_inliers, num_front, poses_out, status, st))) return rc;
+  std::vector<double> E((size_t)num_tasks * 9);
+  EPI_TRY(hipMemcpy(E.data(), A.E_out, E.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int32_t t = 0; t < num_tasks; ++t)
+    if (st[(size_t)t]) for (int k = 0; k < 9; ++k) E_out[(size_t)t * 9 + k] = E[(size_t)t * 9 + k];
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                         const double* E, double threshold_px, uint8_t* inlier_mask) {
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E || !inlier_mask) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiScoreArgs S{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  S.n = n; S.num_tasks = 1; S.na = N.na; S.nb = N.nb; S.f2 = mean_focal2(cam_a, cam_b); S.thr2 = threshold_px * threshold_px;
+  EPI_TRY(B.upload(&S.E, E, 9));
+  uint8_t* d_mask = nullptr;
+  EPI_TRY(B.alloc(&d_mask, (size_t)n));
+  EPI_TRY(launch_epipolar_inliers(S, d_mask, nullptr));
+  EPI_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+  return RSBA_OK;
+}

@@ -1,0 +1,37 @@
+// Arguments of the two-view kernels (kernels_epipolar.hip); all pointers are device pointers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace rsba {
+
+// epipolar_eight_point_kernel
+struct EpiEightArgs {
+  int n, m, num_tasks;
+  const double* na;              // [n][2] undistorted, normalised image points of frame A (pnp_normalise_kernel)
+  const double* nb;              // [n][2] ... of frame B
+  const int32_t* subsets;        // [num_tasks][m]
+  double* E_out;                 // [num_tasks][9]; declined slots are not written
+  uint8_t* status;               // [num_tasks] 0 declined, 1 solved
+};
+
+// epipolar_score_kernel
+struct EpiScoreArgs {
+  int n, num_tasks;
+  double f2, thr2;               // (mean focal length)^2, threshold_px^2
+  const double* na;              // [n][2]
+  const double* nb;              // [n][2]
+  const double* E;               // [num_tasks][9]
+  const uint8_t* status_in;      // [num_tasks] or null: tasks with 0 here are declined without being read
+  int32_t* num_inliers;          // [num_tasks]
+  int32_t* num_front;            // [num_tasks][4]
+  double* poses_out;             // [num_tasks][6]; declined slots are not written
+  uint8_t* status;               // [num_tasks] 0 declined, 1 scored (may alias status_in)
+};
+
+hipError_t launch_epipolar_eight_point(const EpiEightArgs& args, hipStream_t st);
+hipError_t launch_epipolar_score(const EpiScoreArgs& args, hipStream_t st);
+// mask[i] = correspondence i is an inlier of E [9]
+hipError_t launch_epipolar_inliers(const EpiScoreArgs& args, uint8_t* mask, hipStream_t st);
+
+}  // namespace rsba

@@ -1,0 +1,376 @@
+// Essential-matrix hypotheses of the two-view bootstrap (include/rsba/two_view.hpp: epi_detail::eight_point, decompose, score and what they
+// call — hartley, null_matrix, essential_svd, sampson_inlier, in_front, pnp_detail::eigen3, smallest_eigenvector12, pose_from_rt), for every
+// subset at once.  The host functions are the definition; this file restates them for the device, fp64 throughout, every loop with the
+// host's fixed bound (60 / 40 Jacobi sweeps).
+//   epipolar_eight_point_kernel  one lane per subset, one wave per workgroup.  The 9 x 9 Gram matrix (lower triangle, 45 entries) and the
+//                                81 entries of the accumulated rotations live in LDS, lane-interleaved as pnp_dlt_kernel keeps its own
+//                                (entry e of lane l at [e][l]: conflict-free, and indexable by the run-time (p, q) of a Jacobi rotation).
+//                                126 x 64 doubles = 64 512 bytes per workgroup: within a default launch.  The host's three idle unknowns are
+//                                never rotated (their off-diagonals are zero), so they appear here only as the value 2 trace in the gap test.
+//                                The rotation is applied in its symmetric form, as in pnp_dlt_kernel: the same angles, another operation order.
+//                                The 3 x 3 work is unrolled in registers.
+//   epipolar_score_kernel        one wave per hypothesis: every lane holds the decomposition of the hypothesis (computed once, before the
+//                                loop), the lanes stride over the correspondences, the five counts are sums of ballot popcounts — integers,
+//                                so lane order cannot matter.  Lane 0 writes the counts and the winning candidate's pose.
+//   epipolar_inliers_kernel      one lane per correspondence: the inlier flags of one E
+// An eight-point lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
+#include "epipolar_state.hpp"
+
+namespace rsba {
+
+namespace {
+
+constexpr int kEpiBlock = 64;                 // one wave per workgroup
+constexpr int kTri = 45;                      // lower triangle of 9 x 9
+constexpr int kVec = 81;                      // the eigenvector matrix
+__device__ __forceinline__ int sym(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
+
+// pnp_detail::eigen3 in registers (every index is a compile-time constant after unrolling): values ascending, v[r][k] = component r of the
+// unit eigenvector of val[k]
+__device__ __forceinline__ void eigen3(const double s[6], double val[3], double v[3][3]) {
+  double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[r][k] = r == k ? 1.0 : 0.0;
+  }
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+    if (off < 1e-300) break;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < 3; ++q) {
+        if (fabs(a[p][q]) < 1e-300) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)), cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double akp = a[k][p], akq = a[k][q]; a[k][p] = cs * akp - sn * akq; a[k][q] = sn * akp + cs * akq; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double apk = a[p][k], aqk = a[q][k]; a[p][k] = cs * apk - sn * aqk; a[q][k] = sn * apk + cs * aqk; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double vkp = v[k][p], vkq = v[k][q]; v[k][p] = cs * vkp - sn * vkq; v[k][q] = sn * vkp + cs * vkq; }
+      }
+    }
+  }
+  double d[3] = {a[0][0], a[1][1], a[2][2]};
+#define RSBA_EPI_CSWAP(i, j)                                                                     \
+  if (d[j] < d[i]) {                                                                             \
+    const double td = d[i]; d[i] = d[j]; d[j] = td;                                              \
+    _Pragma("unroll") for (int r = 0; r < 3; ++r) { const double tv = v[r][i]; v[r][i] = v[r][j]; v[r][j] = tv; } \
+  }
+  RSBA_EPI_CSWAP(0, 1) RSBA_EPI_CSWAP(0, 2) RSBA_EPI_CSWAP(1, 2)
+#undef RSBA_EPI_CSWAP
+#pragma unroll
+  for (int r = 0; r < 3; ++r) val[r] = d[r];
+}
+
+// epi_detail::essential_svd: U, V as [column][row]
+__device__ __forceinline__ bool essential_svd(const double E[9], double U[3][3], double V[3][3], double s[2]) {
+  double sm[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    sm[0] += E[3 * r] * E[3 * r]; sm[1] += E[3 * r] * E[3 * r + 1]; sm[2] += E[3 * r] * E[3 * r + 2];
+    sm[3] += E[3 * r + 1] * E[3 * r + 1]; sm[4] += E[3 * r + 1] * E[3 * r + 2]; sm[5] += E[3 * r + 2] * E[3 * r + 2];
+  }
+  double val[3], vec[3][3];
+  eigen3(sm, val, vec);
+  s[0] = sqrt(fmax(0.0, val[2])); s[1] = sqrt(fmax(0.0, val[1]));
+  if (!(s[1] > 1e-6 * s[0])) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { V[0][k] = vec[k][2]; V[1][k] = vec[k][1]; }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) U[c][r] = (E[3 * r] * V[c][0] + E[3 * r + 1] * V[c][1] + E[3 * r + 2] * V[c][2]) / s[c];
+  }
+  U[2][0] = U[0][1] * U[1][2] - U[0][2] * U[1][1]; U[2][1] = U[0][2] * U[1][0] - U[0][0] * U[1][2]; U[2][2] = U[0][0] * U[1][1] - U[0][1] * U[1][0];
+  V[2][0] = V[0][1] * V[1][2] - V[0][2] * V[1][1]; V[2][1] = V[0][2] * V[1][0] - V[0][0] * V[1][2]; V[2][2] = V[0][0] * V[1][1] - V[0][1] * V[1][0];
+  // which way round (v1, v2) runs in their plane: the largest component of v3 (the first such) positive
+  double lead = V[2][0];
+#pragma unroll
+  for (int k = 1; k < 3; ++k) if (fabs(V[2][k]) > fabs(lead)) lead = V[2][k];
+  if (lead < 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { V[1][k] = -V[1][k]; U[1][k] = -U[1][k]; V[2][k] = -V[2][k]; U[2][k] = -U[2][k]; }
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(kEpiBlock) void epipolar_eight_point_kernel(const EpiEightArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int lane = threadIdx.x, t = blockIdx.x * kEpiBlock + lane;
+  if (t >= A.num_tasks) return;                  // (no barrier anywhere below)
+  double* G = smem + lane;                       // G[e * 64]: Gram matrix, lower triangle
+  double* V = smem + kTri * kEpiBlock + lane;    // V[(k * 9 + col) * 64]
+  const int m = A.m;
+  const int32_t* sub = A.subsets + (size_t)t * m;
+  const double* na = A.na;
+  const double* nb = A.nb;
+  A.status[t] = 0;
+  for (int i = 0; i < m; ++i) for (int k = i + 1; k < m; ++k) if (sub[i] == sub[k]) return;
+
+  // ---- hartley ----
+  double ca0 = 0.0, ca1 = 0.0, cb0 = 0.0, cb1 = 0.0, sa = 0.0, sb = 0.0;
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)sub[i];
+    ca0 += na[j] / m; ca1 += na[j + 1] / m; cb0 += nb[j] / m; cb1 += nb[j + 1] / m;
+  }
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)sub[i];
+    sa += hypot(na[j] - ca0, na[j + 1] - ca1) / m; sb += hypot(nb[j] - cb0, nb[j + 1] - cb1) / m;
+  }
+  if (!(sa > 0.0) || !(sb > 0.0)) return;
+  sa /= 1.4142135623730951; sb /= 1.4142135623730951;
+
+  // ---- null_matrix: the Gram matrix of one row per point ----
+  for (int e = 0; e < kTri; ++e) G[e * kEpiBlock] = 0.0;
+  for (int i = 0; i < m; ++i) {
+    const size_t j = 2 * (size_t)sub[i];
+    const double xa = (na[j] - ca0) / sa, ya = (na[j + 1] - ca1) / sa, xb = (nb[j] - cb0) / sb, yb = (nb[j + 1] - cb1) / sb;
+    const double r[9] = {xb * xa, xb * ya, xb, yb * xa, yb * ya, yb, xa, ya, 1.0};
+#pragma unroll
+    for (int a = 0; a < 9; ++a) {
+#pragma unroll
+      for (int b = 0; b <= a; ++b) G[(a * (a + 1) / 2 + b) * kEpiBlock] += r[a] * r[b];
+    }
+  }
+  double big = 0.0;
+  for (int a = 0; a < 9; ++a) big += G[sym(a, a) * kEpiBlock];
+  if (!(big > 0.0)) return;
+
+  // ---- smallest_eigenvector12 on its 9 active unknowns: cyclic Jacobi on the triangle in LDS ----
+  for (int e = 0; e < kVec; ++e) V[e * kEpiBlock] = 0.0;
+  for (int k = 0; k < 9; ++k) V[(k * 9 + k) * kEpiBlock] = 1.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0;
+    for (int i = 1; i < 9; ++i) for (int j = 0; j < i; ++j) { const double g = G[(i * (i + 1) / 2 + j) * kEpiBlock]; off += g * g; }
+    if (off < 1e-30) break;
+#pragma unroll 1
+    for (int p = 0; p < 8; ++p) {
+#pragma unroll 1
+      for (int q = p + 1; q < 9; ++q) {
+        const int ipq = q * (q + 1) / 2 + p, ipp = p * (p + 1) / 2 + p, iqq = q * (q + 1) / 2 + q;
+        const double apq = G[ipq * kEpiBlock];
+        if (fabs(apq) < 1e-300) continue;
+        const double app = G[ipp * kEpiBlock], aqq = G[iqq * kEpiBlock];
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)), cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+        for (int k = 0; k < 9; ++k) {
+          if (k == p || k == q) continue;
+          const int ikp = sym(k, p), ikq = sym(k, q);
+          const double akp = G[ikp * kEpiBlock], akq = G[ikq * kEpiBlock];
+          G[ikp * kEpiBlock] = cs * akp - sn * akq; G[ikq * kEpiBlock] = sn * akp + cs * akq;
+        }
+        G[ipp * kEpiBlock] = app - tt * apq; G[iqq * kEpiBlock] = aqq + tt * apq; G[ipq * kEpiBlock] = 0.0;
+        for (int k = 0; k < 9; ++k) {
+          const double vkp = V[(k * 9 + p) * kEpiBlock], vkq = V[(k * 9 + q) * kEpiBlock];
+          V[(k * 9 + p) * kEpiBlock] = cs * vkp - sn * vkq; V[(k * 9 + q) * kEpiBlock] = sn * vkp + cs * vkq;
+        }
+      }
+    }
+  }
+  int best = 0;
+  double dbest = G[0];
+  for (int i = 1; i < 9; ++i) { const double di = G[sym(i, i) * kEpiBlock]; if (di < dbest) { dbest = di; best = i; } }
+  double second = 0.0, largest = 2.0 * big;      // (the idle unknowns' eigenvalue)
+  bool have_second = false;
+  for (int i = 0; i < 9; ++i) {
+    const double di = G[sym(i, i) * kEpiBlock];
+    if (i != best && (!have_second || di < second)) { second = di; have_second = true; }
+    largest = fmax(largest, di);
+  }
+  if (!(second > 1e-9 * largest) || !(dbest < 0.05 * second)) return;   // a second null direction: a plane, or no baseline
+  double ev[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) ev[k] = V[(k * 9 + best) * kEpiBlock];
+
+  // ---- the normalisation undone, the projection onto the essential manifold, the sign ----
+  double M[9], F[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    M[3 * r] = ev[3 * r] / sa; M[3 * r + 1] = ev[3 * r + 1] / sa;
+    M[3 * r + 2] = ev[3 * r + 2] - (ca0 * ev[3 * r] + ca1 * ev[3 * r + 1]) / sa;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    F[k] = M[k] / sb; F[3 + k] = M[3 + k] / sb;
+    F[6 + k] = M[6 + k] - (cb0 * M[k] + cb1 * M[3 + k]) / sb;
+  }
+  double U[3][3], W[3][3], s[2], out[9];
+  if (!essential_svd(F, U, W, s)) return;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * r + k] = U[0][r] * W[0][k] + U[1][r] * W[1][k];
+  }
+  double lead = out[0];
+#pragma unroll
+  for (int k = 1; k < 9; ++k) if (fabs(out[k]) > fabs(lead)) lead = out[k];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { if (lead < 0) out[k] = -out[k]; finite = finite && isfinite(out[k]); }
+  if (!finite) return;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) A.E_out[(size_t)t * 9 + k] = out[k];
+  A.status[t] = 1;
+}
+
+// the two deciding comparisons: the operations of epi_detail::sampson_inlier / in_front in their order, each rounded on its own
+__device__ __forceinline__ bool sampson_inlier(const double E[9], double xa, double ya, double xb, double yb, double f2, double thr2) {
+#pragma clang fp contract(off)
+  const double l0 = E[0] * xa + E[1] * ya + E[2], l1 = E[3] * xa + E[4] * ya + E[5], l2 = E[6] * xa + E[7] * ya + E[8];
+  const double m0 = E[0] * xb + E[3] * yb + E[6], m1 = E[1] * xb + E[4] * yb + E[7];
+  const double r = xb * l0 + yb * l1 + l2;
+  const double den = l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1;
+  const double d2 = (r * r) / den;
+  return d2 * f2 <= thr2;
+}
+__device__ __forceinline__ bool in_front(const double R[9], const double t[3], double sign, double xa, double ya, double xb, double yb) {
+#pragma clang fp contract(off)
+  const double p0 = R[0] * xa + R[1] * ya + R[2], p1 = R[3] * xa + R[4] * ya + R[5], p2 = R[6] * xa + R[7] * ya + R[8];
+  const double t0 = sign * t[0], t1 = sign * t[1], t2 = sign * t[2];
+  const double pp = p0 * p0 + p1 * p1 + p2 * p2, qq = xb * xb + yb * yb + 1.0, pq = p0 * xb + p1 * yb + p2;
+  const double pt = p0 * t0 + p1 * t1 + p2 * t2, qt = xb * t0 + yb * t1 + t2;
+  const double det = pp * qq - pq * pq;
+  const double za = (pq * qt - qq * pt) / det, zb = (pp * qt - pq * pt) / det;
+  return za > 0.0 && zb > 0.0;
+}
+
+// ceres::AngleAxisRotatePoint, as pnp_detail::rotate
+__device__ __forceinline__ void rotate(const double w[3], const double p[3], double out[3]) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  const double wxp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
+  if (th2 > 2.220446049250313e-16) {
+    const double th = sqrt(th2), c = cos(th), s = sin(th), it = 1.0 / th;
+    const double k[3] = {w[0] * it, w[1] * it, w[2] * it};
+    const double kxp[3] = {wxp[0] * it, wxp[1] * it, wxp[2] * it};
+    const double kp = (k[0] * p[0] + k[1] * p[1] + k[2] * p[2]) * (1.0 - c);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = p[i] * c + kxp[i] * s + k[i] * kp;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = p[i] + wxp[i];
+  }
+}
+// pnp_detail::pose_from_rt
+__device__ __forceinline__ bool pose_from_rt(const double R[9], const double tvec[3], double pose[6]) {
+  double rvec[3];
+  const double tr = R[0] + R[4] + R[8], csn = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0))), th = acos(csn);
+  const double ax[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  const double sn = 0.5 * sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+  if (sn > 1e-8) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rvec[k] = ax[k] * (th / (2.0 * sn));
+  } else if (csn > 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rvec[k] = 0.5 * ax[k];
+  } else {   // a half turn: the axis from the diagonal
+    const double d[3] = {sqrt(fmax(0.0, 0.5 * (R[0] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[4] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[8] + 1.0)))};
+    rvec[0] = th * d[0]; rvec[1] = th * d[1] * (R[1] + R[3] >= 0 ? 1.0 : -1.0); rvec[2] = th * d[2] * (R[2] + R[6] >= 0 ? 1.0 : -1.0);
+  }
+  const double rinv[3] = {-rvec[0], -rvec[1], -rvec[2]}, nt[3] = {-tvec[0], -tvec[1], -tvec[2]};
+  double centre[3];
+  rotate(rinv, nt, centre);
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { pose[k] = rvec[k]; pose[3 + k] = centre[k]; finite = finite && isfinite(rvec[k]) && isfinite(centre[k]); }
+  return finite;
+}
+
+__global__ __launch_bounds__(kEpiBlock) void epipolar_score_kernel(const EpiScoreArgs A) {
+  const int lane = threadIdx.x, t = blockIdx.x;   // (one workgroup per task: every branch on t is uniform across the wave)
+  const bool skip = A.status_in && A.status_in[t] == 0;
+  double E[9], R[2][9], tv[3];
+  bool ok = !skip;
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = A.E[(size_t)t * 9 + k];
+    // ---- epi_detail::decompose ----
+    double U[3][3], V[3][3], s[2];
+    ok = essential_svd(E, U, V, s);
+    if (ok) {
+      const double nt = sqrt(U[2][0] * U[2][0] + U[2][1] * U[2][1] + U[2][2] * U[2][2]);
+      ok = nt > 0.0;
+      bool finite = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) tv[k] = U[2][k] / nt;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double w = U[1][r] * V[0][k] - U[0][r] * V[1][k], z = U[2][r] * V[2][k];
+          R[0][3 * r + k] = w + z; R[1][3 * r + k] = z - w;
+          finite = finite && isfinite(w + z) && isfinite(z - w);
+        }
+      }
+      ok = ok && finite && isfinite(tv[0] + tv[1] + tv[2]);
+    }
+  }
+  int inl = 0, front[4] = {0, 0, 0, 0};
+  if (ok) {
+    for (int base = 0; base < A.n; base += kEpiBlock) {   // (uniform trip count: every lane reaches every ballot)
+      const int i = base + lane;
+      bool in = false, fr[4] = {false, false, false, false};
+      if (i < A.n) {
+        const double xa = A.na[2 * (size_t)i], ya = A.na[2 * (size_t)i + 1], xb = A.nb[2 * (size_t)i], yb = A.nb[2 * (size_t)i + 1];
+        in = sampson_inlier(E, xa, ya, xb, yb, A.f2, A.thr2);
+        if (in) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) fr[c] = in_front(R[c >> 1], tv, (c & 1) ? -1.0 : 1.0, xa, ya, xb, yb);
+        }
+      }
+      inl += __popcll(__ballot(in));
+#pragma unroll
+      for (int c = 0; c < 4; ++c) front[c] += __popcll(__ballot(fr[c]));
+    }
+  }
+  if (lane != 0) return;
+  double pose[6];
+  int best = 0;
+  if (ok) {
+#pragma unroll
+    for (int c = 1; c < 4; ++c) if (front[c] > front[best]) best = c;
+    const double sg = (best & 1) ? -1.0 : 1.0;
+    const double tb[3] = {sg * tv[0], sg * tv[1], sg * tv[2]};
+    double Rb[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rb[k] = (best >> 1) ? R[1][k] : R[0][k];
+    ok = pose_from_rt(Rb, tb, pose);
+  }
+  A.status[t] = ok ? 1 : 0;
+  A.num_inliers[t] = ok ? inl : 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) A.num_front[(size_t)t * 4 + c] = ok ? front[c] : 0;
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) A.poses_out[(size_t)t * 6 + k] = pose[k];
+  }
+}
+
+__global__ __launch_bounds__(256) void epipolar_inliers_kernel(const EpiScoreArgs A, uint8_t* __restrict__ mask) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  double E[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) E[k] = A.E[k];
+  mask[i] = sampson_inlier(E, A.na[2 * (size_t)i], A.na[2 * (size_t)i + 1], A.nb[2 * (size_t)i], A.nb[2 * (size_t)i + 1], A.f2, A.thr2) ? 1 : 0;
+}
+
+}  // namespace
+
+hipError_t launch_epipolar_eight_point(const EpiEightArgs& A, hipStream_t st) {
+  const size_t lds = (size_t)(kTri + kVec) * kEpiBlock * sizeof(double);   // 64 512 bytes
+  hipLaunchKernelGGL(epipolar_eight_point_kernel, dim3((A.num_tasks + kEpiBlock - 1) / kEpiBlock), dim3(kEpiBlock), lds, st, A);
+  return hipGetLastError();
+}
+hipError_t launch_epipolar_score(const EpiScoreArgs& A, hipStream_t st) {
+  hipLaunchKernelGGL(epipolar_score_kernel, dim3(A.num_tasks), dim3(kEpiBlock), 0, st, A);
+  return hipGetLastError();
+}
+hipError_t launch_epipolar_inliers(const EpiScoreArgs& A, uint8_t* mask, hipStream_t st) {
+  hipLaunchKernelGGL(epipolar_inliers_kernel, dim3((A.n + 255) / 256), dim3(256), 0, st, A, mask);
+  return hipGetLastError();
+}
+
+}  // namespace rsba
