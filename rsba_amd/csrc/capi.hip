@@ -13,7 +13,7 @@
 #include <thread>
 #include <vector>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 #include "devmem.hpp"
 
 using namespace rsba;
@@ -25,17 +25,10 @@ int32_t fail(int32_t code, const std::string& msg) { g_last_error = msg; return 
 
 int32_t rsba_set_error(int32_t code, const char* msg) { return fail(code, msg); }
 
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                      std::string(#expr) + ": " + hipGetErrorString(e_));          \
-  } while (0)
-
 template <class T>
 static int32_t dev_alloc(rsba_handle* h, T** p, size_t count) {
   void* q = nullptr;
-  HIP_TRY(rsba::dev_malloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  RSBA_HIP_TRY(rsba::dev_malloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
   h->allocs.push_back(q);
   *p = static_cast<T*>(q);
   return RSBA_OK;
@@ -44,7 +37,7 @@ template <class T>
 static int32_t dev_upload(rsba_handle* h, T** p, const T* src, size_t count) {
   int32_t rc = dev_alloc(h, p, count);
   if (rc) return rc;
-  if (count) HIP_TRY(hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice));
+  if (count) RSBA_HIP_TRY(hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice));
   return RSBA_OK;
 }
 
@@ -190,11 +183,8 @@ int32_t rsba_create(const rsba_problem_desc* d, int32_t device, rsba_handle** ou
     if (d->frame_intrinsics[f] < 0 || d->frame_intrinsics[f] >= d->num_intrinsics) return fail(RSBA_ERR_INVALID_ARGUMENT, "frame_intrinsics out of range");
 
   stage("index check + host copies");
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
+  int32_t rc = rsba_select_device(device);
   if (rc) return rc;
-  if (device < 0 || device >= ndev) return fail(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device));
 
   rsba_handle* h = new rsba_handle();
   h->device = device;
@@ -315,38 +305,38 @@ int32_t rsba_set_stream(rsba_handle* h, void* s) {
 
 int32_t rsba_upload_parameters(rsba_handle* h, const double* poses, const double* points, const double* intr) {
   if (!h) return fail(RSBA_ERR_INVALID_ARGUMENT, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   rsba_covariance_invalidate(h);
   const DeviceProblem& dp = h->dp;
-  if (poses) HIP_TRY(hipMemcpyAsync(dp.poses, poses, (size_t)dp.F * dp.P * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (points) HIP_TRY(hipMemcpyAsync(dp.points, points, (size_t)dp.M * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (intr) HIP_TRY(hipMemcpyAsync(dp.intr, intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (dp.pp_count > 0 && h->pp_host) HIP_TRY(hipMemcpyAsync(dp.pp_value, h->pp_host, 6 * (size_t)dp.pp_count * sizeof(double), hipMemcpyHostToDevice, h->stream));   // the priorPoses blocks are parameters too
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (poses) RSBA_HIP_TRY(hipMemcpyAsync(dp.poses, poses, (size_t)dp.F * dp.P * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (points) RSBA_HIP_TRY(hipMemcpyAsync(dp.points, points, (size_t)dp.M * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (intr) RSBA_HIP_TRY(hipMemcpyAsync(dp.intr, intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (dp.pp_count > 0 && h->pp_host) RSBA_HIP_TRY(hipMemcpyAsync(dp.pp_value, h->pp_host, 6 * (size_t)dp.pp_count * sizeof(double), hipMemcpyHostToDevice, h->stream));   // the priorPoses blocks are parameters too
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   return RSBA_OK;
 }
 
 int32_t rsba_download_parameters(rsba_handle* h, double* poses, double* points, double* intr) {
   if (!h) return fail(RSBA_ERR_INVALID_ARGUMENT, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   const DeviceProblem& dp = h->dp;
-  if (poses) HIP_TRY(hipMemcpyAsync(poses, dp.poses, (size_t)dp.F * dp.P * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (points) HIP_TRY(hipMemcpyAsync(points, dp.points, (size_t)dp.M * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (intr) HIP_TRY(hipMemcpyAsync(intr, dp.intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (poses) RSBA_HIP_TRY(hipMemcpyAsync(poses, dp.poses, (size_t)dp.F * dp.P * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (points) RSBA_HIP_TRY(hipMemcpyAsync(points, dp.points, (size_t)dp.M * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (intr) RSBA_HIP_TRY(hipMemcpyAsync(intr, dp.intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   return RSBA_OK;
 }
 
 static int32_t ensure_jacobians(rsba_handle* h) {
   if (h->dp.jac) return RSBA_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   return dev_alloc(h, &h->dp.jac, 2 * (size_t)h->dp.K * kEvalBlock * h->dp.ntiles);
 }
 
 int32_t rsba_evaluate_device(rsba_handle* h, int32_t with_jacobians) {
   if (!h) return fail(RSBA_ERR_INVALID_ARGUMENT, "null handle");
   if (with_jacobians) { if (int32_t rc = ensure_jacobians(h)) return rc; }
-  HIP_TRY(launch_eval(h->dp, with_jacobians ? kRawJacobian : kResidualOnly, h->stream));
+  RSBA_HIP_TRY(launch_eval(h->dp, with_jacobians ? kRawJacobian : kResidualOnly, h->stream));
   return RSBA_OK;
 }
 
@@ -363,16 +353,16 @@ int32_t rsba_get_device_view(rsba_handle* h, rsba_device_view* v) {
 
 int32_t rsba_time_evaluate(rsba_handle* h, int32_t with_jacobians, int32_t warmup, int32_t iters, double* avg_ms) {
   if (!h || !avg_ms || iters <= 0) return fail(RSBA_ERR_INVALID_ARGUMENT, "bad argument");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   const EvalMode mode = with_jacobians ? kRawJacobian : kResidualOnly;
   if (with_jacobians) { if (int32_t rc = ensure_jacobians(h)) return rc; }
-  for (int i = 0; i < warmup; ++i) HIP_TRY(launch_eval(h->dp, mode, h->stream));
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  for (int i = 0; i < iters; ++i) HIP_TRY(launch_eval(h->dp, mode, h->stream));
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(hipEventSynchronize(h->ev1));
+  for (int i = 0; i < warmup; ++i) RSBA_HIP_TRY(launch_eval(h->dp, mode, h->stream));
+  RSBA_HIP_TRY(hipEventRecord(h->ev0, h->stream));
+  for (int i = 0; i < iters; ++i) RSBA_HIP_TRY(launch_eval(h->dp, mode, h->stream));
+  RSBA_HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  RSBA_HIP_TRY(hipEventSynchronize(h->ev1));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  RSBA_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
   *avg_ms = (double)ms / iters;
   return RSBA_OK;
 }
@@ -380,7 +370,7 @@ int32_t rsba_time_evaluate(rsba_handle* h, int32_t with_jacobians, int32_t warmu
 int32_t rsba_set_motion_priors(rsba_handle* h, int32_t kind, double scale, double inter_frame_ratio, const int32_t* frames, int32_t count) {
   if (!h || kind < 0 || kind > 2 || count < 0 || (count > 0 && !frames)) return fail(RSBA_ERR_INVALID_ARGUMENT, "bad motion prior arguments");
   if (h->solver) return fail(RSBA_ERR_INVALID_ARGUMENT, "rsba_set_motion_priors must precede the first solve / gradient call");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   DeviceProblem& dp = h->dp;
   if (kind == 0 || count == 0) { dp.prior_of = nullptr; dp.prior_kind = 0; h->prior_frames.clear(); h->prior_invalid = 0; return RSBA_OK; }
   if (dp.P != 2) return fail(RSBA_ERR_INVALID_ARGUMENT, "motion priors need two poses per frame (CeresHandler.h:151)");
@@ -390,16 +380,16 @@ int32_t rsba_set_motion_priors(rsba_handle* h, int32_t kind, double scale, doubl
     flags[frames[k]] = 1;
   }
   int32_t* d = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), flags.size() * sizeof(int32_t)));
+  RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), flags.size() * sizeof(int32_t)));
   h->allocs.push_back(d);
-  HIP_TRY(hipMemcpy(d, flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  RSBA_HIP_TRY(hipMemcpy(d, flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   double* part = nullptr; unsigned* ticket = nullptr;
   const size_t nwaves = ((size_t)dp.F + 63) / 64;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&part), 2 * nwaves * sizeof(double)));
+  RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&part), 2 * nwaves * sizeof(double)));
   h->allocs.push_back(part);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ticket), sizeof(unsigned)));
+  RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ticket), sizeof(unsigned)));
   h->allocs.push_back(ticket);
-  HIP_TRY(hipMemset(ticket, 0, sizeof(unsigned)));
+  RSBA_HIP_TRY(hipMemset(ticket, 0, sizeof(unsigned)));
   dp.prior_partial = part; dp.prior_ticket = ticket;
   dp.prior_of = d; dp.prior_kind = kind; dp.prior_scale = scale; dp.prior_ratio = inter_frame_ratio;
   h->prior_frames.assign(frames, frames + count);
@@ -422,7 +412,7 @@ int32_t rsba_set_pose_priors(rsba_handle* h, double rotation, double position, c
     if (pose_blocks[k] < 0 || pose_blocks[k] >= nblocks || used[pose_blocks[k]]) return fail(RSBA_ERR_INVALID_ARGUMENT, "pose prior blocks must be distinct pose blocks f * P + q");
     used[pose_blocks[k]] = 1;
   }
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   dp.pp_count = count; dp.pp_rotation = rotation; dp.pp_position = position; dp.pp_spherical = spherical_pose_block < 0 ? -1 : spherical_pose_block;
   h->pp_blocks.assign(pose_blocks, pose_blocks + count); h->pp_host = prior_values;
   if (count > 0) {
@@ -445,7 +435,7 @@ int32_t rsba_set_global_shutter_frames(rsba_handle* h, const uint8_t* is_global)
   if (h->solver) return fail(RSBA_ERR_INVALID_ARGUMENT, "rsba_set_global_shutter_frames must precede the first solve / gradient call");
   DeviceProblem& dp = h->dp;
   if (dp.P != 2) return fail(RSBA_ERR_INVALID_ARGUMENT, "one-pose frames are flagged inside problems with poses_per_frame = 2");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   // the masks the caller gave (pose_fixed_mask) with the second pose slot of every flagged frame held constant on top
   std::vector<double> mask(h->mask_pose_caller.empty() ? h->mask_pose : h->mask_pose_caller);
   if (h->mask_pose_caller.empty()) h->mask_pose_caller = h->mask_pose;
@@ -458,8 +448,8 @@ int32_t rsba_set_global_shutter_frames(rsba_handle* h, const uint8_t* is_global)
     for (int f = 0; f < dp.F; ++f) if (is_global[f]) for (int k = 0; k < 6; ++k) mask[((size_t)f * 2 + 1) * 6 + k] = 0.0;
   }
   h->mask_pose = mask;
-  HIP_TRY(hipMemcpy(h->d_mask_pose, mask.data(), mask.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.scale_pose, mask.data(), mask.size() * sizeof(double), hipMemcpyHostToDevice));
+  RSBA_HIP_TRY(hipMemcpy(h->d_mask_pose, mask.data(), mask.size() * sizeof(double), hipMemcpyHostToDevice));
+  RSBA_HIP_TRY(hipMemcpy(dp.scale_pose, mask.data(), mask.size() * sizeof(double), hipMemcpyHostToDevice));
   return RSBA_OK;
 }
 
@@ -478,33 +468,33 @@ int32_t rsba_get_inter_frame_ratio(rsba_handle* h, double* ratio) {
 
 int32_t rsba_evaluate(rsba_handle* h, double* cost, double* residuals, double* jacobians, double* gradient, int64_t* num_failed) {
   if (!h) return fail(RSBA_ERR_INVALID_ARGUMENT, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   DeviceProblem& dp = h->dp;
   const int64_t N = dp.N; const int K = dp.K;
   if (jacobians) { if (int32_t rc = ensure_jacobians(h)) return rc; }
-  HIP_TRY(hipMemsetAsync(dp.fail_count, 0, sizeof(int), h->stream));
-  HIP_TRY(launch_eval(dp, jacobians ? kRawJacobian : kResidualOnly, h->stream));
-  HIP_TRY(launch_cost_reduce(dp, h->d_cost2, h->stream));
-  if (dp.prior_of && (h->rank == 0 || h->prior_split)) HIP_TRY(launch_prior_cost(dp, h->d_cost2, h->prior_invalid, h->stream));
-  if (h->rank == 0) HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, h->stream));
+  RSBA_HIP_TRY(hipMemsetAsync(dp.fail_count, 0, sizeof(int), h->stream));
+  RSBA_HIP_TRY(launch_eval(dp, jacobians ? kRawJacobian : kResidualOnly, h->stream));
+  RSBA_HIP_TRY(launch_cost_reduce(dp, h->d_cost2, h->stream));
+  if (dp.prior_of && (h->rank == 0 || h->prior_split)) RSBA_HIP_TRY(launch_prior_cost(dp, h->d_cost2, h->prior_invalid, h->stream));
+  if (h->rank == 0) RSBA_HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, h->stream));
   double c2[2] = {0, 0}; int nfail = 0;
-  HIP_TRY(hipMemcpyAsync(c2, h->d_cost2, sizeof c2, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&nfail, dp.fail_count, sizeof nfail, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(c2, h->d_cost2, sizeof c2, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(&nfail, dp.fail_count, sizeof nfail, hipMemcpyDeviceToHost, h->stream));
   if ((residuals || jacobians) && N > 0) {
     if (!h->d_order) {
-      HIP_TRY(rsba::dev_malloc(reinterpret_cast<void**>(&h->d_order), (size_t)N * sizeof(int64_t)));
+      RSBA_HIP_TRY(rsba::dev_malloc(reinterpret_cast<void**>(&h->d_order), (size_t)N * sizeof(int64_t)));
       h->allocs.push_back(h->d_order);
       ensure_order(h);
-      HIP_TRY(hipMemcpyAsync(h->d_order, h->order.data(), (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(rsba::dev_malloc(reinterpret_cast<void**>(&h->d_rows), (size_t)N * (2 + 2 * (size_t)K) * sizeof(double)));
+      RSBA_HIP_TRY(hipMemcpyAsync(h->d_order, h->order.data(), (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+      RSBA_HIP_TRY(rsba::dev_malloc(reinterpret_cast<void**>(&h->d_rows), (size_t)N * (2 + 2 * (size_t)K) * sizeof(double)));
       h->allocs.push_back(h->d_rows);
     }
     double* d_res = h->d_rows; double* d_jac = h->d_rows + 2 * (size_t)N;
-    HIP_TRY(launch_untile(dp, h->d_order, jacobians != nullptr, d_res, d_jac, h->stream));
-    if (residuals) HIP_TRY(hipMemcpyAsync(residuals, d_res, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (jacobians) HIP_TRY(hipMemcpyAsync(jacobians, d_jac, 2 * (size_t)K * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RSBA_HIP_TRY(launch_untile(dp, h->d_order, jacobians != nullptr, d_res, d_jac, h->stream));
+    if (residuals) RSBA_HIP_TRY(hipMemcpyAsync(residuals, d_res, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (jacobians) RSBA_HIP_TRY(hipMemcpyAsync(jacobians, d_jac, 2 * (size_t)K * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   if (cost) *cost = c2[0] + c2[1];
   if (num_failed) *num_failed = nfail;
   if (gradient) {
@@ -517,24 +507,24 @@ int32_t rsba_evaluate(rsba_handle* h, double* cost, double* residuals, double* j
 
 int32_t rsba_validate_observations(rsba_handle* h, double sq_threshold, double min_distance, uint8_t* valid) {
   if (!h || !valid) return fail(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   const int64_t N = h->dp.N;
   if (N == 0) return RSBA_OK;
   int32_t rc = grow(h, &h->d_flags, &h->flags_cap, N);
   if (rc) return rc;
-  HIP_TRY(launch_validate(h->dp, sq_threshold, min_distance, h->d_flags, h->stream));
+  RSBA_HIP_TRY(launch_validate(h->dp, sq_threshold, min_distance, h->d_flags, h->stream));
   const uint8_t* src = h->d_flags;
   if (!h->identity_order) {   // back to the caller's observation order on the device
     if (!h->d_order) {
       if ((rc = dev_alloc(h, &h->d_order, (size_t)N))) return rc;
-      HIP_TRY(hipMemcpyAsync(h->d_order, h->order.data(), (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+      RSBA_HIP_TRY(hipMemcpyAsync(h->d_order, h->order.data(), (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     }
     if ((rc = grow(h, &h->d_flags_out, &h->flags_out_cap, N))) return rc;
-    HIP_TRY(launch_scatter_flags(h->d_flags, h->d_order, N, h->d_flags_out, h->stream));
+    RSBA_HIP_TRY(launch_scatter_flags(h->d_flags, h->d_order, N, h->d_flags_out, h->stream));
     src = h->d_flags_out;
   }
-  HIP_TRY(hipMemcpyAsync(valid, src, (size_t)N, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(valid, src, (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   return RSBA_OK;
 }
 
@@ -543,18 +533,18 @@ int32_t rsba_reproject(rsba_handle* h, const int32_t* frames, const int32_t* poi
   for (int64_t i = 0; i < n; ++i)
     if (frames[i] < 0 || frames[i] >= h->dp.F || points[i] < 0 || points[i] >= h->dp.M) return fail(RSBA_ERR_INVALID_ARGUMENT, "index out of range");
   if (n <= 0) return RSBA_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   int32_t rc = grow(h, &h->d_pairs, &h->pairs_cap, 2 * n);
   if (rc) return rc;
   if ((rc = grow(h, &h->d_pair_xy, &h->pair_xy_cap, 2 * n))) return rc;
   if ((rc = grow(h, &h->d_flags_out, &h->flags_out_cap, n))) return rc;
   uint8_t* dok = h->d_flags_out;
-  HIP_TRY(hipMemcpyAsync(h->d_pairs, frames, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_pairs + n, points, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(launch_reproject(h->dp, h->d_pairs, h->d_pairs + n, n, h->d_pair_xy, dok, h->stream));
-  HIP_TRY(hipMemcpyAsync(xy_out, h->d_pair_xy, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(ok_out, dok, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(h->d_pairs, frames, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(h->d_pairs + n, points, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  RSBA_HIP_TRY(launch_reproject(h->dp, h->d_pairs, h->d_pairs + n, n, h->d_pair_xy, dok, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(xy_out, h->d_pair_xy, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(ok_out, dok, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   return RSBA_OK;
 }
 

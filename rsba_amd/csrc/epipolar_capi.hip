@@ -6,47 +6,13 @@
 #include <string>
 #include <vector>
 
+#include "capi_util.hpp"
 #include "epipolar_state.hpp"
-#include "handle.hpp"
 #include "pnp_state.hpp"
 
 using namespace rsba;
 
 namespace {
-
-struct DeviceBuffers {
-  std::vector<void*> ptrs;
-  ~DeviceBuffers() { for (void* p : ptrs) (void)hipFree(p); }
-  template <class T> hipError_t upload(const T** out, const T* src, size_t count) {
-    T* p = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) return e;
-    ptrs.push_back(p);
-    *out = p;
-    return count ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-  }
-  template <class T> hipError_t alloc(T** out, size_t count) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(out), (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(*out);
-    return e;
-  }
-};
-
-#define EPI_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t select_device(int32_t device) {
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
-  if (rc) return rc;
-  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-  EPI_TRY(hipSetDevice(device));
-  return RSBA_OK;
-}
 
 int32_t check_points(const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
   if (!cam_a || !cam_b || !xy_a || !xy_b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
@@ -71,9 +37,9 @@ int32_t normalise_both(DeviceBuffers& B, Normalised& N, const double* cam_a, con
     PnpDltArgs D{};
     for (int k = 0; k < 9; ++k) D.cam[k] = cams[side][k];
     D.n = n;
-    EPI_TRY(B.upload(&D.image_points, xy[side], (size_t)n * 2));
-    EPI_TRY(B.alloc(&D.normalised, (size_t)n * 2));
-    EPI_TRY(launch_pnp_normalise(D, nullptr));
+    RSBA_HIP_TRY(B.upload(&D.image_points, xy[side], (size_t)n * 2));
+    RSBA_HIP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
+    RSBA_HIP_TRY(launch_pnp_normalise(D, nullptr));
     *out[side] = D.normalised;
   }
   return RSBA_OK;
@@ -86,11 +52,11 @@ double mean_focal2(const double* cam_a, const double* cam_b) {
 
 int32_t run_eight_point(DeviceBuffers& B, EpiEightArgs& A, const Normalised& N, int32_t n, const int32_t* subsets, int32_t m, int32_t num_tasks) {
   A.n = n; A.m = m; A.num_tasks = num_tasks; A.na = N.na; A.nb = N.nb;
-  EPI_TRY(B.upload(&A.subsets, subsets, (size_t)num_tasks * m));
-  EPI_TRY(B.alloc(&A.E_out, (size_t)num_tasks * 9));
-  EPI_TRY(B.alloc(&A.status, (size_t)num_tasks));
-  EPI_TRY(hipMemset(A.E_out, 0, (size_t)num_tasks * 9 * sizeof(double)));
-  EPI_TRY(launch_epipolar_eight_point(A, nullptr));
+  RSBA_HIP_TRY(B.upload(&A.subsets, subsets, (size_t)num_tasks * m));
+  RSBA_HIP_TRY(B.alloc(&A.E_out, (size_t)num_tasks * 9));
+  RSBA_HIP_TRY(B.alloc(&A.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(A.E_out, 0, (size_t)num_tasks * 9 * sizeof(double)));
+  RSBA_HIP_TRY(launch_epipolar_eight_point(A, nullptr));
   return RSBA_OK;
 }
 
@@ -98,28 +64,20 @@ int32_t run_eight_point(DeviceBuffers& B, EpiEightArgs& A, const Normalised& N, 
 int32_t run_score(DeviceBuffers& B, EpiScoreArgs& S, const Normalised& N, const double* cam_a, const double* cam_b, int32_t n, int32_t num_tasks, double threshold_px) {
   S.n = n; S.num_tasks = num_tasks; S.na = N.na; S.nb = N.nb;
   S.f2 = mean_focal2(cam_a, cam_b); S.thr2 = threshold_px * threshold_px;
-  EPI_TRY(B.alloc(&S.num_inliers, (size_t)num_tasks));
-  EPI_TRY(B.alloc(&S.num_front, (size_t)num_tasks * 4));
-  EPI_TRY(B.alloc(&S.poses_out, (size_t)num_tasks * 6));
-  EPI_TRY(B.alloc(&S.status, (size_t)num_tasks));
-  EPI_TRY(hipMemset(S.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
-  EPI_TRY(launch_epipolar_score(S, nullptr));
+  RSBA_HIP_TRY(B.alloc(&S.num_inliers, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&S.num_front, (size_t)num_tasks * 4));
+  RSBA_HIP_TRY(B.alloc(&S.poses_out, (size_t)num_tasks * 6));
+  RSBA_HIP_TRY(B.alloc(&S.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(S.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  RSBA_HIP_TRY(launch_epipolar_score(S, nullptr));
   return RSBA_OK;
 }
 
 // counts, status and the accepted tasks' poses to the caller's arrays (declined pose slots are left as they are)
 int32_t download_score(const EpiScoreArgs& S, int32_t num_tasks, int32_t* num_inliers, int32_t* num_front, double* poses_out, uint8_t* status, std::vector<uint8_t>& st) {
-  std::vector<double> poses((size_t)num_tasks * 6);
-  st.resize((size_t)num_tasks);
-  EPI_TRY(hipMemcpy(poses.data(), S.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
-  EPI_TRY(hipMemcpy(st.data(), S.status, st.size(), hipMemcpyDeviceToHost));
-  EPI_TRY(hipMemcpy(num_inliers, S.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
-  EPI_TRY(hipMemcpy(num_front, S.num_front, (size_t)num_tasks * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int32_t t = 0; t < num_tasks; ++t) {
-    status[t] = st[(size_t)t];
-    if (st[(size_t)t]) for (int k = 0; k < 6; ++k) poses_out[(size_t)t * 6 + k] = poses[(size_t)t * 6 + k];
-  }
-  return RSBA_OK;
+  RSBA_HIP_TRY(hipMemcpy(num_inliers, S.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(num_front, S.num_front, (size_t)num_tasks * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return download_accepted(S.status, S.poses_out, 6, num_tasks, status, poses_out, st);
 }
 
 }  // namespace
@@ -130,21 +88,14 @@ extern "C" int32_t rsba_epipolar_eight_point(int32_t device, const double* cam_a
   if (rc) return rc;
   if (!E_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
   EpiEightArgs A{};
   if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
   if ((rc = run_eight_point(B, A, N, n, subsets, m, num_tasks))) return rc;
-  std::vector<double> E((size_t)num_tasks * 9);
-  std::vector<uint8_t> st((size_t)num_tasks);
-  EPI_TRY(hipMemcpy(E.data(), A.E_out, E.size() * sizeof(double), hipMemcpyDeviceToHost));
-  EPI_TRY(hipMemcpy(st.data(), A.status, st.size(), hipMemcpyDeviceToHost));
-  for (int32_t t = 0; t < num_tasks; ++t) {
-    status[t] = st[(size_t)t];
-    if (st[(size_t)t]) for (int k = 0; k < 9; ++k) E_out[(size_t)t * 9 + k] = E[(size_t)t * 9 + k];
-  }
-  return RSBA_OK;
+  std::vector<uint8_t> st;
+  return download_accepted(A.status, A.E_out, 9, num_tasks, status, E_out, st);
 }
 
 extern "C" int32_t rsba_epipolar_score(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
@@ -154,12 +105,12 @@ extern "C" int32_t rsba_epipolar_score(int32_t device, const double* cam_a, cons
   if (rc) return rc;
   if (!E || !num_inliers || !num_front || !poses_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if (num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_tasks <= 0)");
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
   EpiScoreArgs S{};
   if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
-  EPI_TRY(B.upload(&S.E, E, (size_t)num_tasks * 9));
+  RSBA_HIP_TRY(B.upload(&S.E, E, (size_t)num_tasks * 9));
   if ((rc = run_score(B, S, N, cam_a, cam_b, n, num_tasks, threshold_px))) return rc;
   std::vector<uint8_t> st;
   return download_score(S, num_tasks, num_inliers, num_front, poses_out, status, st);
@@ -172,7 +123,7 @@ extern "C" int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a,
   if (rc) return rc;
   if (!E_out || !poses_out || !status || !num_inliers || !num_front) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
   EpiEightArgs A{};
@@ -183,11 +134,7 @@ extern "C" int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a,
   if ((rc = run_score(B, S, N, cam_a, cam_b, n, num_tasks, threshold_px))) return rc;
   std::vector<uint8_t> st;
   if ((rc = download_score(S, num_tasks, num_inliers, num_front, poses_out, status, st))) return rc;
-  std::vector<double> E((size_t)num_tasks * 9);
-  EPI_TRY(hipMemcpy(E.data(), A.E_out, E.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int32_t t = 0; t < num_tasks; ++t)
-    if (st[(size_t)t]) for (int k = 0; k < 9; ++k) E_out[(size_t)t * 9 + k] = E[(size_t)t * 9 + k];
-  return RSBA_OK;
+  return download_accepted(nullptr, A.E_out, 9, num_tasks, status, E_out, st);   // (st: the score kernel's, downloaded above)
 }
 
 extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
@@ -195,16 +142,16 @@ extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, co
   int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
   if (rc) return rc;
   if (!E || !inlier_mask) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
   EpiScoreArgs S{};
   if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
   S.n = n; S.num_tasks = 1; S.na = N.na; S.nb = N.nb; S.f2 = mean_focal2(cam_a, cam_b); S.thr2 = threshold_px * threshold_px;
-  EPI_TRY(B.upload(&S.E, E, 9));
+  RSBA_HIP_TRY(B.upload(&S.E, E, 9));
   uint8_t* d_mask = nullptr;
-  EPI_TRY(B.alloc(&d_mask, (size_t)n));
-  EPI_TRY(launch_epipolar_inliers(S, d_mask, nullptr));
-  EPI_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(B.alloc(&d_mask, (size_t)n));
+  RSBA_HIP_TRY(launch_epipolar_inliers(S, d_mask, nullptr));
+  RSBA_HIP_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
   return RSBA_OK;
 }

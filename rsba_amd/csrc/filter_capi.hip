@@ -9,7 +9,7 @@
 #include <cstring>
 #include <string>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 
 using namespace rsba;
 
@@ -18,13 +18,6 @@ hipError_t launch_iota(int32_t* zeros, int32_t* iota, int64_t first, int64_t n, 
 }
 
 namespace {
-
-#define FILTER_TRY(expr)                                                                           \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
 
 // per host thread and device: [cam 9 | poses 12 | points 3n | xy 2n | poses of a frame with more than two: 6 np] doubles in,
 // [xy 2n doubles | flags n bytes] out
@@ -47,22 +40,22 @@ struct Arena {
   ~Arena() { release(); if (stream) (void)hipStreamDestroy(stream); }
   int32_t reserve(int dev, int64_t n, int64_t np) {
     if (dev != device) { release(); if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; } device = dev; }
-    FILTER_TRY(hipSetDevice(dev));
-    if (!stream) FILTER_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    RSBA_HIP_TRY(hipSetDevice(dev));
+    if (!stream) RSBA_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     if (n <= cap && np <= pcap) return RSBA_OK;
     const int64_t c0 = cap, p0 = pcap;
     release(); device = dev;
     int64_t c = std::max<int64_t>(c0, 1024); while (c < n) c *= 2;
     int64_t pc = std::max<int64_t>(p0, 2); while (pc < np) pc *= 2;
-    FILTER_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), (21 + 5 * (size_t)c + 6 * (size_t)pc) * sizeof(double)));
-    FILTER_TRY(hipMalloc(reinterpret_cast<void**>(&d_xy), 2 * (size_t)c * sizeof(double)));
-    FILTER_TRY(hipMalloc(reinterpret_cast<void**>(&d_flags), (size_t)c));
-    FILTER_TRY(hipMalloc(reinterpret_cast<void**>(&d_zero), (size_t)c * sizeof(int32_t)));
-    FILTER_TRY(hipMalloc(reinterpret_cast<void**>(&d_iota), (size_t)c * sizeof(int32_t)));
-    FILTER_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), (21 + 5 * (size_t)c + 6 * (size_t)pc) * sizeof(double)));
-    FILTER_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_xy), 2 * (size_t)c * sizeof(double)));
-    FILTER_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_flags), (size_t)c));
-    FILTER_TRY(launch_iota(d_zero, d_iota, 0, c, stream));
+    RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), (21 + 5 * (size_t)c + 6 * (size_t)pc) * sizeof(double)));
+    RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_xy), 2 * (size_t)c * sizeof(double)));
+    RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_flags), (size_t)c));
+    RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_zero), (size_t)c * sizeof(int32_t)));
+    RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_iota), (size_t)c * sizeof(int32_t)));
+    RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), (21 + 5 * (size_t)c + 6 * (size_t)pc) * sizeof(double)));
+    RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_xy), 2 * (size_t)c * sizeof(double)));
+    RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_flags), (size_t)c));
+    RSBA_HIP_TRY(launch_iota(d_zero, d_iota, 0, c, stream));
     cap = c; pcap = pc;
     return RSBA_OK;
   }
@@ -75,10 +68,8 @@ int32_t stage(Arena& A, DeviceProblem& dp, int32_t device, const double* cam, co
   if (num_poses < 1) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "empty frame");   // (getPose throws, struct/VideoSfM.cc:105)
   if (shutter < 0 || shutter > 2) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "shutter");
   if (shutter != RSBA_SHUTTER_GLOBAL && num_poses == 2 && scanlines[0] == scanlines[1]) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "scanlines[0] == scanlines[1]");
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
+  int32_t rc = rsba_check_device(device);
   if (rc) return rc;
-  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
   if ((rc = A.reserve(device, n, num_poses))) return rc;
   // one or two poses sit in front; the poses of a frame with more ("fullDoF": one per scan line, picked per item by the kernels as
   // getPose does, struct/VideoSfM.cc:118-132) behind the items, still ONE upload
@@ -87,7 +78,7 @@ int32_t stage(Arena& A, DeviceProblem& dp, int32_t device, const double* cam, co
   std::memcpy(A.h_in + pose_off, poses, 6 * (size_t)num_poses * sizeof(double));
   std::memcpy(A.h_in + 21, points, 3 * (size_t)n * sizeof(double));
   if (obs_xy) std::memcpy(A.h_in + 21 + 3 * (size_t)n, obs_xy, 2 * (size_t)n * sizeof(double));
-  FILTER_TRY(hipMemcpyAsync(A.d_in, A.h_in, (items + (num_poses <= 2 ? 0 : 6 * (size_t)num_poses)) * sizeof(double), hipMemcpyHostToDevice, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.d_in, A.h_in, (items + (num_poses <= 2 ? 0 : 6 * (size_t)num_poses)) * sizeof(double), hipMemcpyHostToDevice, A.stream));
   std::memset(&dp, 0, sizeof dp);
   dp.pp_spherical = -1;   // "no SphericalPrior" is -1, not 0 (only the filter kernels see this dp, but a zero would name pose block 0)
   dp.shutter = shutter; dp.scan0 = scanlines[0]; dp.scan1 = scanlines[1]; dp.interp_rotation = interpolate_rotation != 0; dp.calibrated = 1; dp.P = num_poses;
@@ -109,9 +100,9 @@ extern "C" int32_t rsba_validate_frame(int32_t device, const double* cam, const 
   Arena& A = g_arena; DeviceProblem dp;
   int32_t rc = stage(A, dp, device, cam, poses, num_poses, shutter, scanlines, interpolate_rotation, points, obs_xy, n);
   if (rc) return rc;
-  FILTER_TRY(launch_validate(dp, sq_threshold, min_distance, A.d_flags, A.stream));
-  FILTER_TRY(hipMemcpyAsync(A.h_flags, A.d_flags, (size_t)n, hipMemcpyDeviceToHost, A.stream));
-  FILTER_TRY(hipStreamSynchronize(A.stream));
+  RSBA_HIP_TRY(launch_validate(dp, sq_threshold, min_distance, A.d_flags, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.h_flags, A.d_flags, (size_t)n, hipMemcpyDeviceToHost, A.stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(A.stream));
   std::memcpy(valid, A.h_flags, (size_t)n);
   return RSBA_OK;
 }
@@ -124,10 +115,10 @@ extern "C" int32_t rsba_reproject_frame(int32_t device, const double* cam, const
   Arena& A = g_arena; DeviceProblem dp;
   int32_t rc = stage(A, dp, device, cam, poses, num_poses, shutter, scanlines, interpolate_rotation, points, nullptr, n);
   if (rc) return rc;
-  FILTER_TRY(launch_reproject(dp, A.d_zero, A.d_iota, n, A.d_xy, A.d_flags, A.stream));
-  FILTER_TRY(hipMemcpyAsync(A.h_xy, A.d_xy, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, A.stream));
-  FILTER_TRY(hipMemcpyAsync(A.h_flags, A.d_flags, (size_t)n, hipMemcpyDeviceToHost, A.stream));
-  FILTER_TRY(hipStreamSynchronize(A.stream));
+  RSBA_HIP_TRY(launch_reproject(dp, A.d_zero, A.d_iota, n, A.d_xy, A.d_flags, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.h_xy, A.d_xy, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.h_flags, A.d_flags, (size_t)n, hipMemcpyDeviceToHost, A.stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(A.stream));
   std::memcpy(xy_out, A.h_xy, 2 * (size_t)n * sizeof(double));
   std::memcpy(ok_out, A.h_flags, (size_t)n);
   return RSBA_OK;

@@ -15,6 +15,7 @@
 //   epipolar_inliers_kernel      one lane per correspondence: the inlier flags of one E
 // An eight-point lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
 #include "epipolar_state.hpp"
+#include "hyp_math.hpp"
 
 namespace rsba {
 
@@ -23,47 +24,6 @@ namespace {
 constexpr int kEpiBlock = 64;                 // one wave per workgroup
 constexpr int kTri = 45;                      // lower triangle of 9 x 9
 constexpr int kVec = 81;                      // the eigenvector matrix
-__device__ __forceinline__ int sym(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
-
-// pnp_detail::eigen3 in registers (every index is a compile-time constant after unrolling): values ascending, v[r][k] = component r of the
-// unit eigenvector of val[k]
-__device__ __forceinline__ void eigen3(const double s[6], double val[3], double v[3][3]) {
-  double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[r][k] = r == k ? 1.0 : 0.0;
-  }
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-    if (off < 1e-300) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        if (fabs(a[p][q]) < 1e-300) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)), cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double akp = a[k][p], akq = a[k][q]; a[k][p] = cs * akp - sn * akq; a[k][q] = sn * akp + cs * akq; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double apk = a[p][k], aqk = a[q][k]; a[p][k] = cs * apk - sn * aqk; a[q][k] = sn * apk + cs * aqk; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double vkp = v[k][p], vkq = v[k][q]; v[k][p] = cs * vkp - sn * vkq; v[k][q] = sn * vkp + cs * vkq; }
-      }
-    }
-  }
-  double d[3] = {a[0][0], a[1][1], a[2][2]};
-#define RSBA_EPI_CSWAP(i, j)                                                                     \
-  if (d[j] < d[i]) {                                                                             \
-    const double td = d[i]; d[i] = d[j]; d[j] = td;                                              \
-    _Pragma("unroll") for (int r = 0; r < 3; ++r) { const double tv = v[r][i]; v[r][i] = v[r][j]; v[r][j] = tv; } \
-  }
-  RSBA_EPI_CSWAP(0, 1) RSBA_EPI_CSWAP(0, 2) RSBA_EPI_CSWAP(1, 2)
-#undef RSBA_EPI_CSWAP
-#pragma unroll
-  for (int r = 0; r < 3; ++r) val[r] = d[r];
-}
 
 // epi_detail::essential_svd: U, V as [column][row]
 __device__ __forceinline__ bool essential_svd(const double E[9], double U[3][3], double V[3][3], double s[2]) {
@@ -139,48 +99,9 @@ __global__ __launch_bounds__(kEpiBlock) void epipolar_eight_point_kernel(const E
   for (int a = 0; a < 9; ++a) big += G[sym(a, a) * kEpiBlock];
   if (!(big > 0.0)) return;
 
-  // ---- smallest_eigenvector12 on its 9 active unknowns: cyclic Jacobi on the triangle in LDS ----
-  for (int e = 0; e < kVec; ++e) V[e * kEpiBlock] = 0.0;
-  for (int k = 0; k < 9; ++k) V[(k * 9 + k) * kEpiBlock] = 1.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0;
-    for (int i = 1; i < 9; ++i) for (int j = 0; j < i; ++j) { const double g = G[(i * (i + 1) / 2 + j) * kEpiBlock]; off += g * g; }
-    if (off < 1e-30) break;
-#pragma unroll 1
-    for (int p = 0; p < 8; ++p) {
-#pragma unroll 1
-      for (int q = p + 1; q < 9; ++q) {
-        const int ipq = q * (q + 1) / 2 + p, ipp = p * (p + 1) / 2 + p, iqq = q * (q + 1) / 2 + q;
-        const double apq = G[ipq * kEpiBlock];
-        if (fabs(apq) < 1e-300) continue;
-        const double app = G[ipp * kEpiBlock], aqq = G[iqq * kEpiBlock];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)), cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-        for (int k = 0; k < 9; ++k) {
-          if (k == p || k == q) continue;
-          const int ikp = sym(k, p), ikq = sym(k, q);
-          const double akp = G[ikp * kEpiBlock], akq = G[ikq * kEpiBlock];
-          G[ikp * kEpiBlock] = cs * akp - sn * akq; G[ikq * kEpiBlock] = sn * akp + cs * akq;
-        }
-        G[ipp * kEpiBlock] = app - tt * apq; G[iqq * kEpiBlock] = aqq + tt * apq; G[ipq * kEpiBlock] = 0.0;
-        for (int k = 0; k < 9; ++k) {
-          const double vkp = V[(k * 9 + p) * kEpiBlock], vkq = V[(k * 9 + q) * kEpiBlock];
-          V[(k * 9 + p) * kEpiBlock] = cs * vkp - sn * vkq; V[(k * 9 + q) * kEpiBlock] = sn * vkp + cs * vkq;
-        }
-      }
-    }
-  }
-  int best = 0;
-  double dbest = G[0];
-  for (int i = 1; i < 9; ++i) { const double di = G[sym(i, i) * kEpiBlock]; if (di < dbest) { dbest = di; best = i; } }
-  double second = 0.0, largest = 2.0 * big;      // (the idle unknowns' eigenvalue)
-  bool have_second = false;
-  for (int i = 0; i < 9; ++i) {
-    const double di = G[sym(i, i) * kEpiBlock];
-    if (i != best && (!have_second || di < second)) { second = di; have_second = true; }
-    largest = fmax(largest, di);
-  }
-  if (!(second > 1e-9 * largest) || !(dbest < 0.05 * second)) return;   // a second null direction: a plane, or no baseline
+  // ---- smallest_eigenvector12 on its 9 active unknowns (2 big: the idle unknowns' eigenvalue): cyclic Jacobi on the triangle in LDS ----
+  const int best = smallest_eigenvector_lds<9, kEpiBlock>(G, V, 2.0 * big);
+  if (best < 0) return;                          // a second null direction: a plane, or no baseline
   double ev[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) ev[k] = V[(k * 9 + best) * kEpiBlock];
@@ -235,47 +156,6 @@ __device__ __forceinline__ bool in_front(const double R[9], const double t[3], d
   const double det = pp * qq - pq * pq;
   const double za = (pq * qt - qq * pt) / det, zb = (pp * qt - pq * pt) / det;
   return za > 0.0 && zb > 0.0;
-}
-
-// ceres::AngleAxisRotatePoint, as pnp_detail::rotate
-__device__ __forceinline__ void rotate(const double w[3], const double p[3], double out[3]) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double wxp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
-  if (th2 > 2.220446049250313e-16) {
-    const double th = sqrt(th2), c = cos(th), s = sin(th), it = 1.0 / th;
-    const double k[3] = {w[0] * it, w[1] * it, w[2] * it};
-    const double kxp[3] = {wxp[0] * it, wxp[1] * it, wxp[2] * it};
-    const double kp = (k[0] * p[0] + k[1] * p[1] + k[2] * p[2]) * (1.0 - c);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] * c + kxp[i] * s + k[i] * kp;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] + wxp[i];
-  }
-}
-// pnp_detail::pose_from_rt
-__device__ __forceinline__ bool pose_from_rt(const double R[9], const double tvec[3], double pose[6]) {
-  double rvec[3];
-  const double tr = R[0] + R[4] + R[8], csn = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0))), th = acos(csn);
-  const double ax[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-  const double sn = 0.5 * sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-  if (sn > 1e-8) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = ax[k] * (th / (2.0 * sn));
-  } else if (csn > 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = 0.5 * ax[k];
-  } else {   // a half turn: the axis from the diagonal
-    const double d[3] = {sqrt(fmax(0.0, 0.5 * (R[0] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[4] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[8] + 1.0)))};
-    rvec[0] = th * d[0]; rvec[1] = th * d[1] * (R[1] + R[3] >= 0 ? 1.0 : -1.0); rvec[2] = th * d[2] * (R[2] + R[6] >= 0 ? 1.0 : -1.0);
-  }
-  const double rinv[3] = {-rvec[0], -rvec[1], -rvec[2]}, nt[3] = {-tvec[0], -tvec[1], -tvec[2]};
-  double centre[3];
-  rotate(rinv, nt, centre);
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { pose[k] = rvec[k]; pose[3 + k] = centre[k]; finite = finite && isfinite(rvec[k]) && isfinite(centre[k]); }
-  return finite;
 }
 
 __global__ __launch_bounds__(kEpiBlock) void epipolar_score_kernel(const EpiScoreArgs A) {

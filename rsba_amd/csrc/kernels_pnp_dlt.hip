@@ -11,6 +11,7 @@
 //                         set to zero) — the same rotation angles as the host's column-then-row update, a different operation order.
 //   pnp_compact_kernel    gathers the accepted subsets and their poses (both pose slots the same) for pnp_tasks_kernel
 // A lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
+#include "hyp_math.hpp"
 #include "pnp_state.hpp"
 
 namespace rsba {
@@ -20,7 +21,6 @@ namespace {
 constexpr int kDltBlock = 64;                 // one wave per workgroup
 constexpr int kTri = 78;                      // lower triangle of 12 x 12
 constexpr int kVec = 144;                     // the eigenvector matrix
-__device__ __forceinline__ int sym(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
 
 __global__ __launch_bounds__(256) void pnp_normalise_kernel(const PnpDltArgs A) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -38,23 +38,6 @@ __global__ __launch_bounds__(256) void pnp_normalise_kernel(const PnpDltArgs A) 
 
 __device__ __forceinline__ double det3(const double R[9]) {
   return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-}
-
-// ceres::AngleAxisRotatePoint, as pnp_detail::rotate
-__device__ __forceinline__ void rotate(const double w[3], const double p[3], double out[3]) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double wxp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
-  if (th2 > 2.220446049250313e-16) {
-    const double th = sqrt(th2), c = cos(th), s = sin(th), it = 1.0 / th;
-    const double k[3] = {w[0] * it, w[1] * it, w[2] * it};
-    const double kxp[3] = {wxp[0] * it, wxp[1] * it, wxp[2] * it};
-    const double kp = (k[0] * p[0] + k[1] * p[1] + k[2] * p[2]) * (1.0 - c);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] * c + kxp[i] * s + k[i] * kp;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] + wxp[i];
-  }
 }
 
 __global__ __launch_bounds__(kDltBlock) void pnp_dlt_kernel(const PnpDltArgs A) {
@@ -87,7 +70,9 @@ __global__ __launch_bounds__(kDltBlock) void pnp_dlt_kernel(const PnpDltArgs A) 
     const double d0 = ((double)op[j] - c[0]) / scale, d1 = ((double)op[j + 1] - c[1]) / scale, d2 = ((double)op[j + 2] - c[2]) / scale;
     sc[0] += d0 * d0; sc[1] += d0 * d1; sc[2] += d0 * d2; sc[3] += d1 * d1; sc[4] += d1 * d2; sc[5] += d2 * d2;
   }
-  // ---- eigen3: cyclic Jacobi in registers (every index below is a compile-time constant after unrolling) ----
+  // ---- eigen3: cyclic Jacobi in registers (every index below is a compile-time constant after unrolling).  The text of hyp_math.hpp's eigen3,
+  // kept in line: a call in its place changes how the compiler contracts the planar branch's sums of products below (the last bits of
+  // its poses), whichever way the function hands its results back ----
   double val[3], e1[3], e2[3];                   // planar branch: e1 / e2 = eigenvectors of the largest / middle eigenvalue
   {
     double a[3][3] = {{sc[0], sc[1], sc[2]}, {sc[1], sc[3], sc[4]}, {sc[2], sc[4], sc[5]}}, v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -169,47 +154,8 @@ __global__ __launch_bounds__(kDltBlock) void pnp_dlt_kernel(const PnpDltArgs A) 
   }
 
   // ---- smallest_eigenvector12: cyclic Jacobi on the triangle in LDS ----
-  for (int e = 0; e < kVec; ++e) V[e * kDltBlock] = 0.0;
-  for (int k = 0; k < 12; ++k) V[(k * 12 + k) * kDltBlock] = 1.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0;
-    for (int i = 1; i < 12; ++i) for (int j = 0; j < i; ++j) { const double g = G[(i * (i + 1) / 2 + j) * kDltBlock]; off += g * g; }
-    if (off < 1e-30) break;
-#pragma unroll 1
-    for (int p = 0; p < 11; ++p) {
-#pragma unroll 1
-      for (int q = p + 1; q < 12; ++q) {
-        const int ipq = q * (q + 1) / 2 + p, ipp = p * (p + 1) / 2 + p, iqq = q * (q + 1) / 2 + q;
-        const double apq = G[ipq * kDltBlock];
-        if (fabs(apq) < 1e-300) continue;
-        const double app = G[ipp * kDltBlock], aqq = G[iqq * kDltBlock];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)), cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-        for (int k = 0; k < 12; ++k) {
-          if (k == p || k == q) continue;
-          const int ikp = sym(k, p), ikq = sym(k, q);
-          const double akp = G[ikp * kDltBlock], akq = G[ikq * kDltBlock];
-          G[ikp * kDltBlock] = cs * akp - sn * akq; G[ikq * kDltBlock] = sn * akp + cs * akq;
-        }
-        G[ipp * kDltBlock] = app - tt * apq; G[iqq * kDltBlock] = aqq + tt * apq; G[ipq * kDltBlock] = 0.0;
-        for (int k = 0; k < 12; ++k) {
-          const double vkp = V[(k * 12 + p) * kDltBlock], vkq = V[(k * 12 + q) * kDltBlock];
-          V[(k * 12 + p) * kDltBlock] = cs * vkp - sn * vkq; V[(k * 12 + q) * kDltBlock] = sn * vkp + cs * vkq;
-        }
-      }
-    }
-  }
-  int best = 0;
-  double dbest = G[0];
-  for (int i = 1; i < 12; ++i) { const double di = G[sym(i, i) * kDltBlock]; if (di < dbest) { dbest = di; best = i; } }
-  double second = 0.0, largest = 0.0;
-  bool have_second = false;
-  for (int i = 0; i < 12; ++i) {
-    const double di = G[sym(i, i) * kDltBlock];
-    if (i != best && (!have_second || di < second)) { second = di; have_second = true; }
-    largest = fmax(largest, di);
-  }
-  if (!(second > 1e-9 * largest) || !(dbest < 0.05 * second)) return;   // an ambiguous null space is not an initialisation
+  const int best = smallest_eigenvector_lds<12, kDltBlock>(G, V, 0.0);
+  if (best < 0) return;                          // an ambiguous null space is not an initialisation
   double pv[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) pv[k] = V[(k * 12 + best) * kDltBlock];
@@ -281,30 +227,8 @@ __global__ __launch_bounds__(kDltBlock) void pnp_dlt_kernel(const PnpDltArgs A) 
 #pragma unroll
   for (int r = 0; r < 3; ++r) tvec[r] = tp[r] - (R[3 * r] * c[0] + R[3 * r + 1] * c[1] + R[3 * r + 2] * c[2]);
 
-  // ---- pose_from_rt ----
-  double rvec[3];
-  const double tr = R[0] + R[4] + R[8], csn = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0))), th = acos(csn);
-  const double ax[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-  const double sn = 0.5 * sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-  if (sn > 1e-8) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = ax[k] * (th / (2.0 * sn));
-  } else if (csn > 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = 0.5 * ax[k];
-  } else {   // a half turn: the axis from the diagonal
-    const double d[3] = {sqrt(fmax(0.0, 0.5 * (R[0] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[4] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[8] + 1.0)))};
-    rvec[0] = th * d[0]; rvec[1] = th * d[1] * (R[1] + R[3] >= 0 ? 1.0 : -1.0); rvec[2] = th * d[2] * (R[2] + R[6] >= 0 ? 1.0 : -1.0);
-  }
-  // to_pose: (rvec, -R(rvec)^T tvec)
-  const double rinv[3] = {-rvec[0], -rvec[1], -rvec[2]}, nt[3] = {-tvec[0], -tvec[1], -tvec[2]};
-  double centre[3];
-  rotate(rinv, nt, centre);
-  const double pose[6] = {rvec[0], rvec[1], rvec[2], centre[0], centre[1], centre[2]};
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) finite = finite && isfinite(pose[k]);
-  if (!finite) return;
+  double pose[6];
+  if (!pose_from_rt(R, tvec, pose)) return;
 #pragma unroll
   for (int k = 0; k < 6; ++k) A.poses_out[(size_t)t * 6 + k] = pose[k];
   A.status[t] = planar ? 2 : 1;

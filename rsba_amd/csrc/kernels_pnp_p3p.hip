@@ -7,6 +7,7 @@
 //                    and the up to four roots are walked by unrolled loops), so there is no LDS table and no scratch.
 // The image points come from pnp_normalise_kernel (kernels_pnp_dlt.hip), the accepted subsets go on through pnp_compact_kernel.
 // A lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
+#include "hyp_math.hpp"
 #include "pnp_state.hpp"
 
 namespace rsba {
@@ -144,23 +145,6 @@ __device__ __forceinline__ void p3p_rt(const P3pProblem& S, const double e[3][3]
   for (int r = 0; r < 3; ++r) tvec[r] = (Q[0][r] + Q[1][r] + Q[2][r]) / 3.0 - (R[3 * r] * pc[0] + R[3 * r + 1] * pc[1] + R[3 * r + 2] * pc[2]);
 }
 
-// ceres::AngleAxisRotatePoint, as pnp_detail::rotate
-__device__ __forceinline__ void p3p_rotate(const double w[3], const double p[3], double out[3]) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double wxp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
-  if (th2 > 2.220446049250313e-16) {
-    const double th = sqrt(th2), c = cos(th), s = sin(th), it = 1.0 / th;
-    const double k[3] = {w[0] * it, w[1] * it, w[2] * it};
-    const double kxp[3] = {wxp[0] * it, wxp[1] * it, wxp[2] * it};
-    const double kp = (k[0] * p[0] + k[1] * p[1] + k[2] * p[2]) * (1.0 - c);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] * c + kxp[i] * s + k[i] * kp;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = p[i] + wxp[i];
-  }
-}
-
 __global__ __launch_bounds__(kP3pBlock) void pnp_p3p_kernel(const PnpP3pArgs A) {
   const int t = blockIdx.x * kP3pBlock + threadIdx.x;
   if (t >= A.num_tasks) return;
@@ -225,30 +209,8 @@ __global__ __launch_bounds__(kP3pBlock) void pnp_p3p_kernel(const PnpP3pArgs A) 
   }
   if (found == 0) return;
 
-  // ---- pose_from_rt ----
-  const double* R = bestR;
-  double rvec[3];
-  const double trc = R[0] + R[4] + R[8], csn = fmin(1.0, fmax(-1.0, 0.5 * (trc - 1.0))), th = acos(csn);
-  const double ax[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-  const double sn = 0.5 * sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-  if (sn > 1e-8) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = ax[k] * (th / (2.0 * sn));
-  } else if (csn > 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rvec[k] = 0.5 * ax[k];
-  } else {   // a half turn: the axis from the diagonal
-    const double d[3] = {sqrt(fmax(0.0, 0.5 * (R[0] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[4] + 1.0))), sqrt(fmax(0.0, 0.5 * (R[8] + 1.0)))};
-    rvec[0] = th * d[0]; rvec[1] = th * d[1] * (R[1] + R[3] >= 0 ? 1.0 : -1.0); rvec[2] = th * d[2] * (R[2] + R[6] >= 0 ? 1.0 : -1.0);
-  }
-  const double rinv[3] = {-rvec[0], -rvec[1], -rvec[2]}, nt[3] = {-bestT[0], -bestT[1], -bestT[2]};
-  double centre[3];
-  p3p_rotate(rinv, nt, centre);
-  const double pose[6] = {rvec[0], rvec[1], rvec[2], centre[0], centre[1], centre[2]};
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) finite = finite && isfinite(pose[k]);
-  if (!finite) return;
+  double pose[6];
+  if (!pose_from_rt(bestR, bestT, pose)) return;
 #pragma unroll
   for (int k = 0; k < 6; ++k) A.poses_out[(size_t)t * 6 + k] = pose[k];
   A.num_solutions[t] = found;

@@ -9,19 +9,12 @@
 #include <string>
 #include <vector>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 #include "match.hpp"
 
 using namespace rsba;
 
 namespace {
-
-#define MATCH_TRY(expr)                                                                            \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
 
 inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
 
@@ -48,28 +41,28 @@ struct Arena {
   static size_t grow(size_t have, size_t need) { size_t c = std::max<size_t>(have, 1 << 16); while (c < need) c *= 2; return c; }
   int32_t reserve(int dev, size_t in_bytes, size_t out_bytes, size_t tmp_bytes) {
     if (dev != device) { release(); device = dev; }
-    MATCH_TRY(hipSetDevice(dev));
-    if (!stream) MATCH_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (!ev0) MATCH_TRY(hipEventCreate(&ev0));
-    if (!ev1) MATCH_TRY(hipEventCreate(&ev1));
+    RSBA_HIP_TRY(hipSetDevice(dev));
+    if (!stream) RSBA_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (!ev0) RSBA_HIP_TRY(hipEventCreate(&ev0));
+    if (!ev1) RSBA_HIP_TRY(hipEventCreate(&ev1));
     if (in_bytes > in_cap) {
       (void)hipFree(d_in); (void)hipHostFree(h_in); d_in = h_in = nullptr; in_cap = 0;
       const size_t c = grow(in_cap, in_bytes);
-      MATCH_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), c));
-      MATCH_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), c));
+      RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), c));
       in_cap = c;
     }
     if (out_bytes > out_cap) {
       (void)hipFree(d_out); (void)hipHostFree(h_out); d_out = h_out = nullptr; out_cap = 0;
       const size_t c = grow(out_cap, out_bytes);
-      MATCH_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), c));
-      MATCH_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), c));
+      RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), c));
       out_cap = c;
     }
     if (tmp_bytes > tmp_cap) {
       (void)hipFree(d_tmp); d_tmp = nullptr; tmp_cap = 0;
       const size_t c = grow(tmp_cap, tmp_bytes);
-      MATCH_TRY(hipMalloc(reinterpret_cast<void**>(&d_tmp), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_tmp), c));
       tmp_cap = c;
     }
     return RSBA_OK;
@@ -133,10 +126,8 @@ extern "C" int32_t rsba_match_descriptors(int32_t device, const float* desc, int
     std::sort(rg.begin(), rg.end());
     for (size_t i = 1; i < rg.size(); ++i) if (rg[i].first < rg[i - 1].second) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "output ranges of two pairs overlap");
   }
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
+  int32_t rc = rsba_check_device(device);
   if (rc) return rc;
-  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
 
   // work items: (pair, block of 128 queries, range of train tiles)
   const int64_t split = blocks0 ? std::min<int64_t>(kMaxSplit, std::max<int64_t>(1, (kTargetItems + blocks0 - 1) / blocks0)) : 1;
@@ -168,12 +159,12 @@ extern "C" int32_t rsba_match_descriptors(int32_t device, const float* desc, int
   std::memcpy(A.h_in + o_pairs, pairs.data(), NP * sizeof(MatchPair));
   if (NI) std::memcpy(A.h_in + o_items, items.data(), NI * sizeof(MatchItem));
   std::memcpy(A.h_in + o_qs, qstart.data(), (NP + 1) * sizeof(int64_t));
-  MATCH_TRY(hipMemcpyAsync(A.d_in, A.h_in, in.size, hipMemcpyHostToDevice, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.d_in, A.h_in, in.size, hipMemcpyHostToDevice, A.stream));
   // The whole slot range [0, slots_end) is downloaded and handed to the caller.  Slots in gaps between the pairs' ranges are
   // written by no kernel: their index is preset to -1 (all bits set) and their count to 0 here; their DISTANCE stays
   // uninitialised device memory and is set to +inf on the host after the download, wherever the index is negative.
-  MATCH_TRY(hipMemsetAsync(A.d_out, 0xff, o_dist, A.stream));
-  MATCH_TRY(hipMemsetAsync(A.d_out + o_cnt, 0, NS / (size_t)k * sizeof(int32_t), A.stream));
+  RSBA_HIP_TRY(hipMemsetAsync(A.d_out, 0xff, o_dist, A.stream));
+  RSBA_HIP_TRY(hipMemsetAsync(A.d_out + o_cnt, 0, NS / (size_t)k * sizeof(int32_t), A.stream));
 
   MatchArgs a;
   a.desc = reinterpret_cast<const float*>(A.d_in + o_desc);
@@ -188,12 +179,12 @@ extern "C" int32_t rsba_match_descriptors(int32_t device, const float* desc, int
   a.nn_index = reinterpret_cast<int32_t*>(A.d_out + o_idx);
   a.nn_dist = reinterpret_cast<float*>(A.d_out + o_dist);
   a.nn_count = reinterpret_cast<int32_t*>(A.d_out + o_cnt);
-  MATCH_TRY(hipEventRecord(A.ev0, A.stream));
-  MATCH_TRY(launch_match(a, A.stream));
-  MATCH_TRY(hipEventRecord(A.ev1, A.stream));
-  MATCH_TRY(hipMemcpyAsync(A.h_out, A.d_out, out.size, hipMemcpyDeviceToHost, A.stream));
-  MATCH_TRY(hipStreamSynchronize(A.stream));
-  MATCH_TRY(hipEventElapsedTime(&A.last_kernel_ms, A.ev0, A.ev1));
+  RSBA_HIP_TRY(hipEventRecord(A.ev0, A.stream));
+  RSBA_HIP_TRY(launch_match(a, A.stream));
+  RSBA_HIP_TRY(hipEventRecord(A.ev1, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.h_out, A.d_out, out.size, hipMemcpyDeviceToHost, A.stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(A.stream));
+  RSBA_HIP_TRY(hipEventElapsedTime(&A.last_kernel_ms, A.ev0, A.ev1));
   std::memcpy(nn_index, A.h_out + o_idx, NS * sizeof(int32_t));
   std::memcpy(nn_dist, A.h_out + o_dist, NS * sizeof(float));
   std::memcpy(nn_count, A.h_out + o_cnt, NS / (size_t)k * sizeof(int32_t));

@@ -6,46 +6,12 @@
 #include <string>
 #include <vector>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 #include "pnp_state.hpp"
 
 using namespace rsba;
 
 namespace {
-
-struct DeviceBuffers {
-  std::vector<void*> ptrs;
-  ~DeviceBuffers() { for (void* p : ptrs) (void)hipFree(p); }
-  template <class T> hipError_t upload(const T** out, const T* src, size_t count) {
-    T* p = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) return e;
-    ptrs.push_back(p);
-    *out = p;
-    return count ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-  }
-  template <class T> hipError_t alloc(T** out, size_t count) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(out), (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(*out);
-    return e;
-  }
-};
-
-#define PNP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int32_t select_device(int32_t device) {
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
-  if (rc) return rc;
-  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-  PNP_TRY(hipSetDevice(device));
-  return RSBA_OK;
-}
 
 int32_t fill_camera(PnpArgs& A, const double* cam, int32_t shutter, const int32_t* scanlines, float reprojection_error) {
   if (!cam || !scanlines) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
@@ -72,25 +38,25 @@ extern "C" int32_t rsba_pnp_tasks(int32_t device, const double* cam, int32_t shu
   PnpArgs A{};
   int32_t rc = fill_camera(A, cam, shutter, scanlines, reprojection_error);
   if (rc) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   A.n = n; A.m = m; A.num_tasks = num_tasks; A.init_stride = init_stride; A.max_num_iterations = max_num_iterations; A.drop_coincident = drop_coincident;
   DeviceBuffers B;
-  PNP_TRY(B.upload(&A.object_points, object_points, (size_t)n * 3));
-  PNP_TRY(B.upload(&A.image_points, image_points, (size_t)n * 2));
-  PNP_TRY(B.upload(&A.subsets, subsets, (size_t)num_tasks * m));
-  PNP_TRY(B.upload(&A.init_poses, init_poses, init_stride ? (size_t)num_tasks * 12 : 12));
-  PNP_TRY(B.alloc(&A.poses_out, (size_t)num_tasks * 12));
-  PNP_TRY(B.alloc(&A.status, (size_t)num_tasks));
-  PNP_TRY(B.alloc(&A.final_cost, (size_t)num_tasks));
-  PNP_TRY(B.alloc(&A.num_inliers, (size_t)num_tasks));
-  PNP_TRY(hipMemset(A.poses_out, 0, (size_t)num_tasks * 12 * sizeof(double)));
-  PNP_TRY(hipMemset(A.final_cost, 0, (size_t)num_tasks * sizeof(double)));
-  PNP_TRY(hipMemset(A.num_inliers, 0, (size_t)num_tasks * sizeof(int32_t)));
-  PNP_TRY(launch_pnp_tasks(A, nullptr));
-  PNP_TRY(hipMemcpy(poses_out, A.poses_out, (size_t)num_tasks * 12 * sizeof(double), hipMemcpyDeviceToHost));
-  PNP_TRY(hipMemcpy(status, A.status, (size_t)num_tasks, hipMemcpyDeviceToHost));
-  if (final_cost) PNP_TRY(hipMemcpy(final_cost, A.final_cost, (size_t)num_tasks * sizeof(double), hipMemcpyDeviceToHost));
-  if (num_inliers) PNP_TRY(hipMemcpy(num_inliers, A.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(B.upload(&A.object_points, object_points, (size_t)n * 3));
+  RSBA_HIP_TRY(B.upload(&A.image_points, image_points, (size_t)n * 2));
+  RSBA_HIP_TRY(B.upload(&A.subsets, subsets, (size_t)num_tasks * m));
+  RSBA_HIP_TRY(B.upload(&A.init_poses, init_poses, init_stride ? (size_t)num_tasks * 12 : 12));
+  RSBA_HIP_TRY(B.alloc(&A.poses_out, (size_t)num_tasks * 12));
+  RSBA_HIP_TRY(B.alloc(&A.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&A.final_cost, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&A.num_inliers, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(A.poses_out, 0, (size_t)num_tasks * 12 * sizeof(double)));
+  RSBA_HIP_TRY(hipMemset(A.final_cost, 0, (size_t)num_tasks * sizeof(double)));
+  RSBA_HIP_TRY(hipMemset(A.num_inliers, 0, (size_t)num_tasks * sizeof(int32_t)));
+  RSBA_HIP_TRY(launch_pnp_tasks(A, nullptr));
+  RSBA_HIP_TRY(hipMemcpy(poses_out, A.poses_out, (size_t)num_tasks * 12 * sizeof(double), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(status, A.status, (size_t)num_tasks, hipMemcpyDeviceToHost));
+  if (final_cost) RSBA_HIP_TRY(hipMemcpy(final_cost, A.final_cost, (size_t)num_tasks * sizeof(double), hipMemcpyDeviceToHost));
+  if (num_inliers) RSBA_HIP_TRY(hipMemcpy(num_inliers, A.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
   return RSBA_OK;
 }
 
@@ -101,16 +67,16 @@ extern "C" int32_t rsba_pnp_inliers(int32_t device, const double* cam, int32_t s
   PnpArgs A{};
   int32_t rc = fill_camera(A, cam, shutter, scanlines, reprojection_error);
   if (rc) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   A.n = n;
   DeviceBuffers B;
   const double* d_poses = nullptr; uint8_t* d_mask = nullptr;
-  PNP_TRY(B.upload(&A.object_points, object_points, (size_t)n * 3));
-  PNP_TRY(B.upload(&A.image_points, image_points, (size_t)n * 2));
-  PNP_TRY(B.upload(&d_poses, poses, 12));
-  PNP_TRY(B.alloc(&d_mask, (size_t)n));
-  PNP_TRY(launch_pnp_inliers(A, d_poses, d_mask, nullptr));
-  PNP_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(B.upload(&A.object_points, object_points, (size_t)n * 3));
+  RSBA_HIP_TRY(B.upload(&A.image_points, image_points, (size_t)n * 2));
+  RSBA_HIP_TRY(B.upload(&d_poses, poses, 12));
+  RSBA_HIP_TRY(B.alloc(&d_mask, (size_t)n));
+  RSBA_HIP_TRY(launch_pnp_inliers(A, d_poses, d_mask, nullptr));
+  RSBA_HIP_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
   return RSBA_OK;
 }
 
@@ -131,15 +97,15 @@ int32_t run_dlt(DeviceBuffers& B, PnpDltArgs& D, const double* cam, const float*
                 const int32_t* subsets, int32_t m, int32_t num_tasks) {
   for (int k = 0; k < 9; ++k) D.cam[k] = cam[k];
   D.n = n; D.m = m; D.num_tasks = num_tasks;
-  PNP_TRY(B.upload(&D.object_points, object_points, (size_t)n * 3));
-  PNP_TRY(B.upload(&D.image_points, image_points, (size_t)n * 2));
-  PNP_TRY(B.upload(&D.subsets, subsets, (size_t)num_tasks * m));
-  PNP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
-  PNP_TRY(B.alloc(&D.poses_out, (size_t)num_tasks * 6));
-  PNP_TRY(B.alloc(&D.status, (size_t)num_tasks));
-  PNP_TRY(hipMemset(D.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
-  PNP_TRY(launch_pnp_normalise(D, nullptr));
-  PNP_TRY(launch_pnp_dlt(D, nullptr));
+  RSBA_HIP_TRY(B.upload(&D.object_points, object_points, (size_t)n * 3));
+  RSBA_HIP_TRY(B.upload(&D.image_points, image_points, (size_t)n * 2));
+  RSBA_HIP_TRY(B.upload(&D.subsets, subsets, (size_t)num_tasks * m));
+  RSBA_HIP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
+  RSBA_HIP_TRY(B.alloc(&D.poses_out, (size_t)num_tasks * 6));
+  RSBA_HIP_TRY(B.alloc(&D.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(D.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  RSBA_HIP_TRY(launch_pnp_normalise(D, nullptr));
+  RSBA_HIP_TRY(launch_pnp_dlt(D, nullptr));
   return RSBA_OK;
 }
 
@@ -151,7 +117,7 @@ int32_t refine_and_scatter(DeviceBuffers& B, const double* cam, const float* d_o
                            float reprojection_error, double* poses_out, uint8_t* status, double* final_cost, int32_t* num_inliers) {
   // which subsets were accepted: one byte per subset comes back; the poses stay where they are
   std::vector<uint8_t> accepted((size_t)num_tasks);
-  PNP_TRY(hipMemcpy(accepted.data(), start_status, accepted.size(), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(accepted.data(), start_status, accepted.size(), hipMemcpyDeviceToHost));
   std::vector<int32_t> map;
   for (int32_t t = 0; t < num_tasks; ++t) if (accepted[(size_t)t]) map.push_back(t);
   const int32_t count = (int32_t)map.size();
@@ -166,23 +132,23 @@ int32_t refine_and_scatter(DeviceBuffers& B, const double* cam, const float* d_o
     A.n = n; A.m = m; A.num_tasks = count; A.init_stride = 12; A.max_num_iterations = max_num_iterations; A.drop_coincident = 0;
     A.object_points = d_object_points; A.image_points = d_image_points;
     const int32_t* d_map = nullptr; int32_t* d_subsets = nullptr; double* d_init = nullptr;
-    PNP_TRY(B.upload(&d_map, map.data(), (size_t)count));
-    PNP_TRY(B.alloc(&d_subsets, (size_t)count * m));
-    PNP_TRY(B.alloc(&d_init, (size_t)count * 12));
-    PNP_TRY(launch_pnp_compact(d_map, count, m, d_subsets_in, start_poses, d_subsets, d_init, nullptr));
+    RSBA_HIP_TRY(B.upload(&d_map, map.data(), (size_t)count));
+    RSBA_HIP_TRY(B.alloc(&d_subsets, (size_t)count * m));
+    RSBA_HIP_TRY(B.alloc(&d_init, (size_t)count * 12));
+    RSBA_HIP_TRY(launch_pnp_compact(d_map, count, m, d_subsets_in, start_poses, d_subsets, d_init, nullptr));
     A.subsets = d_subsets; A.init_poses = d_init;
-    PNP_TRY(B.alloc(&A.poses_out, (size_t)count * 12));
-    PNP_TRY(B.alloc(&A.status, (size_t)count));
-    PNP_TRY(B.alloc(&A.final_cost, (size_t)count));
-    PNP_TRY(B.alloc(&A.num_inliers, (size_t)count));
-    PNP_TRY(hipMemset(A.poses_out, 0, (size_t)count * 12 * sizeof(double)));
-    PNP_TRY(hipMemset(A.final_cost, 0, (size_t)count * sizeof(double)));
-    PNP_TRY(hipMemset(A.num_inliers, 0, (size_t)count * sizeof(int32_t)));
-    PNP_TRY(launch_pnp_tasks(A, nullptr));
-    PNP_TRY(hipMemcpy(poses.data(), A.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
-    PNP_TRY(hipMemcpy(st.data(), A.status, st.size(), hipMemcpyDeviceToHost));
-    PNP_TRY(hipMemcpy(cost.data(), A.final_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost));
-    PNP_TRY(hipMemcpy(inl.data(), A.num_inliers, inl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(B.alloc(&A.poses_out, (size_t)count * 12));
+    RSBA_HIP_TRY(B.alloc(&A.status, (size_t)count));
+    RSBA_HIP_TRY(B.alloc(&A.final_cost, (size_t)count));
+    RSBA_HIP_TRY(B.alloc(&A.num_inliers, (size_t)count));
+    RSBA_HIP_TRY(hipMemset(A.poses_out, 0, (size_t)count * 12 * sizeof(double)));
+    RSBA_HIP_TRY(hipMemset(A.final_cost, 0, (size_t)count * sizeof(double)));
+    RSBA_HIP_TRY(hipMemset(A.num_inliers, 0, (size_t)count * sizeof(int32_t)));
+    RSBA_HIP_TRY(launch_pnp_tasks(A, nullptr));
+    RSBA_HIP_TRY(hipMemcpy(poses.data(), A.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(hipMemcpy(st.data(), A.status, st.size(), hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(hipMemcpy(cost.data(), A.final_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(hipMemcpy(inl.data(), A.num_inliers, inl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   for (int32_t t = 0; t < num_tasks; ++t) {
     status[t] = 0;
@@ -205,19 +171,12 @@ extern "C" int32_t rsba_pnp_dlt(int32_t device, const double* cam, const float* 
                                 const int32_t* subsets, int32_t m, int32_t num_tasks, double* poses_out, uint8_t* status) {
   int32_t rc = check_dlt_arguments(cam, object_points, image_points, n, subsets, m, num_tasks, poses_out, status);
   if (rc) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   PnpDltArgs D{};
   if ((rc = run_dlt(B, D, cam, object_points, image_points, n, subsets, m, num_tasks))) return rc;
-  std::vector<double> poses((size_t)num_tasks * 6);
-  std::vector<uint8_t> st((size_t)num_tasks);
-  PNP_TRY(hipMemcpy(poses.data(), D.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
-  PNP_TRY(hipMemcpy(st.data(), D.status, st.size(), hipMemcpyDeviceToHost));
-  for (int32_t t = 0; t < num_tasks; ++t) {
-    status[t] = st[(size_t)t];
-    if (st[(size_t)t]) for (int k = 0; k < 6; ++k) poses_out[(size_t)t * 6 + k] = poses[(size_t)t * 6 + k];
-  }
-  return RSBA_OK;
+  std::vector<uint8_t> st;
+  return download_accepted(D.status, D.poses_out, 6, num_tasks, status, poses_out, st);
 }
 
 extern "C" int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* object_points, const float* image_points, int32_t n,
@@ -226,7 +185,7 @@ extern "C" int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, con
   int32_t rc = check_dlt_arguments(cam, object_points, image_points, n, subsets, m, num_tasks, poses_out, status);
   if (rc) return rc;
   if (max_num_iterations < 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (max_num_iterations < 0)");
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   PnpDltArgs D{};
   if ((rc = run_dlt(B, D, cam, object_points, image_points, n, subsets, m, num_tasks))) return rc;
@@ -251,17 +210,17 @@ int32_t run_p3p(DeviceBuffers& B, PnpDltArgs& D, PnpP3pArgs& P, const double* ca
                 const int32_t* subsets, int32_t num_tasks) {
   for (int k = 0; k < 9; ++k) D.cam[k] = cam[k];
   D.n = n; D.m = 4; D.num_tasks = num_tasks;
-  PNP_TRY(B.upload(&D.object_points, object_points, (size_t)n * 3));
-  PNP_TRY(B.upload(&D.image_points, image_points, (size_t)n * 2));
-  PNP_TRY(B.upload(&D.subsets, subsets, (size_t)num_tasks * 4));
-  PNP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
+  RSBA_HIP_TRY(B.upload(&D.object_points, object_points, (size_t)n * 3));
+  RSBA_HIP_TRY(B.upload(&D.image_points, image_points, (size_t)n * 2));
+  RSBA_HIP_TRY(B.upload(&D.subsets, subsets, (size_t)num_tasks * 4));
+  RSBA_HIP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
   P.n = n; P.num_tasks = num_tasks; P.object_points = D.object_points; P.normalised = D.normalised; P.subsets = D.subsets;
-  PNP_TRY(B.alloc(&P.poses_out, (size_t)num_tasks * 6));
-  PNP_TRY(B.alloc(&P.status, (size_t)num_tasks));
-  PNP_TRY(B.alloc(&P.num_solutions, (size_t)num_tasks));
-  PNP_TRY(hipMemset(P.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
-  PNP_TRY(launch_pnp_normalise(D, nullptr));
-  PNP_TRY(launch_pnp_p3p(P, nullptr));
+  RSBA_HIP_TRY(B.alloc(&P.poses_out, (size_t)num_tasks * 6));
+  RSBA_HIP_TRY(B.alloc(&P.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&P.num_solutions, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(P.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  RSBA_HIP_TRY(launch_pnp_normalise(D, nullptr));
+  RSBA_HIP_TRY(launch_pnp_p3p(P, nullptr));
   return RSBA_OK;
 }
 
@@ -271,23 +230,14 @@ extern "C" int32_t rsba_pnp_p3p(int32_t device, const double* cam, const float* 
                                 const int32_t* subsets, int32_t num_tasks, double* poses_out, uint8_t* status, int32_t* num_solutions) {
   int32_t rc = check_p3p_arguments(cam, object_points, image_points, n, subsets, num_tasks, poses_out, status);
   if (rc) return rc;
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   PnpDltArgs D{};
   PnpP3pArgs P{};
   if ((rc = run_p3p(B, D, P, cam, object_points, image_points, n, subsets, num_tasks))) return rc;
-  std::vector<double> poses((size_t)num_tasks * 6);
-  std::vector<uint8_t> st((size_t)num_tasks);
-  std::vector<int32_t> ns((size_t)num_tasks);
-  PNP_TRY(hipMemcpy(poses.data(), P.poses_out, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
-  PNP_TRY(hipMemcpy(st.data(), P.status, st.size(), hipMemcpyDeviceToHost));
-  PNP_TRY(hipMemcpy(ns.data(), P.num_solutions, ns.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int32_t t = 0; t < num_tasks; ++t) {
-    status[t] = st[(size_t)t];
-    if (num_solutions) num_solutions[t] = ns[(size_t)t];
-    if (st[(size_t)t]) for (int k = 0; k < 6; ++k) poses_out[(size_t)t * 6 + k] = poses[(size_t)t * 6 + k];
-  }
-  return RSBA_OK;
+  if (num_solutions) RSBA_HIP_TRY(hipMemcpy(num_solutions, P.num_solutions, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> st;
+  return download_accepted(P.status, P.poses_out, 6, num_tasks, status, poses_out, st);
 }
 
 // rsba_pnp_gs_hypotheses with the minimal solver in the DLT's place: the same steps after the start-pose kernel, for m = 4
@@ -297,7 +247,7 @@ extern "C" int32_t rsba_pnp_gs_hypotheses_p3p(int32_t device, const double* cam,
   int32_t rc = check_p3p_arguments(cam, object_points, image_points, n, subsets, num_tasks, poses_out, status);
   if (rc) return rc;
   if (max_num_iterations < 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (max_num_iterations < 0)");
-  if ((rc = select_device(device))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   PnpDltArgs D{};
   PnpP3pArgs P{};

@@ -24,13 +24,13 @@ namespace rsba {
 
 int32_t reset_scales(rsba_handle* h) {
   const DeviceProblem& dp = h->dp;
-  HIP_TRY(hipMemcpyAsync(dp.scale_pose, h->d_mask_pose, h->mask_pose.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dp.scale_point, h->d_mask_point, h->mask_point.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dp.scale_intr, h->d_mask_intr, h->mask_intr.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(dp.scale_pose, h->d_mask_pose, h->mask_pose.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(dp.scale_point, h->d_mask_point, h->mask_point.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(dp.scale_intr, h->d_mask_intr, h->mask_intr.size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   if (dp.pp_count > 0) {   // the priorPoses blocks are always free: scale 1
     static const std::vector<double> ones(1 << 16, 1.0);
     for (size_t o = 0; o < 6 * (size_t)dp.pp_count; o += ones.size())
-      HIP_TRY(hipMemcpyAsync(dp.pp_scale + o, ones.data(), std::min(ones.size(), 6 * (size_t)dp.pp_count - o) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      RSBA_HIP_TRY(hipMemcpyAsync(dp.pp_scale + o, ones.data(), std::min(ones.size(), 6 * (size_t)dp.pp_count - o) * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   return RSBA_OK;
 }
@@ -71,11 +71,11 @@ DeviceProblem all_priors(const rsba_handle* h) {
 // ride, every rank's gradient maximum over its points behind the payload and the cameras' maximum taken from the summed gradient
 static int32_t exchange_camera_gradient(rsba_handle* h, bool ride) {
   Solver* s = h->solver;
-  HIP_TRY(launch_pack_linearize(h->dp, s->sv, h->d_cost2, h->stream, ride ? h->world : 0));
-  if (ride) HIP_TRY(launch_gradient_max_points(h->dp, s->sv, h->rank, h->stream));
+  RSBA_HIP_TRY(launch_pack_linearize(h->dp, s->sv, h->d_cost2, h->stream, ride ? h->world : 0));
+  if (ride) RSBA_HIP_TRY(launch_gradient_max_points(h->dp, s->sv, h->rank, h->stream));
   if (int32_t rc = exchange(h, s->sv.xbuf, 2 * s->sv.n + 3 + (ride ? h->world : 0), 0, RSBA_EXCHANGE_CAMERA)) return rc;
-  HIP_TRY(launch_unpack_linearize(h->dp, s->sv, h->stream));
-  if (ride) HIP_TRY(launch_gradient_max_cameras(h->dp, s->sv, h->world, h->stream));
+  RSBA_HIP_TRY(launch_unpack_linearize(h->dp, s->sv, h->stream));
+  if (ride) RSBA_HIP_TRY(launch_gradient_max_cameras(h->dp, s->sv, h->world, h->stream));
   return RSBA_OK;
 }
 
@@ -83,35 +83,35 @@ int32_t linearize(rsba_handle* h, bool have_eval, bool want_gradmax) {
   Solver* s = h->solver;
   if (!have_eval) {
     PhaseScope ps(h, RSBA_PHASE_EVAL_LM);
-    HIP_TRY(launch_eval(h->dp, kLmJacobian, h->stream));   // (the cost reduction overwrites dp.fail_count: nothing to clear)
-    HIP_TRY(launch_cost_reduce(h->dp, h->d_cost2, h->stream));
+    RSBA_HIP_TRY(launch_eval(h->dp, kLmJacobian, h->stream));   // (the cost reduction overwrites dp.fail_count: nothing to clear)
+    RSBA_HIP_TRY(launch_cost_reduce(h->dp, h->d_cost2, h->stream));
   }
   {
     PhaseScope ps(h, RSBA_PHASE_CAMERA_BLOCKS);
-    HIP_TRY(launch_camera_blocks(h->dp, s->sv, h->stream));
-    HIP_TRY(launch_intr_blocks(h->dp, s->sv, h->stream));
+    RSBA_HIP_TRY(launch_camera_blocks(h->dp, s->sv, h->stream));
+    RSBA_HIP_TRY(launch_intr_blocks(h->dp, s->sv, h->stream));
   }
   const bool my_priors = owns_motion_priors(h);
   if (my_priors || s->border) {
     PhaseScope ps(h, RSBA_PHASE_PRIORS);
     if (my_priors) {
-      if (!have_eval) HIP_TRY(launch_prior_cost(h->dp, h->d_cost2, h->prior_invalid, h->stream));
-      HIP_TRY(launch_prior_blocks(h->dp, s->sv, s->ucross, h->stream));
+      if (!have_eval) RSBA_HIP_TRY(launch_prior_cost(h->dp, h->d_cost2, h->prior_invalid, h->stream));
+      RSBA_HIP_TRY(launch_prior_blocks(h->dp, s->sv, s->ucross, h->stream));
     }
-    if (s->border) HIP_TRY(launch_prior_border(all_priors(h), s->sv, s->border, s->ratio4, h->stream));   // every rank: from replicated poses
+    if (s->border) RSBA_HIP_TRY(launch_prior_border(all_priors(h), s->sv, s->border, s->ratio4, h->stream));   // every rank: from replicated poses
   }
   if (h->dp.pp_count > 0 || h->dp.pp_spherical >= 0) {   // per-pose priors: replicated terms, contributed by the lead rank;
     PhaseScope ps(h, RSBA_PHASE_PRIORS);                   // the linearisation of the priorPoses coordinates (v0, g0, cross) on every rank: each one steps them itself
-    if (s->sv.lead && !have_eval) HIP_TRY(launch_pose_prior_cost(h->dp, h->d_cost2, h->stream));
-    HIP_TRY(launch_pose_prior_blocks(h->dp, s->sv, s->pp, h->stream));
+    if (s->sv.lead && !have_eval) RSBA_HIP_TRY(launch_pose_prior_cost(h->dp, h->d_cost2, h->stream));
+    RSBA_HIP_TRY(launch_pose_prior_blocks(h->dp, s->sv, s->pp, h->stream));
   }
   {
     PhaseScope ps(h, RSBA_PHASE_POINT_BLOCKS);
-    HIP_TRY(launch_point_blocks(h->dp, s->sv, h->stream));
+    RSBA_HIP_TRY(launch_point_blocks(h->dp, s->sv, h->stream));
   }
   PhaseScope ps(h, RSBA_PHASE_EXCHANGE);
   s->gradmax_done = false;
-  if (!h->allreduce) { HIP_TRY(launch_local_linearize(h->dp, s->sv, h->d_cost2, h->stream)); return RSBA_OK; }   // one rank: nothing to sum
+  if (!h->allreduce) { RSBA_HIP_TRY(launch_local_linearize(h->dp, s->sv, h->d_cost2, h->stream)); return RSBA_OK; }   // one rank: nothing to sum
   // max |g_i| (the gradient test that follows an accepted step) rides in this exchange instead of taking a MAX all-reduce of its own —
   // every collective is tens of microseconds of latency on a node: each rank's maximum over ITS points (they are nobody else's) in a
   // slot of its own behind the payload, the other ranks' slots zero, so the SUM delivers all of them; the cameras' maximum is taken
@@ -126,48 +126,48 @@ int32_t gradient_max(rsba_handle* h) {
   Solver* s = h->solver;
   if (s->gradmax_done) { s->gradmax_done = false; return RSBA_OK; }   // (came with the camera exchange of the linearisation just before)
   PhaseScope ps(h, RSBA_PHASE_OTHER);
-  HIP_TRY(launch_gradient_max(h->dp, s->sv, h->stream));
-  if (s->sv.lead) HIP_TRY(launch_pose_prior_gradmax(h->dp, s->sv, s->pp, h->stream));
+  RSBA_HIP_TRY(launch_gradient_max(h->dp, s->sv, h->stream));
+  if (s->sv.lead) RSBA_HIP_TRY(launch_pose_prior_gradmax(h->dp, s->sv, s->pp, h->stream));
   return exchange(h, s->sv.scalars + kGradMax, 1, 1, RSBA_EXCHANGE_SCALARS);
 }
 
 // reduced camera system S and rhs at the given trust-region radius (point elimination), summed over the ranks
 int32_t reduce_system(rsba_handle* h, double radius) {
   Solver* s = h->solver; const SolverDev& sv = s->sv; hipStream_t st = h->stream;
-  { PhaseScope ps(h, RSBA_PHASE_POINT_FACTOR); HIP_TRY(launch_point_factor(h->dp, sv, radius, st, s->clamp_with_factor ? s->clamp_lo_hi : nullptr)); }
+  { PhaseScope ps(h, RSBA_PHASE_POINT_FACTOR); RSBA_HIP_TRY(launch_point_factor(h->dp, sv, radius, st, s->clamp_with_factor ? s->clamp_lo_hi : nullptr)); }
   {
     PhaseScope ps(h, RSBA_PHASE_PROJECT);
     // A shared intrinsics block at scale (4k cameras: projection 1.03 ms of stores, virtual-record sweep 0.57 ms of fp64): the two passes
     // read the same point factors and write different records — side by side, the sweep on the arming stream (idle here), two events.
     const bool beside = sv.NPF > 0 && sv.nvgroups > 0 && s->mstream && s->ev_fork && h->dp.N >= 2000000 && !std::getenv("RSBA_NO_SIDE_SWEEP") && !project_covers_virtual_records(h->dp, sv);   // (round 5: one fused sweep does both where it applies)
     if (beside) {
-      HIP_TRY(hipEventRecord(s->ev_fork, st));
-      HIP_TRY(hipStreamWaitEvent(s->mstream, s->ev_fork, 0));
-      HIP_TRY(launch_virtual_records(h->dp, sv, s->mstream));
-      HIP_TRY(hipEventRecord(s->ev_join, s->mstream));
+      RSBA_HIP_TRY(hipEventRecord(s->ev_fork, st));
+      RSBA_HIP_TRY(hipStreamWaitEvent(s->mstream, s->ev_fork, 0));
+      RSBA_HIP_TRY(launch_virtual_records(h->dp, sv, s->mstream));
+      RSBA_HIP_TRY(hipEventRecord(s->ev_join, s->mstream));
     }
-    HIP_TRY(launch_project(h->dp, sv, st));
-    if (beside) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
-    else HIP_TRY(launch_virtual_records(h->dp, sv, st));
+    RSBA_HIP_TRY(launch_project(h->dp, sv, st));
+    if (beside) RSBA_HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
+    else RSBA_HIP_TRY(launch_virtual_records(h->dp, sv, st));
   }
   {
     PhaseScope ps(h, RSBA_PHASE_SCHUR);
     // (S needs no clearing: the merge kernel overwrites every tile a tile pair maps to, and the fill-only tiles — zeroed when the
     // plan was built — are never written by anyone: the factorisation keeps its own tiles, the multi-GPU exchange adds zeros)
-    HIP_TRY(launch_schur_blocks(h->dp, sv, radius, st));
+    RSBA_HIP_TRY(launch_schur_blocks(h->dp, sv, radius, st));
     ++s->schur_launches;
-    if (sv.lead || sv.frame_lead) HIP_TRY(launch_pose_prior_reduce(h->dp, sv, s->pp, radius, st));   // the priorPoses blocks leave the system like points (each on the rank that holds its pose's tile)
+    if (sv.lead || sv.frame_lead) RSBA_HIP_TRY(launch_pose_prior_reduce(h->dp, sv, s->pp, radius, st));   // the priorPoses blocks leave the system like points (each on the rank that holds its pose's tile)
   }
   // exchange (2): partial reduced camera systems -> the full one on every rank (then factored redundantly) — unless every rank
   // factors its own part: then only the separators travel, between the two launches of the factorisation (solve_reduced_system)
   if (s->hp.sharded && !s->sharded_off && !s->use_levels) return RSBA_OK;
   PhaseScope ps(h, RSBA_PHASE_EXCHANGE);
-  if (s->hp.sharded && s->ntop_fill) HIP_TRY(launch_zero_tiles(sv.S, s->d_top_fill, s->ntop_fill, st));   // (a sharded solve left its reduced values in the fill-only separator tiles)
+  if (s->hp.sharded && s->ntop_fill) RSBA_HIP_TRY(launch_zero_tiles(sv.S, s->d_top_fill, s->ntop_fill, st));   // (a sharded solve left its reduced values in the fill-only separator tiles)
   if (h->allreduce && s->exch_slots) {   // only the tiles that can be non-zero travel (the fill-in tiles of the layout are zero on every rank)
     const int64_t count = (int64_t)s->exch_tiles * kTile * kTile + sv.npad;
-    HIP_TRY(launch_exchange_pack(sv, s->exch_slots, s->exch_tiles, s->exch_buf, false, st));
+    RSBA_HIP_TRY(launch_exchange_pack(sv, s->exch_slots, s->exch_tiles, s->exch_buf, false, st));
     if (int32_t rc = exchange(h, s->exch_buf, count, 0, RSBA_EXCHANGE_SYSTEM)) return rc;
-    HIP_TRY(launch_exchange_pack(sv, s->exch_slots, s->exch_tiles, s->exch_buf, true, st));
+    RSBA_HIP_TRY(launch_exchange_pack(sv, s->exch_slots, s->exch_tiles, s->exch_buf, true, st));
     return RSBA_OK;
   }
   return exchange(h, sv.S, (int64_t)sv.nslots * kTile * kTile + sv.npad, 0, RSBA_EXCHANGE_SYSTEM);
@@ -179,7 +179,7 @@ int32_t reduce_system(rsba_handle* h, double radius) {
 // the solver's stream waits for a verification still running beside it (before its flag is read, and before the cells it reads are re-armed)
 int32_t await_verification(rsba_handle* h) {
   Solver* s = h->solver;
-  if (s->verify_pending) { HIP_TRY(hipStreamWaitEvent(h->stream, s->ev_verified, 0)); s->verify_pending = false; }
+  if (s->verify_pending) { RSBA_HIP_TRY(hipStreamWaitEvent(h->stream, s->ev_verified, 0)); s->verify_pending = false; }
   return RSBA_OK;
 }
 int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays) {
@@ -190,12 +190,12 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays) {
     // The set of cells the last solve used is released here — everything that reads it has been enqueued on this stream or has been
     // waited for above — and re-armed (every cell empty: all ones) on the side stream while THIS solve runs on the other set.
     const int used = s->cur_cells, now = used ^ 1;
-    HIP_TRY(hipEventRecord(s->ev_released, st));
-    HIP_TRY(hipStreamWaitEvent(s->mstream, s->ev_released, 0));
-    HIP_TRY(hipMemsetAsync(s->cells[used], 0xFF, s->ncells * sizeof(double), s->mstream));
-    HIP_TRY(hipEventRecord(s->ev_armed[used], s->mstream));
+    RSBA_HIP_TRY(hipEventRecord(s->ev_released, st));
+    RSBA_HIP_TRY(hipStreamWaitEvent(s->mstream, s->ev_released, 0));
+    RSBA_HIP_TRY(hipMemsetAsync(s->cells[used], 0xFF, s->ncells * sizeof(double), s->mstream));
+    RSBA_HIP_TRY(hipEventRecord(s->ev_armed[used], s->mstream));
     s->arm_pending[used] = true;
-    if (s->arm_pending[now]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_armed[now], 0)); s->arm_pending[now] = false; }
+    if (s->arm_pending[now]) { RSBA_HIP_TRY(hipStreamWaitEvent(st, s->ev_armed[now], 0)); s->arm_pending[now] = false; }
     s->cur_cells = now;
     double* c = s->cells[now];
     sv.Lf = c + s->cell_off[0]; sv.chol_part = c + s->cell_off[1]; sv.Winv = c + s->cell_off[2]; sv.zv = c + s->cell_off[3]; sv.yv = sv.zv + sv.npad; sv.Xpub = c + s->cell_off[4];
@@ -203,56 +203,56 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays) {
     s->d_dag_args = s->d_dag_args2[now];
     if (s->hp.sharded && !s->sharded_off) {
       // launch A: the columns of this rank's part, from its own partial S — complete for them: every point that sees one of its tiles is here
-      HIP_TRY(launch_chol_dag(sv, s->plan_a, s->d_dag_args_a[now], std::min(s->dag_workgroups, std::max(1, s->plan_a.ntasks)), s->dag_one_per_cu, st));
+      RSBA_HIP_TRY(launch_chol_dag(sv, s->plan_a, s->d_dag_args_a[now], std::min(s->dag_workgroups, std::max(1, s->plan_a.ntasks)), s->dag_one_per_cu, st));
       // exchange (2'): the separators' tiles, each rank's share less what its part subtracts from them, summed over the ranks
       const int64_t count = (int64_t)s->ntop_slots * kTile * kTile + (int64_t)s->ntop_tiles * kTile + (s->hp.two_rhs ? (int64_t)s->ntop_tiles * kTile + 8 : 0);   // (+ the second right-hand side's share: launch A left it behind the rows of the first)
       ps.stop();
       {
         PhaseScope pe(h, RSBA_PHASE_EXCHANGE);
-        HIP_TRY(launch_top_assemble(sv, s->d_top_slots, s->d_top_info, s->d_asm_ptr, s->d_asm_list, s->d_top_tiles, s->ntop_slots, s->topx_buf, st));
+        RSBA_HIP_TRY(launch_top_assemble(sv, s->d_top_slots, s->d_top_info, s->d_asm_ptr, s->d_asm_list, s->d_top_tiles, s->ntop_slots, s->topx_buf, st));
         if (int32_t rc = exchange(h, s->topx_buf, count, 0, RSBA_EXCHANGE_SYSTEM)) return rc;
-        HIP_TRY(launch_top_unpack(sv, s->d_top_slots, s->d_top_info, s->d_top_tiles, s->ntop_slots, s->topx_buf, st));
+        RSBA_HIP_TRY(launch_top_unpack(sv, s->d_top_slots, s->d_top_info, s->d_top_tiles, s->ntop_slots, s->topx_buf, st));
       }
       ps.start();
       // launch B: the separators (every rank alike), forward and backward, then this rank's part backward
-      HIP_TRY(launch_chol_dag(sv, s->plan_b, s->d_dag_args_b[now], std::min(s->dag_workgroups, std::max(1, s->plan_b.ntasks)), s->dag_one_per_cu, st));
+      RSBA_HIP_TRY(launch_chol_dag(sv, s->plan_b, s->d_dag_args_b[now], std::min(s->dag_workgroups, std::max(1, s->plan_b.ntasks)), s->dag_one_per_cu, st));
       // exchange (4): the camera step — every rank contributes the rows of its part, rank 0 the separators'
       ps.stop();
       {
         PhaseScope pe(h, RSBA_PHASE_EXCHANGE);
-        HIP_TRY(launch_step_rows(sv.yv, s->d_row_mine, sv.npad, s->ybuf, st));
+        RSBA_HIP_TRY(launch_step_rows(sv.yv, s->d_row_mine, sv.npad, s->ybuf, st));
         if (int32_t rc = exchange(h, s->ybuf, sv.npad, 0, RSBA_EXCHANGE_STEP)) return rc;
-        HIP_TRY(hipMemcpyAsync(sv.yv, s->ybuf, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st));
+        RSBA_HIP_TRY(hipMemcpyAsync(sv.yv, s->ybuf, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st));
       }
       ps.start();
     } else
-    HIP_TRY(launch_chol_dag(sv, s->plan, s->d_dag_args, s->dag_workgroups, s->dag_one_per_cu, st));
-    if (s->test_corrupt_once) { s->test_corrupt_once = false; HIP_TRY(hipMemsetAsync(sv.yv + (sv.n / 2 / 6) * 6 + 1, 0, sizeof(double), st)); }   // test hook: one entry of the solution (a pose coordinate in mid-video) lost
+    RSBA_HIP_TRY(launch_chol_dag(sv, s->plan, s->d_dag_args, s->dag_workgroups, s->dag_one_per_cu, st));
+    if (s->test_corrupt_once) { s->test_corrupt_once = false; RSBA_HIP_TRY(hipMemsetAsync(sv.yv + (sv.n / 2 / 6) * 6 + 1, 0, sizeof(double), st)); }   // test hook: one entry of the solution (a pose coordinate in mid-video) lost
     if (s->verify_dag) {
       // (rhs_stays: nobody writes sv.rhs before the check has been waited for — the LM iteration without a free ratio; otherwise the check gets a copy)
       const double* b_rhs = sv.rhs;
-      if (s->hp.two_rhs) { HIP_TRY(launch_border_combine(s->verify_b, sv.rhs, s->border, 0.0, sv.npad, st, s->ratio4 + kRtC)); b_rhs = s->verify_b; }   // what was solved for: g - (s eta) b
-      else if (!rhs_stays) { HIP_TRY(hipMemcpyAsync(s->verify_b, sv.rhs, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st)); b_rhs = s->verify_b; }
-      HIP_TRY(hipEventRecord(s->ev_solved, st));
-      HIP_TRY(hipStreamWaitEvent(s->vstream, s->ev_solved, 0));
-      HIP_TRY(launch_chol_verify(sv, s->d_slot_tiles, b_rhs, s->d_verify, s->d_verify + sv.npad, 1e-7, sv.scalars + kDagSuspect, s->vstream,
+      if (s->hp.two_rhs) { RSBA_HIP_TRY(launch_border_combine(s->verify_b, sv.rhs, s->border, 0.0, sv.npad, st, s->ratio4 + kRtC)); b_rhs = s->verify_b; }   // what was solved for: g - (s eta) b
+      else if (!rhs_stays) { RSBA_HIP_TRY(hipMemcpyAsync(s->verify_b, sv.rhs, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st)); b_rhs = s->verify_b; }
+      RSBA_HIP_TRY(hipEventRecord(s->ev_solved, st));
+      RSBA_HIP_TRY(hipStreamWaitEvent(s->vstream, s->ev_solved, 0));
+      RSBA_HIP_TRY(launch_chol_verify(sv, s->d_slot_tiles, b_rhs, s->d_verify, s->d_verify + sv.npad, 1e-7, sv.scalars + kDagSuspect, s->vstream,
                                  s->hp.sharded && !s->sharded_off ? s->d_row_check : nullptr));   // (a rank of a sharded factorisation holds the whole of its part's rows of S, nothing else)
-      HIP_TRY(hipEventRecord(s->ev_verified, s->vstream));
+      RSBA_HIP_TRY(hipEventRecord(s->ev_verified, s->vstream));
       s->verify_pending = true;
     }
   } else {
     for (int l = 0; l < s->hp.nlev; ++l) {
       const int d0 = s->hp.lev_diag_ptr[l], d1 = s->hp.lev_diag_ptr[l + 1], t0 = s->hp.lev_sub_ptr[l], t1 = s->hp.lev_sub_ptr[l + 1];
       const int u0 = s->hp.lev_upd_ptr[l], u1 = s->hp.lev_upd_ptr[l + 1];
-      HIP_TRY(launch_chol_level(sv, s->plan, kTaskUpdate, u0, u1 - u0, st));
-      HIP_TRY(launch_chol_level(sv, s->plan, kTaskDiag, d0, d1 - d0, st));
-      if (s->hp.two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskFwd2, d0, d1 - d0, st));
-      HIP_TRY(launch_chol_level(sv, s->plan, kTaskSub, t0, t1 - t0, st));
+      RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskUpdate, u0, u1 - u0, st));
+      RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskDiag, d0, d1 - d0, st));
+      if (s->hp.two_rhs) RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskFwd2, d0, d1 - d0, st));
+      RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskSub, t0, t1 - t0, st));
     }
-    if (s->hp.two_rhs) HIP_TRY(launch_chol_level(sv, s->plan, kTaskEta, 0, 1, st));
+    if (s->hp.two_rhs) RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskEta, 0, 1, st));
     for (int l = s->hp.nlev - 1; l >= 0; --l) {
       const int d0 = s->hp.lev_diag_ptr[l], d1 = s->hp.lev_diag_ptr[l + 1];
-      HIP_TRY(launch_chol_level(sv, s->plan, kTaskBack, d0, d1 - d0, st));
+      RSBA_HIP_TRY(launch_chol_level(sv, s->plan, kTaskBack, d0, d1 - d0, st));
     }
   }
   return RSBA_OK;
@@ -264,17 +264,17 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays) {
 int32_t solve_again(rsba_handle* h, const double* b2, const double** v_out) {
   Solver* s = h->solver; const SolverDev& sv = s->sv; hipStream_t st = h->stream;
   PhaseScope ps(h, RSBA_PHASE_CHOLESKY);
-  if (!s->use_levels) HIP_TRY(launch_chol_solve(sv, s->plan, s->d_dag_args, b2, s->zy2, s->d_dag_sync + 2, s->dag_workgroups, st));
+  if (!s->use_levels) RSBA_HIP_TRY(launch_chol_solve(sv, s->plan, s->d_dag_args, b2, s->zy2, s->d_dag_sync + 2, s->dag_workgroups, st));
   else {   // the same tasks, one launch per level: no polling (what a suspect persistent result is redone with)
-    for (int l = 0; l < s->hp.nlev; ++l) HIP_TRY(launch_chol_solve_level(sv, s->plan, false, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
-    for (int l = s->hp.nlev - 1; l >= 0; --l) HIP_TRY(launch_chol_solve_level(sv, s->plan, true, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
+    for (int l = 0; l < s->hp.nlev; ++l) RSBA_HIP_TRY(launch_chol_solve_level(sv, s->plan, false, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
+    for (int l = s->hp.nlev - 1; l >= 0; --l) RSBA_HIP_TRY(launch_chol_solve_level(sv, s->plan, true, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
   }
   *v_out = s->zy2 + sv.npad;
   if (!s->use_levels && s->verify_dag) {
     if (int32_t rc = await_verification(h)) return rc;   // (the accumulators of the check are shared)
     SolverDev sv2 = sv;
     sv2.yv = s->zy2 + sv.npad;
-    HIP_TRY(launch_chol_verify(sv2, s->d_slot_tiles, b2, s->d_verify, s->d_verify + sv.npad, 1e-7, sv.scalars + kDagSuspect, st));
+    RSBA_HIP_TRY(launch_chol_verify(sv2, s->d_slot_tiles, b2, s->d_verify, s->d_verify + sv.npad, 1e-7, sv.scalars + kDagSuspect, st));
   }
   return RSBA_OK;
 }
@@ -311,15 +311,15 @@ static int32_t solve_reduced_pcg(rsba_handle* h) {
   const PcgDev& pc = s->pcg.dev;
   const rsba_linear_solver_options& lo = h->lin_opt;
   const PcgRule rule{lo.min_iterations, lo.max_iterations, lo.eta, lo.r_tolerance};
-  HIP_TRY(launch_pcg_begin(sv, pc, st));
+  RSBA_HIP_TRY(launch_pcg_begin(sv, pc, st));
   double sc[kPcgScSize] = {};
   int enqueued = 0, flip = 0, chunk = 8;
   for (;;) {
     const int n = std::min(chunk, lo.max_iterations - enqueued);
-    for (int k = 0; k < n; ++k) { HIP_TRY(launch_pcg_iteration(sv, pc, rule, flip, st)); flip ^= 1; }
+    for (int k = 0; k < n; ++k) { RSBA_HIP_TRY(launch_pcg_iteration(sv, pc, rule, flip, st)); flip ^= 1; }
     enqueued += n;
-    HIP_TRY(hipMemcpyAsync(sc, pc.sc, sizeof sc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RSBA_HIP_TRY(hipMemcpyAsync(sc, pc.sc, sizeof sc, hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipStreamSynchronize(st));
     if (sc[kPcgDone] != 0.0 || enqueued >= lo.max_iterations) break;
     chunk = std::min(2 * chunk, 64);
   }
@@ -340,24 +340,24 @@ static int32_t solve_reduced_pcg(rsba_handle* h) {
 // ratio == nullptr with a two-column plan: the device-side loop — the ratio's scalars are on the device already (ratio_prepare_ctl).
 int32_t factor_and_solve(rsba_handle* h, double radius, RatioStep* ratio) {
   Solver* s = h->solver; const SolverDev& sv = s->sv; hipStream_t st = h->stream;
-  if (ratio) HIP_TRY(launch_ratio_prepare(s->ratio4, ratio->diag, ratio->gs, ratio->scale, st));
+  if (ratio) RSBA_HIP_TRY(launch_ratio_prepare(s->ratio4, ratio->diag, ratio->gs, ratio->scale, st));
   int32_t rc = reduce_system(h, radius);
   if (rc) return rc;
   if (s->pcg.on) {   // the iterative solver: no factor, no verification — its own residual is its check
     if ((rc = solve_reduced_pcg(h))) return rc;
     s->sv.step = s->pcg.dev.y;
     PhaseScope ps(h, RSBA_PHASE_BACK_SUBSTITUTE);
-    HIP_TRY(launch_back_substitute(h->dp, sv, st));
+    RSBA_HIP_TRY(launch_back_substitute(h->dp, sv, st));
     return RSBA_OK;
   }
   if ((rc = solve_reduced_system(h, /*rhs_stays=*/!s->hp.two_rhs))) return rc;
   if (ratio) {
-    HIP_TRY(hipMemcpyAsync(&ratio->eta, s->ratio4 + kRtEta, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RSBA_HIP_TRY(hipMemcpyAsync(&ratio->eta, s->ratio4 + kRtEta, sizeof(double), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipStreamSynchronize(st));
   }
   s->sv.step = sv.yv;   // the camera step is read where the solve left it (the cells of this solve stay armed until the next one)
   PhaseScope ps(h, RSBA_PHASE_BACK_SUBSTITUTE);
-  HIP_TRY(launch_back_substitute(h->dp, sv, st));
+  RSBA_HIP_TRY(launch_back_substitute(h->dp, sv, st));
   return RSBA_OK;
 }
 
@@ -367,8 +367,8 @@ int32_t factor_and_solve(rsba_handle* h, double radius, RatioStep* ratio) {
 // of the second kind writes its own entries only, so what the first kind left elsewhere goes here
 int32_t rsba_solver_loss_changed(rsba_handle* h) {
   if (!h || !h->solver || !h->solver->ucross) return RSBA_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipMemsetAsync(h->solver->ucross, 0, h->solver->ucross_len * sizeof(double), h->stream));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipMemsetAsync(h->solver->ucross, 0, h->solver->ucross_len * sizeof(double), h->stream));
   return RSBA_OK;
 }
 
@@ -379,14 +379,14 @@ int32_t rsba_gradient(rsba_handle* h, double* g) {
   Solver* s = h->solver; const DeviceProblem& dp = h->dp;
   if ((rc = reset_scales(h))) return rc;
   if ((rc = linearize(h))) return rc;
-  HIP_TRY(launch_unscaled_gradient(dp, s->sv, s->d_gpose, s->d_gpoint, h->stream));
+  RSBA_HIP_TRY(launch_unscaled_gradient(dp, s->sv, s->d_gpose, s->d_gpoint, h->stream));
   const size_t npose = (size_t)dp.F * dp.P * 6, npt = (size_t)dp.M * 3;
-  HIP_TRY(hipMemcpyAsync(g, s->d_gpose, npose * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(g + npose, s->d_gpoint, npt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(g, s->d_gpose, npose * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(g + npose, s->d_gpoint, npt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::fill(g + npose + npt, g + npose + npt + (size_t)dp.NI * 9, 0.0);
   for (int c = 0; c < s->sv.NIB; ++c)   // the 9 coordinates of block c sit at the front of its pseudo frames
-    HIP_TRY(hipMemcpyAsync(g + npose + npt + (size_t)c * 9, s->d_gpose + npose + (size_t)c * s->sv.NPF * s->sv.CD, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+    RSBA_HIP_TRY(hipMemcpyAsync(g + npose + npt + (size_t)c * 9, s->d_gpose + npose + (size_t)c * s->sv.NPF * s->sv.CD, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   return RSBA_OK;
 }
 
@@ -451,13 +451,13 @@ extern "C" const char* rsba_phase_name(int32_t phase) {
 }
 extern "C" int32_t rsba_get_plan_stats(rsba_handle* h, rsba_plan_stats* out) {
   if (!h || !out) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   int32_t rc = build_solver(h);
   if (rc) return rc;
   *out = h->solver->stats;
   unsigned long long issued = 0;
-  HIP_TRY(hipMemcpyAsync(&issued, h->solver->sv.schur_mfma_count, sizeof issued, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(&issued, h->solver->sv.schur_mfma_count, sizeof issued, hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   out->schur_mfma_issued = (int64_t)issued; out->schur_launches = h->solver->schur_launches;
   return RSBA_OK;
 }
@@ -466,7 +466,7 @@ extern "C" int32_t rsba_sync_block_structure(rsba_handle* h) {
   if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
   if (h->solver) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "rsba_sync_block_structure must precede the first solve / gradient call");
   if (!h->allreduce) return RSBA_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   const size_t F = (size_t)h->dp.F, M = (size_t)h->dp.M, count = F * F + F + M;
   std::vector<uint8_t> mask(F * F); std::vector<int64_t> cnt(F);
   int32_t rc = rsba_get_block_structure(h, mask.data(), cnt.data());
@@ -477,7 +477,7 @@ extern "C" int32_t rsba_sync_block_structure(rsba_handle* h) {
   for (size_t f = 0; f < F; ++f) host[F * F + f] = (double)cnt[f];
   for (int64_t i = 0; i < h->dp.N; ++i) host[F * F + F + (size_t)h->obs_point[i]] = 1.0;
   double* dev = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), count * sizeof(double)));
+  RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), count * sizeof(double)));
   hipError_t e = hipMemcpyAsync(dev, host.data(), count * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) { rc = exchange(h, dev, (int64_t)count, 0, RSBA_EXCHANGE_SETUP); if (rc) { (void)hipFree(dev); return rc; } }
   if (e == hipSuccess) e = hipMemcpyAsync(host.data(), dev, count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -493,18 +493,18 @@ extern "C" int32_t rsba_sync_block_structure(rsba_handle* h) {
 
 extern "C" int32_t rsba_normal_equations(rsba_handle* h, double* U, double* gc, double* V, double* gp) {
   if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver; const DeviceProblem& dp = h->dp; const int CD = s->sv.CD;
   if ((rc = reset_scales(h))) return rc;
   if ((rc = linearize(h))) return rc;
-  if (U) HIP_TRY(hipMemcpyAsync(U, s->sv.U, (size_t)dp.F * CD * CD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (gc) HIP_TRY(hipMemcpyAsync(gc, s->sv.gc, (size_t)dp.F * CD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (U) RSBA_HIP_TRY(hipMemcpyAsync(U, s->sv.U, (size_t)dp.F * CD * CD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (gc) RSBA_HIP_TRY(hipMemcpyAsync(gc, s->sv.gc, (size_t)dp.F * CD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::vector<double> v6;
-  if (V) { v6.resize((size_t)dp.M * 6); HIP_TRY(hipMemcpyAsync(v6.data(), s->sv.V, v6.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
-  if (gp) HIP_TRY(hipMemcpyAsync(gp, s->sv.gp, (size_t)dp.M * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (V) { v6.resize((size_t)dp.M * 6); RSBA_HIP_TRY(hipMemcpyAsync(v6.data(), s->sv.V, v6.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+  if (gp) RSBA_HIP_TRY(hipMemcpyAsync(gp, s->sv.gp, (size_t)dp.M * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));
   if (V) for (int j = 0; j < dp.M; ++j) {
     const double* v = &v6[(size_t)j * 6]; double* o = V + (size_t)j * 9;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[1]; o[4] = v[3]; o[5] = v[4]; o[6] = v[2]; o[7] = v[4]; o[8] = v[5];
@@ -571,9 +571,9 @@ struct LmRun {
 };
 
 int32_t LmRun::read_back() {
-  HIP_TRY(hipMemcpyAsync(host_sc, sv.scalars, sizeof host_sc, hipMemcpyDeviceToHost, st));
-  if (free_ratio) HIP_TRY(hipMemcpyAsync(ratio_hg, s->ratio4, sizeof ratio_hg, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  RSBA_HIP_TRY(hipMemcpyAsync(host_sc, sv.scalars, sizeof host_sc, hipMemcpyDeviceToHost, st));
+  if (free_ratio) RSBA_HIP_TRY(hipMemcpyAsync(ratio_hg, s->ratio4, sizeof ratio_hg, hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipStreamSynchronize(st));
   if (s->timer.on) s->timer.resolve();
   if (s->xtimer.on) s->xtimer.resolve();
   cost2[0] = host_sc[kCost]; cost2[1] = host_sc[kFixedCost];
@@ -588,16 +588,16 @@ int32_t LmRun::finish(int32_t term) {
   (void)reset_scales(h);
   const size_t npose = (size_t)dp.F * dp.P * 6, npt = (size_t)dp.M * 3;
   if (h->allreduce && h->world > 1) {   // every rank leaves with the complete point array: each point from its owner
-    HIP_TRY(launch_own_points(dp, sv, s->merge_buf, st));
+    RSBA_HIP_TRY(launch_own_points(dp, sv, s->merge_buf, st));
     int32_t rc2 = exchange(h, s->merge_buf, 4 * (int64_t)dp.M, 0, RSBA_EXCHANGE_POINTS);
     if (rc2) return rc2;
-    HIP_TRY(launch_merge_points(dp, s->merge_buf, st));
+    RSBA_HIP_TRY(launch_merge_points(dp, s->merge_buf, st));
   }
-  HIP_TRY(hipMemcpyAsync(h->desc.poses, dp.poses, npose * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h->desc.points, dp.points, npt * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (!dp.calibrated) HIP_TRY(hipMemcpyAsync(h->desc.intrinsics, dp.intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (dp.pp_count > 0 && h->pp_host) HIP_TRY(hipMemcpyAsync(h->pp_host, dp.pp_value, 6 * (size_t)dp.pp_count * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  RSBA_HIP_TRY(hipMemcpyAsync(h->desc.poses, dp.poses, npose * sizeof(double), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipMemcpyAsync(h->desc.points, dp.points, npt * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (!dp.calibrated) RSBA_HIP_TRY(hipMemcpyAsync(h->desc.intrinsics, dp.intr, (size_t)dp.NI * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (dp.pp_count > 0 && h->pp_host) RSBA_HIP_TRY(hipMemcpyAsync(h->pp_host, dp.pp_value, 6 * (size_t)dp.pp_count * sizeof(double), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipStreamSynchronize(st));
   if (s->timer.on) { s->timer.resolve(); s->timer.on = false; }
   if (s->xtimer.on) { s->xtimer.resolve(); s->xtimer.on = false; }
   h->prior_ratio_result = dp.prior_ratio;
@@ -605,7 +605,7 @@ int32_t LmRun::finish(int32_t term) {
   if (const char* path = h->solver->d_trace ? std::getenv("RSBA_CHOL_TRACE") : nullptr) {   // debugging aid, off by default
     Solver* sl = h->solver;
     std::vector<long long> tr(8 * (size_t)sl->plan.ntasks);
-    HIP_TRY(hipMemcpy(tr.data(), sl->d_trace, tr.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(hipMemcpy(tr.data(), sl->d_trace, tr.size() * sizeof(long long), hipMemcpyDeviceToHost));
     if (FILE* f = std::fopen(path, "wb")) {
       const int32_t n = sl->plan.ntasks;
       std::fwrite(&n, sizeof(n), 1, f);
@@ -638,11 +638,11 @@ int32_t LmRun::exchange_problem_size() {
   const bool host_form_only = dp.N == 0 || s->timer.on || s->pcg.on || test_hook("RSBA_DEVICE_LM_OFF_ON_THIS_RANK") != nullptr;   // (the iterative linear solver reads its convergence flag on the host)
   double cnt[4] = {(double)dp.N + npri, (double)(s->num_reduced_blocks + s->num_priors_reduced), (double)s->num_reduced_params, host_form_only ? 1.0 : 0.0};
   if (h->allreduce) {
-    HIP_TRY(hipMemcpyAsync(sv.scalars + 8, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(sv.scalars + 8, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
     if ((rc = exchange(h, sv.scalars + 8, 4, 0, RSBA_EXCHANGE_SETUP))) return rc;
-    HIP_TRY(hipMemcpyAsync(cnt, sv.scalars + 8, sizeof cnt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(sv.scalars + 8, 0, 4 * sizeof(double), st));   // slots 8-11 ride in the per-iteration sum from here on
-    HIP_TRY(hipStreamSynchronize(st));
+    RSBA_HIP_TRY(hipMemcpyAsync(cnt, sv.scalars + 8, sizeof cnt, hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemsetAsync(sv.scalars + 8, 0, 4 * sizeof(double), st));   // slots 8-11 ride in the per-iteration sum from here on
+    RSBA_HIP_TRY(hipStreamSynchronize(st));
   }
   sum->num_residual_blocks = (int32_t)cnt[0]; sum->num_residual_blocks_reduced = (int32_t)cnt[1]; sum->num_parameters_reduced = (int32_t)cnt[2];
   any_rank_needs_host = cnt[3] != 0.0;
@@ -668,8 +668,8 @@ int32_t LmRun::initial_evaluation() {
   if (opt->jacobi_scaling) {
     // EstimateScale from the first Jacobian, then the Jacobian is column-scaled for good; here the
     // scales feed the evaluation kernel, so re-linearise once with them
-    HIP_TRY(launch_jacobi_scale(dp, sv, st));
-    HIP_TRY(launch_pose_prior_scale(dp, s->pp, st));
+    RSBA_HIP_TRY(launch_jacobi_scale(dp, sv, st));
+    RSBA_HIP_TRY(launch_pose_prior_scale(dp, s->pp, st));
     if (free_ratio) ratio_scale = 1.0 / (1.0 + std::sqrt(ratio_hg[0]));
     if ((rc = linearize(h))) return rc;
   }
@@ -707,60 +707,60 @@ bool LmRun::choose_device_loop() {
 int32_t LmRun::enqueue_device_iteration(const LmRules& R, int cap, int enqueued) {
   int32_t rc;
   const bool multi = h->allreduce != nullptr;   // several ranks: the same loop with the three exchanges of an iteration enqueued between its kernels (RCCL: stream-ordered, no host wait)
-  if (free_ratio) HIP_TRY(launch_ratio_prepare_ctl(s->ratio4, s->d_ctl, opt->min_lm_diagonal, opt->max_lm_diagonal, st));   // the ratio's damped pivot and gradient for the ETA task of the factorisation
-  if (dp.pp_count > 0) HIP_TRY(launch_pose_prior_clamp(dp, s->pp, opt->min_lm_diagonal, opt->max_lm_diagonal, st));   // (the priorPoses coordinates' LM diagonal: recomputed from what the last accepted linearisation left — the same numbers after a rejected step)
+  if (free_ratio) RSBA_HIP_TRY(launch_ratio_prepare_ctl(s->ratio4, s->d_ctl, opt->min_lm_diagonal, opt->max_lm_diagonal, st));   // the ratio's damped pivot and gradient for the ETA task of the factorisation
+  if (dp.pp_count > 0) RSBA_HIP_TRY(launch_pose_prior_clamp(dp, s->pp, opt->min_lm_diagonal, opt->max_lm_diagonal, st));   // (the priorPoses coordinates' LM diagonal: recomputed from what the last accepted linearisation left — the same numbers after a rejected step)
   if ((rc = factor_and_solve(h, 1.0))) return rc;   // (the radius argument is ignored: the kernels read ctl)
-  if (free_ratio) HIP_TRY(launch_ratio_candidate(s->ratio4, s->d_ctl, st));
-  HIP_TRY(launch_candidate_and_model_cost(dp, sv, st));
-  if (owns_motion_priors(h)) HIP_TRY(launch_prior_model(dp, sv, sv.scalars + kModelCostChange, 0.0, st, free_ratio ? s->ratio4 + kRtC : nullptr));   // motion priors: their share of the model cost change (a free ratio's step included) ...
-  if (has_pp) HIP_TRY(launch_pose_prior_step(dp, sv, s->pp, 1.0, st));   // per-pose priors: the candidate priorPoses values, their share of the three sums (the lead rank's to add)
+  if (free_ratio) RSBA_HIP_TRY(launch_ratio_candidate(s->ratio4, s->d_ctl, st));
+  RSBA_HIP_TRY(launch_candidate_and_model_cost(dp, sv, st));
+  if (owns_motion_priors(h)) RSBA_HIP_TRY(launch_prior_model(dp, sv, sv.scalars + kModelCostChange, 0.0, st, free_ratio ? s->ratio4 + kRtC : nullptr));   // motion priors: their share of the model cost change (a free ratio's step included) ...
+  if (has_pp) RSBA_HIP_TRY(launch_pose_prior_step(dp, sv, s->pp, 1.0, st));   // per-pose priors: the candidate priorPoses values, their share of the three sums (the lead rank's to add)
   swap_params();
-  { DeviceProblem dq = dp; dq.rec_candidate = 1; HIP_TRY(launch_eval(dq, kLmJacobian, st)); }   // (a problem that keeps records: the candidate's go to the other set)
+  { DeviceProblem dq = dp; dq.rec_candidate = 1; RSBA_HIP_TRY(launch_eval(dq, kLmJacobian, st)); }   // (a problem that keeps records: the candidate's go to the other set)
   const bool extra_cost = s->ucross != nullptr || has_pp;   // prior blocks add their cost behind the observations': the cost is reduced by a launch of its own then
   if (extra_cost) {                                                                                // ... their cost at the candidate, behind the observations' ...
-    HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
+    RSBA_HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
     if (owns_motion_priors(h)) {
       DeviceProblem dq = dp;
       if (free_ratio) dq.prior_ratio_ptr = s->ratio4 + kRtRatioEval;   // (... at the candidate's ratio)
-      HIP_TRY(launch_prior_cost(dq, h->d_cost2, h->prior_invalid, st));
+      RSBA_HIP_TRY(launch_prior_cost(dq, h->d_cost2, h->prior_invalid, st));
     }
-    if (has_pp && sv.lead) HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, st));   // (replicated blocks: the lead rank's share of the summed cost)
+    if (has_pp && sv.lead) RSBA_HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, st));   // (replicated blocks: the lead rank's share of the summed cost)
   }
   swap_params();
   if ((rc = await_verification(h))) return rc;
   const bool my_priors = owns_motion_priors(h);
-  if (!multi) HIP_TRY(launch_lm_verdict_step(dp, sv, h->d_cost2, s->d_ctl, R, s->d_trace_it, cap, st, /*cost_reduced=*/extra_cost));
+  if (!multi) RSBA_HIP_TRY(launch_lm_verdict_step(dp, sv, h->d_cost2, s->d_ctl, R, s->d_trace_it, cap, st, /*cost_reduced=*/extra_cost));
   else {   // several ranks: the scalars of the step are summed over the ranks between the reduction and the decision — exchange (3), enqueued like a kernel
-    if (!extra_cost) HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
-    HIP_TRY(launch_pack_trial(dp, sv, h->d_cost2, st));
+    if (!extra_cost) RSBA_HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
+    RSBA_HIP_TRY(launch_pack_trial(dp, sv, h->d_cost2, st));
     if ((rc = exchange(h, sv.scalars, 12, 0, RSBA_EXCHANGE_SCALARS))) return rc;
-    HIP_TRY(launch_lm_decide_step(sv, s->d_ctl, R, s->d_trace_it, cap, st));
+    RSBA_HIP_TRY(launch_lm_decide_step(sv, s->d_ctl, R, s->d_trace_it, cap, st));
   }
   bool fused = false;
-  HIP_TRY(launch_linearize_blocks(dp, sv, st, &fused));   // camera blocks, the accepted candidate's copy over x, point blocks: side by side in one launch
-  if (!fused) HIP_TRY(launch_camera_blocks(dp, sv, st, /*take_candidate=*/true, /*padding_is_zero=*/true));   // (the initial linearisation zeroed the pseudo frames' padding)
-  if (my_priors) HIP_TRY(launch_prior_blocks(dp, sv, s->ucross, st));                             // ... and their blocks of an accepted step's linearisation
-  if (free_ratio) HIP_TRY(launch_prior_border(all_priors(h), sv, s->border, s->ratio4, st));      // (the ratio's column at the accepted point: every rank, from replicated poses)
-  if (has_pp) { HIP_TRY(launch_pose_prior_take(dp, sv, st)); HIP_TRY(launch_pose_prior_blocks(dp, sv, s->pp, st)); }   // per-pose priors: the accepted values, their blocks
-  HIP_TRY(launch_intr_blocks(dp, sv, st));
-  if (!fused) HIP_TRY(launch_point_blocks(dp, sv, st));
+  RSBA_HIP_TRY(launch_linearize_blocks(dp, sv, st, &fused));   // camera blocks, the accepted candidate's copy over x, point blocks: side by side in one launch
+  if (!fused) RSBA_HIP_TRY(launch_camera_blocks(dp, sv, st, /*take_candidate=*/true, /*padding_is_zero=*/true));   // (the initial linearisation zeroed the pseudo frames' padding)
+  if (my_priors) RSBA_HIP_TRY(launch_prior_blocks(dp, sv, s->ucross, st));                             // ... and their blocks of an accepted step's linearisation
+  if (free_ratio) RSBA_HIP_TRY(launch_prior_border(all_priors(h), sv, s->border, s->ratio4, st));      // (the ratio's column at the accepted point: every rank, from replicated poses)
+  if (has_pp) { RSBA_HIP_TRY(launch_pose_prior_take(dp, sv, st)); RSBA_HIP_TRY(launch_pose_prior_blocks(dp, sv, s->pp, st)); }   // per-pose priors: the accepted values, their blocks
+  RSBA_HIP_TRY(launch_intr_blocks(dp, sv, st));
+  if (!fused) RSBA_HIP_TRY(launch_point_blocks(dp, sv, st));
   s->ctl_seq += 1.0;
   double* const slot = s->h_ctl_dev + (size_t)(enqueued % Solver::kCtlRing) * kCtlSize;   // (where the last kernel of this iteration leaves the state for the host)
   if (!multi) {
-    HIP_TRY(launch_lm_linearize_gradient(dp, sv, h->d_cost2, st));
+    RSBA_HIP_TRY(launch_lm_linearize_gradient(dp, sv, h->d_cost2, st));
     const int ngm = (int)((sv.n + 3 * (int64_t)dp.M + 255) / 256);
-    if (dp.pp_count > 0) HIP_TRY(launch_pose_prior_gradmax(dp, sv, s->pp, st, sv.partial + ngm));   // (one more partial maximum for the verdict)
-    HIP_TRY(launch_lm_verdict_gradient(dp, sv, s->d_ctl, R, s->d_trace_it, cap, slot, s->ctl_seq, st, false, dp.pp_count > 0 ? 1 : 0));
+    if (dp.pp_count > 0) RSBA_HIP_TRY(launch_pose_prior_gradmax(dp, sv, s->pp, st, sv.partial + ngm));   // (one more partial maximum for the verdict)
+    RSBA_HIP_TRY(launch_lm_verdict_gradient(dp, sv, s->d_ctl, R, s->d_trace_it, cap, slot, s->ctl_seq, st, false, dp.pp_count > 0 ? 1 : 0));
   } else {   // exchange (1): the camera gradient, diag(U), the cost — and every rank's gradient maximum over its points — whether or not the candidate
              // was accepted (the host does not know): the unpacking skips itself after a rejected one, the maximum comes out as it was
     const bool ride = h->world <= kMaxRankSlots && dp.pp_count == 0;   // (the priorPoses blocks' maximum is the lead rank's alone: a MAX exchange of its own then, as in the host form)
     if ((rc = exchange_camera_gradient(h, ride))) return rc;
     if (!ride) {
-      HIP_TRY(launch_gradient_max(dp, sv, st));
-      if (sv.lead) HIP_TRY(launch_pose_prior_gradmax(dp, sv, s->pp, st));
+      RSBA_HIP_TRY(launch_gradient_max(dp, sv, st));
+      if (sv.lead) RSBA_HIP_TRY(launch_pose_prior_gradmax(dp, sv, s->pp, st));
       if ((rc = exchange(h, sv.scalars + kGradMax, 1, 1, RSBA_EXCHANGE_SCALARS))) return rc;
     }
-    HIP_TRY(launch_lm_verdict_gradient(dp, sv, s->d_ctl, R, s->d_trace_it, cap, slot, s->ctl_seq, st, /*gradmax_done=*/true));
+    RSBA_HIP_TRY(launch_lm_verdict_gradient(dp, sv, s->d_ctl, R, s->d_trace_it, cap, slot, s->ctl_seq, st, /*gradmax_done=*/true));
   }
   return RSBA_OK;
 }
@@ -773,25 +773,25 @@ int32_t LmRun::run_device_loop() {
                   opt->function_tolerance, opt->gradient_tolerance, opt->parameter_tolerance};
   if (!s->h_ctl) {
     static_assert((size_t)(Solver::kCtlRing + 1) * kCtlSize * sizeof(double) <= 4096, "one pooled pinned block");
-    HIP_TRY(dev_pinned_acquire(reinterpret_cast<void**>(&s->h_ctl), (size_t)(Solver::kCtlRing + 1) * kCtlSize * sizeof(double)));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_ctl_dev), s->h_ctl, 0));
+    RSBA_HIP_TRY(dev_pinned_acquire(reinterpret_cast<void**>(&s->h_ctl), (size_t)(Solver::kCtlRing + 1) * kCtlSize * sizeof(double)));
+    RSBA_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_ctl_dev), s->h_ctl, 0));
     std::fill(s->h_ctl, s->h_ctl + (size_t)(Solver::kCtlRing + 1) * kCtlSize, 0.0);
   }
   double* const hc0 = s->h_ctl + (size_t)Solver::kCtlRing * kCtlSize;   // the initial state (pinned: the upload does not wait for the host)
   std::fill(hc0, hc0 + kCtlSize, 0.0);
   hc0[kCtlRadius] = radius; hc0[kCtlDecrease] = decrease_factor; hc0[kCtlCost] = cost; hc0[kCtlFixed] = fixed; hc0[kCtlGmax] = gmax; hc0[kCtlFinalCost] = sum->final_cost;
-  HIP_TRY(hipMemcpyAsync(s->d_ctl, hc0, kCtlSize * sizeof(double), hipMemcpyHostToDevice, st));
+  RSBA_HIP_TRY(hipMemcpyAsync(s->d_ctl, hc0, kCtlSize * sizeof(double), hipMemcpyHostToDevice, st));
   struct CtlGuard {   // whichever way this block is left, the host form finds the state it expects: nobody skips, the radius (and the ratio) come by value
     rsba_handle* h; Solver* s;
     ~CtlGuard() { (void)hipStreamSynchronize(h->stream); s->sv.ctl = nullptr; h->dp.ctl = nullptr; h->dp.prior_ratio_ptr = nullptr; s->clamp_with_factor = false; (void)hipMemsetAsync(s->d_ctl, 0, kCtlSize * sizeof(double), h->stream); }
   } ctl_guard{h, s};
   sv.ctl = s->d_ctl; dp.ctl = s->d_ctl;
   if (free_ratio) {   // the ratio joins the state on the device: value, Jacobi scale, lower bound ({h, g} of the last linearisation are there)
-    HIP_TRY(launch_ratio_init(s->ratio4, ratio, ratio_scale, ratio_lb, st));
+    RSBA_HIP_TRY(launch_ratio_init(s->ratio4, ratio, ratio_scale, ratio_lb, st));
     dp.prior_ratio_ptr = s->ratio4 + kRtRatio;
   }
   s->clamp_with_factor = true; s->clamp_lo_hi[0] = opt->min_lm_diagonal; s->clamp_lo_hi[1] = opt->max_lm_diagonal;
-  HIP_TRY(launch_begin_solve(sv, st));   // (from here on the last kernel of an iteration clears the two flags for the next)
+  RSBA_HIP_TRY(launch_begin_solve(sv, st));   // (from here on the last kernel of an iteration clears the two flags for the next)
   // The last kernel of an iteration writes the state to a slot of pinned host memory and stamps it; the host polls the stamp (no
   // event, no copy in the stream) and enqueues the next iteration the moment it shows.  RSBA_LM_AHEAD = k keeps k iterations
   // enqueued beyond the one whose outcome the host has seen (those behind a termination fall through: every kernel looks at the
@@ -831,14 +831,14 @@ int32_t LmRun::run_device_loop() {
   {
     const int have = std::min((int)hc[kCtlNumTrace], cap);
     std::vector<rsba_iteration> recs((size_t)std::max(have, 1));
-    if (have > 0) HIP_TRY(hipMemcpyAsync(recs.data(), s->d_trace_it, (size_t)have * sizeof(rsba_iteration), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (have > 0) RSBA_HIP_TRY(hipMemcpyAsync(recs.data(), s->d_trace_it, (size_t)have * sizeof(rsba_iteration), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < have; ++k) push(recs[(size_t)k]);
   }
   sum->linear_solver_time_s += now_s() - t0;
   if (free_ratio) {   // the ratio's state back to the host (the stream is idle)
     double rt[kRtSize];
-    HIP_TRY(hipMemcpy(rt, s->ratio4, sizeof rt, hipMemcpyDeviceToHost));
+    RSBA_HIP_TRY(hipMemcpy(rt, s->ratio4, sizeof rt, hipMemcpyDeviceToHost));
     ratio = rt[kRtRatio]; ratio_new = ratio; ratio_diag = rt[kRtDiag]; ratio_hg[0] = rt[kRtH]; ratio_hg[1] = rt[kRtG];
     dp.prior_ratio = ratio;
   }
@@ -865,40 +865,40 @@ int32_t LmRun::run_host_loop() {
     t0 = now_s();
     if (!reuse_diagonal) {
       PhaseScope ps(h, RSBA_PHASE_OTHER);
-      HIP_TRY(launch_clamp_diagonal(dp, sv, opt->min_lm_diagonal, opt->max_lm_diagonal, st));
-      HIP_TRY(launch_pose_prior_clamp(dp, s->pp, opt->min_lm_diagonal, opt->max_lm_diagonal, st));
+      RSBA_HIP_TRY(launch_clamp_diagonal(dp, sv, opt->min_lm_diagonal, opt->max_lm_diagonal, st));
+      RSBA_HIP_TRY(launch_pose_prior_clamp(dp, s->pp, opt->min_lm_diagonal, opt->max_lm_diagonal, st));
       ratio_diag = std::min(std::max(ratio_scale * ratio_scale * ratio_hg[0], opt->min_lm_diagonal), opt->max_lm_diagonal);
     }
-    HIP_TRY(launch_begin_solve(sv, st));   // chol_fail = 0 and the sticky verification flag of the DAG Cholesky = 0 (any solve of this iteration may raise it): one launch
+    RSBA_HIP_TRY(launch_begin_solve(sv, st));   // chol_fail = 0 and the sticky verification flag of the DAG Cholesky = 0 (any solve of this iteration may raise it): one launch
     RatioStep rs{ratio_scale * ratio_scale * ratio_hg[0] + ratio_diag / radius, ratio_scale * ratio_hg[1], ratio_scale, 0.0};
     if ((rc = factor_and_solve(h, radius, free_ratio ? &rs : nullptr))) return rc;
     reuse_diagonal = true;
     const double ratio_step = free_ratio ? ratio_scale * rs.eta : 0.0;      // the ratio's step in its own units is -ratio_step
     ratio_new = free_ratio ? std::max(ratio_lb, ratio - ratio_step) : ratio;
-    { PhaseScope ps(h, RSBA_PHASE_BACK_SUBSTITUTE); HIP_TRY(launch_model_cost_change(dp, sv, st)); }
-    if (owns_motion_priors(h)) { PhaseScope ps(h, RSBA_PHASE_PRIORS); HIP_TRY(launch_prior_model(dp, sv, sv.scalars + kModelCostChange, std::isfinite(ratio_step) ? ratio_step : 0.0, st)); }
-    { PhaseScope ps(h, RSBA_PHASE_CANDIDATE); HIP_TRY(launch_candidate(dp, sv, st)); }
-    if (dp.pp_count > 0 || dp.pp_spherical >= 0) { PhaseScope ps(h, RSBA_PHASE_PRIORS); HIP_TRY(launch_pose_prior_step(dp, sv, s->pp, radius, st)); }   // every rank: candidate priorPoses values (scalars from the lead rank only)
+    { PhaseScope ps(h, RSBA_PHASE_BACK_SUBSTITUTE); RSBA_HIP_TRY(launch_model_cost_change(dp, sv, st)); }
+    if (owns_motion_priors(h)) { PhaseScope ps(h, RSBA_PHASE_PRIORS); RSBA_HIP_TRY(launch_prior_model(dp, sv, sv.scalars + kModelCostChange, std::isfinite(ratio_step) ? ratio_step : 0.0, st)); }
+    { PhaseScope ps(h, RSBA_PHASE_CANDIDATE); RSBA_HIP_TRY(launch_candidate(dp, sv, st)); }
+    if (dp.pp_count > 0 || dp.pp_spherical >= 0) { PhaseScope ps(h, RSBA_PHASE_PRIORS); RSBA_HIP_TRY(launch_pose_prior_step(dp, sv, s->pp, radius, st)); }   // every rank: candidate priorPoses values (scalars from the lead rank only)
     // residuals only at the candidate (T = double path)
     swap_params();
     {
       PhaseScope ps(h, RSBA_PHASE_EVAL_TRIAL);
-      { DeviceProblem dq = dp; dq.rec_candidate = 1; HIP_TRY(launch_eval(dq, speculate ? kLmJacobian : kResidualOnly, st)); }
-      HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
+      { DeviceProblem dq = dp; dq.rec_candidate = 1; RSBA_HIP_TRY(launch_eval(dq, speculate ? kLmJacobian : kResidualOnly, st)); }
+      RSBA_HIP_TRY(launch_cost_reduce(dp, h->d_cost2, st));
     }
     if (owns_motion_priors(h)) {
       PhaseScope ps(h, RSBA_PHASE_PRIORS);
       dp.prior_ratio = std::isfinite(ratio_new) ? ratio_new : ratio;
-      HIP_TRY(launch_prior_cost(dp, h->d_cost2, h->prior_invalid, st));
+      RSBA_HIP_TRY(launch_prior_cost(dp, h->d_cost2, h->prior_invalid, st));
       dp.prior_ratio = ratio;
     }
-    if (sv.lead) HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, st));
+    if (sv.lead) RSBA_HIP_TRY(launch_pose_prior_cost(dp, h->d_cost2, st));
     swap_params();
     // exchange (3): model decrease, |step|^2, |x|^2, (skip the max slot), trial cost, -, failure flags
     {
       PhaseScope ps(h, RSBA_PHASE_EXCHANGE);
       if ((rc = await_verification(h))) return rc;   // (its flag rides in the scalars below)
-      HIP_TRY(launch_pack_trial(dp, sv, h->d_cost2, st));
+      RSBA_HIP_TRY(launch_pack_trial(dp, sv, h->d_cost2, st));
       if ((rc = exchange(h, sv.scalars, 12, 0, RSBA_EXCHANGE_SCALARS))) return rc;   // one sum: ... and the verification flag of the Cholesky driver (every rank decides alike); slot kGradMax comes back as it was (pack_trial: the lead rank's copy, zeros from the others)
     }
     if ((rc = read_back())) return rc;
@@ -939,7 +939,7 @@ int32_t LmRun::run_host_loop() {
         swap_params();   // x = x_plus_delta
         if (speculate && dp.rec_alt) std::swap(dp.rec, dp.rec_alt);   // ... and its records, where the problem keeps them
         if (free_ratio) { ratio = ratio_new; dp.prior_ratio = ratio; }
-        if (sv.NPF > 0) HIP_TRY(hipMemcpyAsync(sv.trial_intr, dp.intr, 9 * (size_t)dp.NI * sizeof(double), hipMemcpyDeviceToDevice, st));   // constant coordinates stay in sync
+        if (sv.NPF > 0) RSBA_HIP_TRY(hipMemcpyAsync(sv.trial_intr, dp.intr, 9 * (size_t)dp.NI * sizeof(double), hipMemcpyDeviceToDevice, st));   // constant coordinates stay in sync
         t0 = now_s();
         if ((rc = linearize(h, speculate, true))) return rc;
         if ((rc = gradient_max(h))) return rc;
@@ -964,7 +964,7 @@ int32_t LmRun::run_host_loop() {
 
 extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rsba_solver_summary* sum, rsba_iteration* trace, int32_t trace_cap) {
   if (!h || !opt || !sum) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   const double t_start = now_s();
   std::memset(sum, 0, sizeof *sum);
   int32_t rc = build_solver(h);

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 #include "devmem.hpp"
 #include "solver_state.hpp"
 #include "chol_plan.hpp"
@@ -140,15 +140,6 @@ struct Solver {
 
 }  // namespace rsba
 
-#define HIP_TRY(expr)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP,        \
-                            (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str());             \
-  } while (0)
-
-
 #pragma GCC visibility push(hidden)
 namespace rsba {
 
@@ -156,7 +147,7 @@ namespace rsba {
 template <class T>
 inline int32_t s_alloc(Solver* s, T** p, size_t count) {
   void* q = nullptr;
-  HIP_TRY(dev_malloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  RSBA_HIP_TRY(dev_malloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
   s->allocs.push_back(q);
   *p = static_cast<T*>(q);
   return RSBA_OK;
@@ -165,7 +156,7 @@ template <class T>
 inline int32_t s_upload(Solver* s, T** p, const std::vector<T>& v) {
   int32_t rc = s_alloc(s, p, v.size());
   if (rc) return rc;
-  if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  if (!v.empty()) RSBA_HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return RSBA_OK;
 }
 template <class T>

@@ -18,21 +18,21 @@ using namespace rsba;
 extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* cov) {
   if (!h || !cov) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if (frame < 0 || frame >= h->dp.F) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "frame out of range");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver; SolverDev& sv = s->sv; hipStream_t st = h->stream; const int CD = sv.CD;
   if ((rc = reset_scales(h))) return rc;
   if ((rc = linearize(h))) return rc;
-  HIP_TRY(launch_clamp_diagonal(h->dp, sv, 1e-6, 1e32, st));   // only its floor matters: the decoupled diagonal of fixed coordinates
-  HIP_TRY(launch_pose_prior_clamp(h->dp, s->pp, 1e-6, 1e32, st));
-  HIP_TRY(hipMemsetAsync(sv.chol_fail, 0, sizeof(int), st));
+  RSBA_HIP_TRY(launch_clamp_diagonal(h->dp, sv, 1e-6, 1e32, st));   // only its floor matters: the decoupled diagonal of fixed coordinates
+  RSBA_HIP_TRY(launch_pose_prior_clamp(h->dp, s->pp, 1e-6, 1e32, st));
+  RSBA_HIP_TRY(hipMemsetAsync(sv.chol_fail, 0, sizeof(int), st));
   // (CD + 1 right-hand sides through ONE factorisation: the substitution-only solves walk every column's factor tiles, so a sharded
   // plan takes its replicated form here — the whole of S summed onto every rank)
   struct ShardedOff { Solver* s; bool was; ~ShardedOff() { s->sharded_off = was; } } sharded_guard{s, s->sharded_off};
   s->sharded_off = true;
   if ((rc = reduce_system(h, 1e300))) return rc;
-  if (s->hp.two_rhs) HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));   // (a plan that carries the ratio's column through its factorisation: s eta = 0 here — the plain solves S y = e_k)
+  if (s->hp.two_rhs) RSBA_HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));   // (a plan that carries the ratio's column through its factorisation: s eta = 0 here — the plain solves S y = e_k)
   std::vector<double> col((size_t)CD * CD, 0.0);
   const double one = 1.0;
   // CD (+1 with the border) solves through the factorisation; the DAG driver's verification flag is sticky, so one read after
@@ -40,14 +40,14 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
   const bool levels_before = s->use_levels;
   std::vector<double> vf; double hb[3] = {0.0, 0.0, 0.0};
   for (int attempt = 0; attempt < 2; ++attempt) {
-  HIP_TRY(hipMemsetAsync(sv.scalars + kDagSuspect, 0, sizeof(double), st));
+  RSBA_HIP_TRY(hipMemsetAsync(sv.scalars + kDagSuspect, 0, sizeof(double), st));
   for (int k = 0; k < CD; ++k) {
-    HIP_TRY(hipMemsetAsync(sv.rhs, 0, (size_t)sv.npad * sizeof(double), st));
-    HIP_TRY(hipMemcpyAsync(sv.rhs + (size_t)frame * CD + k, &one, sizeof(double), hipMemcpyHostToDevice, st));
+    RSBA_HIP_TRY(hipMemsetAsync(sv.rhs, 0, (size_t)sv.npad * sizeof(double), st));
+    RSBA_HIP_TRY(hipMemcpyAsync(sv.rhs + (size_t)frame * CD + k, &one, sizeof(double), hipMemcpyHostToDevice, st));
     const double* y = sv.yv;
     if (k == 0) { if ((rc = solve_reduced_system(h))) return rc; y = sv.yv; }   // the factorisation, once; every other column is a pair of substitutions
     else if ((rc = solve_again(h, sv.rhs, &y))) return rc;
-    HIP_TRY(hipMemcpyAsync(&col[(size_t)k * CD], y + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(&col[(size_t)k * CD], y + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   // A free interFrameRatio is one more parameter block of J^T J, coupled to every pose through its column b (the 1-wide
   // border of the reduced system, diagonal entry h): by the block inverse the pose block of the bordered system is
@@ -55,25 +55,25 @@ extern "C" int32_t rsba_pose_covariance(rsba_handle* h, int32_t frame, double* c
   if (s->border) {
     const double* v = nullptr;
     if ((rc = solve_again(h, s->border, &v))) return rc;
-    HIP_TRY(launch_border_dots(s->border, v, v, sv.npad, s->ratio4 + 2, st));
+    RSBA_HIP_TRY(launch_border_dots(s->border, v, v, sv.npad, s->ratio4 + 2, st));
     vf.resize(CD);
-    HIP_TRY(hipMemcpyAsync(vf.data(), v + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hb, s->ratio4, sizeof hb, hipMemcpyDeviceToHost, st));     // {h, g, b.v}
+    RSBA_HIP_TRY(hipMemcpyAsync(vf.data(), v + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(hb, s->ratio4, sizeof hb, hipMemcpyDeviceToHost, st));     // {h, g, b.v}
   }
   double suspect = 0.0;
   if ((rc = await_verification(h))) return rc;
-  HIP_TRY(hipMemcpyAsync(&suspect, sv.scalars + kDagSuspect, sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  RSBA_HIP_TRY(hipMemcpyAsync(&suspect, sv.scalars + kDagSuspect, sizeof(double), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipStreamSynchronize(st));
   if (suspect == 0.0 || s->use_levels) break;
   s->use_levels = true; ++s->dag_fallbacks;
   }
   s->use_levels = levels_before;
   int fail = 0, nfail = 0;
   std::vector<double> ud(CD, 0.0);   // diag(U) of the frame: exactly zero where no residual touches the coordinate
-  HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(ud.data(), sv.udiag + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  RSBA_HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipMemcpyAsync(ud.data(), sv.udiag + (size_t)frame * CD, (size_t)CD * sizeof(double), hipMemcpyDeviceToHost, st));
+  RSBA_HIP_TRY(hipStreamSynchronize(st));
   if (nfail) return rsba_set_error(RSBA_ERR_EVALUATION_FAILED, "residual and Jacobian evaluation failed");
   if (fail) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "J^T J is rank deficient (fix the gauge): no covariance, as ceres::Covariance::Compute returns false");
   double border_scale = 0.0;
@@ -135,7 +135,7 @@ int32_t covariance_gather(rsba_handle* h, const std::vector<int64_t>& row0, cons
   }
   void* d_desc = nullptr; void* d_out = nullptr;
   const size_t out_bytes = (size_t)n * dim * dim * sizeof(double);
-  HIP_TRY(dev_malloc(&d_desc, desc.size() * sizeof(int32_t)));
+  RSBA_HIP_TRY(dev_malloc(&d_desc, desc.size() * sizeof(int32_t)));
   hipError_t e = dev_malloc(&d_out, out_bytes);
   if (e == hipSuccess) e = hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
   CovStopwatch watch;
@@ -155,7 +155,7 @@ int32_t covariance_gather(rsba_handle* h, const std::vector<int64_t>& row0, cons
 extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
   if (!h) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null handle");
   if (h->allreduce) return rsba_set_error(RSBA_ERR_UNSUPPORTED, "rsba_covariance_compute does not take a handle with an exchange attached (one rank only)");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver; SolverDev& sv = s->sv; hipStream_t st = h->stream; const int CD = sv.CD;
@@ -182,23 +182,23 @@ extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
     else {
       double2* sxy = nullptr;
       if ((rc = s_alloc(s, &sxy, (size_t)h->dp.N))) return rc;
-      HIP_TRY(launch_slot_xy(h->dp, sxy, st));
+      RSBA_HIP_TRY(launch_slot_xy(h->dp, sxy, st));
       s->cov.slot_xy = sxy;
       s->cov.plan_bytes += (int64_t)sizeof(double2) * h->dp.N;
     }
     s->cov.ready = true;
   }
   const size_t tile_bytes = (size_t)sv.nslots * kTile * kTile * sizeof(double);
-  for (double** p : {&s->cov.sigma, &s->cov.g}) if (!*p) { void* q = nullptr; HIP_TRY(dev_malloc(&q, tile_bytes)); *p = static_cast<double*>(q); }
-  for (double** p : {&s->cov.live, &s->cov.vdev}) if (!*p) { void* q = nullptr; HIP_TRY(dev_malloc(&q, (size_t)sv.npad * sizeof(double))); *p = static_cast<double*>(q); }
+  for (double** p : {&s->cov.sigma, &s->cov.g}) if (!*p) { void* q = nullptr; RSBA_HIP_TRY(dev_malloc(&q, tile_bytes)); *p = static_cast<double*>(q); }
+  for (double** p : {&s->cov.live, &s->cov.vdev}) if (!*p) { void* q = nullptr; RSBA_HIP_TRY(dev_malloc(&q, (size_t)sv.npad * sizeof(double))); *p = static_cast<double*>(q); }
   // the undamped, unscaled reduced system and its factor: as rsba_pose_covariance
   if ((rc = reset_scales(h))) return rc;
   if ((rc = linearize(h))) return rc;
-  HIP_TRY(launch_clamp_diagonal(h->dp, sv, 1e-6, 1e32, st));
-  HIP_TRY(launch_pose_prior_clamp(h->dp, s->pp, 1e-6, 1e32, st));
-  HIP_TRY(hipMemsetAsync(sv.chol_fail, 0, sizeof(int), st));
+  RSBA_HIP_TRY(launch_clamp_diagonal(h->dp, sv, 1e-6, 1e32, st));
+  RSBA_HIP_TRY(launch_pose_prior_clamp(h->dp, s->pp, 1e-6, 1e32, st));
+  RSBA_HIP_TRY(hipMemsetAsync(sv.chol_fail, 0, sizeof(int), st));
   if ((rc = reduce_system(h, 1e300))) return rc;
-  if (s->hp.two_rhs) HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));
+  if (s->hp.two_rhs) RSBA_HIP_TRY(launch_ratio_prepare(s->ratio4, 1.0, 0.0, 0.0, st));
   // the factorisation rides on one solve (the right-hand side reduce_system left: its result is only what the persistent driver's
   // verification looks at), the border column of a free interFrameRatio on a second; a suspect result is redone on the level schedule
   double hb[3] = {0.0, 0.0, 0.0};
@@ -207,26 +207,26 @@ extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
   {
   struct LevelsGuard { Solver* s; bool was; ~LevelsGuard() { s->use_levels = was; } } levels_guard{s, s->use_levels};   // (whichever way the attempts end)
   for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_TRY(hipMemsetAsync(sv.scalars + kDagSuspect, 0, sizeof(double), st));
+    RSBA_HIP_TRY(hipMemsetAsync(sv.scalars + kDagSuspect, 0, sizeof(double), st));
     if ((rc = solve_reduced_system(h))) return rc;
     if (s->border) {
       const double* v = nullptr;
       if ((rc = solve_again(h, s->border, &v))) return rc;
-      HIP_TRY(launch_border_dots(s->border, v, v, sv.npad, s->ratio4 + 2, st));
+      RSBA_HIP_TRY(launch_border_dots(s->border, v, v, sv.npad, s->ratio4 + 2, st));
       s->cov.v.resize((size_t)sv.npad);
-      HIP_TRY(hipMemcpyAsync(s->cov.v.data(), v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->cov.vdev, v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st));
-      HIP_TRY(hipMemcpyAsync(hb, s->ratio4, sizeof hb, hipMemcpyDeviceToHost, st));     // {h, g, b.v}
+      RSBA_HIP_TRY(hipMemcpyAsync(s->cov.v.data(), v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToHost, st));
+      RSBA_HIP_TRY(hipMemcpyAsync(s->cov.vdev, v, (size_t)sv.npad * sizeof(double), hipMemcpyDeviceToDevice, st));
+      RSBA_HIP_TRY(hipMemcpyAsync(hb, s->ratio4, sizeof hb, hipMemcpyDeviceToHost, st));     // {h, g, b.v}
     }
     double suspect = 0.0;
     if ((rc = await_verification(h))) return rc;
     // (the two failure flags and diag(U) ride on the synchronisation the verification needs anyway)
     s->cov.ud.resize((size_t)h->dp.F * CD);
-    HIP_TRY(hipMemcpyAsync(&suspect, sv.scalars + kDagSuspect, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->cov.ud.data(), sv.udiag, s->cov.ud.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RSBA_HIP_TRY(hipMemcpyAsync(&suspect, sv.scalars + kDagSuspect, sizeof(double), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(&fail, sv.chol_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(&nfail, h->dp.fail_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipMemcpyAsync(s->cov.ud.data(), sv.udiag, s->cov.ud.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    RSBA_HIP_TRY(hipStreamSynchronize(st));
     if (suspect == 0.0 || s->use_levels) break;
     s->use_levels = true; ++s->dag_fallbacks;
   }
@@ -242,19 +242,19 @@ extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
     ~Marks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
     hipError_t mark(int k, hipStream_t st) { if (!on) return hipSuccess; hipEvent_t e; hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; ev.push_back(e); kind.push_back(k); return hipEventRecord(e, st); }
   } marks;
-  HIP_TRY(launch_cov_live(sv, h->d_mask_pose, s->cov.live, st));
-  HIP_TRY(marks.mark(0, st));
-  HIP_TRY(launch_selinv_g(sv, s->cov.sel_dev, s->cov.live, s->cov.g, 0, (int)(sp.g_info.size() / 2), st));
+  RSBA_HIP_TRY(launch_cov_live(sv, h->d_mask_pose, s->cov.live, st));
+  RSBA_HIP_TRY(marks.mark(0, st));
+  RSBA_HIP_TRY(launch_selinv_g(sv, s->cov.sel_dev, s->cov.live, s->cov.g, 0, (int)(sp.g_info.size() / 2), st));
   for (int p = 0; p < sp.nlev; ++p) {
-    HIP_TRY(marks.mark(1, st));
-    HIP_TRY(launch_selinv_off(s->cov.sel_dev, s->cov.sigma, s->cov.g, sp.lev_off_ptr[p], sp.lev_off_ptr[p + 1] - sp.lev_off_ptr[p], st));
-    HIP_TRY(marks.mark(2, st));
-    HIP_TRY(launch_selinv_diag(sv, s->cov.sel_dev, s->cov.live, s->cov.sigma, s->cov.g, sp.lev_diag_ptr[p], sp.lev_diag_ptr[p + 1] - sp.lev_diag_ptr[p], st));
+    RSBA_HIP_TRY(marks.mark(1, st));
+    RSBA_HIP_TRY(launch_selinv_off(s->cov.sel_dev, s->cov.sigma, s->cov.g, sp.lev_off_ptr[p], sp.lev_off_ptr[p + 1] - sp.lev_off_ptr[p], st));
+    RSBA_HIP_TRY(marks.mark(2, st));
+    RSBA_HIP_TRY(launch_selinv_diag(sv, s->cov.sel_dev, s->cov.live, s->cov.sigma, s->cov.g, sp.lev_diag_ptr[p], sp.lev_diag_ptr[p + 1] - sp.lev_diag_ptr[p], st));
   }
-  HIP_TRY(marks.mark(-1, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  RSBA_HIP_TRY(marks.mark(-1, st));
+  RSBA_HIP_TRY(hipStreamSynchronize(st));
   s->cov.ms[0] = s->cov.ms[1] = s->cov.ms[2] = 0.0;
-  for (size_t k = 0; k + 1 < marks.ev.size(); ++k) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, marks.ev[k], marks.ev[k + 1])); s->cov.ms[marks.kind[k]] += ms; }
+  for (size_t k = 0; k + 1 < marks.ev.size(); ++k) { float ms = 0.f; RSBA_HIP_TRY(hipEventElapsedTime(&ms, marks.ev[k], marks.ev[k + 1])); s->cov.ms[marks.kind[k]] += ms; }
   s->cov.border_scale = 0.0;
   if (s->border) {
     const double schur = hb[0] - hb[2];
@@ -268,7 +268,7 @@ extern "C" int32_t rsba_covariance_compute(rsba_handle* h) {
 extern "C" int32_t rsba_covariance_frame_blocks(rsba_handle* h, const int32_t* frame_a, const int32_t* frame_b, int64_t n, double* cov) {
   if (int32_t rc = covariance_ready(h)) return rc;
   if (n < 0 || (n > 0 && (!frame_a || !frame_b || !cov))) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad covariance block arguments");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   Solver* s = h->solver; const int CD = s->sv.CD, F = h->dp.F;
   std::vector<int64_t> row0((size_t)n), col0((size_t)n);
   for (int64_t p = 0; p < n; ++p) {
@@ -298,7 +298,7 @@ extern "C" int32_t rsba_covariance_intrinsics_block(rsba_handle* h, int32_t bloc
   Solver* s = h->solver; const SolverDev& sv = s->sv;
   if (!cov) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if (block < 0 || block >= sv.NIB) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, sv.NIB ? "intrinsics block out of range" : "the problem has no intrinsics parameter blocks (calibrated)");
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   // the 9 coordinates of block c sit at the front of its pseudo frames, behind the real frames
   const int64_t r0 = ((int64_t)sv.F + (int64_t)block * sv.NPF) * sv.CD;
   int64_t missing = -1;
@@ -320,7 +320,7 @@ extern "C" int32_t rsba_covariance_point_blocks(rsba_handle* h, const int32_t* p
   if (n < 0 || (n > 0 && !cov) || (!points && n > M)) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad covariance block arguments");
   if (points) for (int64_t p = 0; p < n; ++p) if (points[p] < 0 || points[p] >= M) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "point out of range");
   if (n == 0) return RSBA_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  RSBA_HIP_TRY(hipSetDevice(h->device));
   Solver* s = h->solver; hipStream_t st = h->stream;
   void *d_pts = nullptr, *d_out = nullptr, *d_miss = nullptr;
   const size_t out_bytes = (size_t)n * 9 * sizeof(double);
@@ -377,8 +377,8 @@ extern "C" int32_t rsba_covariance_release(rsba_handle* h) {
   Solver* s = h->solver;
   s->cov.valid = false;
   if (s->cov.sigma || s->cov.g || s->cov.live || s->cov.vdev) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // nothing on the device touches the tiles any more: they go back to the cache (devmem.hpp)
+    RSBA_HIP_TRY(hipSetDevice(h->device));
+    RSBA_HIP_TRY(hipStreamSynchronize(h->stream));   // nothing on the device touches the tiles any more: they go back to the cache (devmem.hpp)
     for (double** p : {&s->cov.sigma, &s->cov.g, &s->cov.live, &s->cov.vdev}) if (*p) { dev_free(*p); *p = nullptr; }
   }
   s->cov.v.clear(); s->cov.v.shrink_to_fit(); s->cov.ud.clear(); s->cov.ud.shrink_to_fit();

@@ -1009,19 +1009,19 @@ int32_t PlanBuild::uploads() {
     s->cell_off[0] = 0; s->cell_off[1] = nLf; s->cell_off[2] = nLf + nPart; s->cell_off[3] = nLf + nPart + nW; s->cell_off[4] = nLf + nPart + nW + nZ;
     for (int b = 0; b < 2; ++b) {
       if ((rc = s_alloc(s, &s->cells[b], s->ncells))) return rc;
-      HIP_TRY(hipMemsetAsync(s->cells[b], 0xFF, s->ncells * sizeof(double), h->stream));   // both sets start out armed
+      RSBA_HIP_TRY(hipMemsetAsync(s->cells[b], 0xFF, s->ncells * sizeof(double), h->stream));   // both sets start out armed
     }
-    HIP_TRY(dev_stream_acquire(&s->mstream));
-    for (int b = 0; b < 2; ++b) HIP_TRY(dev_event_acquire(&s->ev_armed[b], false));
-    HIP_TRY(dev_event_acquire(&s->ev_released, false));
-    HIP_TRY(dev_event_acquire(&s->ev_fork, false));
-    HIP_TRY(dev_event_acquire(&s->ev_join, false));
+    RSBA_HIP_TRY(dev_stream_acquire(&s->mstream));
+    for (int b = 0; b < 2; ++b) RSBA_HIP_TRY(dev_event_acquire(&s->ev_armed[b], false));
+    RSBA_HIP_TRY(dev_event_acquire(&s->ev_released, false));
+    RSBA_HIP_TRY(dev_event_acquire(&s->ev_fork, false));
+    RSBA_HIP_TRY(dev_event_acquire(&s->ev_join, false));
     double* cells = s->cells[0];
     sv.Lf = cells; sv.chol_part = cells + nLf; sv.Winv = sv.chol_part + nPart; sv.zv = sv.Winv + nW; sv.yv = sv.zv + sv.npad; sv.Xpub = sv.zv + nZ;
     sv.zv2 = nullptr; sv.ceta = nullptr; sv.border2 = nullptr; sv.rt = nullptr;   // (set with the border, below)
   }
   if ((rc = s_alloc(s, &s->d_dag_sync, 4))) return rc;
-  HIP_TRY(hipMemsetAsync(s->d_dag_sync, 0, 4 * sizeof(unsigned int), h->stream));   // (the persistent kernel leaves its counters at zero behind every launch)
+  RSBA_HIP_TRY(hipMemsetAsync(s->d_dag_sync, 0, 4 * sizeof(unsigned int), h->stream));   // (the persistent kernel leaves its counters at zero behind every launch)
   if ((rc = s_alloc(s, &s->zy2, 2 * (size_t)sv.npad))) return rc;
   for (size_t i = 0; i < kNumPlanLists; ++i) if (sharded || (kPlanLists[i].plans & kPlanRep)) up->upload_ref(&s->d_plan_lists[i], hp.*kPlanLists[i].host);
 
@@ -1041,9 +1041,9 @@ int32_t PlanBuild::uploads() {
     // (+ with a second right-hand side: the parts' share of the separators' rows of it, and of the two dots — behind the tiles and the rhs rows)
     if ((rc = s_alloc(s, &s->topx_buf, (size_t)s->ntop_slots * kTile * kTile + (size_t)s->ntop_tiles * kTile + (two_rhs ? (size_t)s->ntop_tiles * kTile + 8 : 0)))) return rc;
     if ((rc = s_alloc(s, &s->ybuf, (size_t)sv.npad))) return rc;
-    if (two_rhs) HIP_TRY(hipMemsetAsync(s->topx_buf + (size_t)s->ntop_slots * kTile * kTile + (size_t)s->ntop_tiles * kTile, 0, ((size_t)s->ntop_tiles * kTile + 8) * sizeof(double), h->stream));
+    if (two_rhs) RSBA_HIP_TRY(hipMemsetAsync(s->topx_buf + (size_t)s->ntop_slots * kTile * kTile + (size_t)s->ntop_tiles * kTile, 0, ((size_t)s->ntop_tiles * kTile + 8) * sizeof(double), h->stream));
   }
-  HIP_TRY(up->finish());
+  RSBA_HIP_TRY(up->finish());
   tick("uploads");
   return RSBA_OK;
 }
@@ -1058,7 +1058,7 @@ int32_t PlanBuild::allocations() {
   if (recompute) {
     double2* sxy = nullptr;
     if ((rc = s_alloc(s, &sxy, (size_t)N))) return rc;
-    HIP_TRY(launch_slot_xy(h->dp, sxy, h->stream));
+    RSBA_HIP_TRY(launch_slot_xy(h->dp, sxy, h->stream));
     sv.slot_xy = sxy;
   } else {
     if ((rc = s_alloc(s, &h->dp.rec, (size_t)N * REC))) return rc;
@@ -1088,19 +1088,19 @@ int32_t PlanBuild::allocations() {
   }
   const size_t ucross_len = h->prior_frames.empty() ? 0 : (size_t)FR * CD * CD;
   if ((rc = s_alloc(s, &sv.U, (size_t)ucross_base + ucross_len))) return rc;
-  if (ucross_len) { s->ucross = sv.U + ucross_base; s->ucross_len = ucross_len; HIP_TRY(hipMemset(s->ucross, 0, ucross_len * sizeof(double))); }   // stays zero on the other ranks
+  if (ucross_len) { s->ucross = sv.U + ucross_base; s->ucross_len = ucross_len; RSBA_HIP_TRY(hipMemset(s->ucross, 0, ucross_len * sizeof(double))); }   // stays zero on the other ranks
   if (ucross_len && h->prior_free) {   // the ratio is one more camera-side unknown: a 1-wide dense border of S, handled by a second solve
     if ((rc = s_alloc(s, &s->border, (size_t)sv.npad))) return rc;
     if ((rc = s_alloc(s, &s->ratio4, kRtSize))) return rc;
-    HIP_TRY(hipMemset(s->ratio4, 0, kRtSize * sizeof(double)));
-    HIP_TRY(hipMemset(s->border, 0, (size_t)sv.npad * sizeof(double)));
+    RSBA_HIP_TRY(hipMemset(s->ratio4, 0, kRtSize * sizeof(double)));
+    RSBA_HIP_TRY(hipMemset(s->border, 0, (size_t)sv.npad * sizeof(double)));
     sv.zv2 = sv.zv + 2 * sv.npad; sv.ceta = sv.zv + 3 * sv.npad; sv.border2 = s->border; sv.rt = s->ratio4;
     if (lead) s->num_reduced_params += 1;
   }
   if ((rc = s_alloc(s, &sv.gc, (size_t)F * CD))) return rc;
   if ((rc = s_alloc(s, &sv.intr_part, (size_t)FR * 54))) return rc;
   if ((rc = s_alloc(s, &sv.trial_intr, 9 * (size_t)std::max(dp.NI, 1)))) return rc;
-  HIP_TRY(hipMemcpy(sv.trial_intr, dp.intr, 9 * (size_t)dp.NI * sizeof(double), hipMemcpyDeviceToDevice));
+  RSBA_HIP_TRY(hipMemcpy(sv.trial_intr, dp.intr, 9 * (size_t)dp.NI * sizeof(double), hipMemcpyDeviceToDevice));
   if ((rc = s_alloc(s, &sv.V, (size_t)M * 6))) return rc;
   if ((rc = s_alloc(s, &sv.gp, (size_t)M * 3))) return rc;
   if ((rc = s_alloc(s, &sv.diag_c, (size_t)F * CD))) return rc;
@@ -1111,15 +1111,15 @@ int32_t PlanBuild::allocations() {
   sv.zero_off = (uint32_t)pt_total;
   sv.lerp_rot = dp.interp_rotation && dp.shutter != 0;
   if ((rc = s_alloc(s, &sv.Pm, pm_doubles))) return rc;
-  HIP_TRY(hipMemsetAsync(sv.Pm, 0, pm_doubles * sizeof(double), h->stream));   // rows of frames that do not see the point stay zero for good: nothing ever writes them
+  RSBA_HIP_TRY(hipMemsetAsync(sv.Pm, 0, pm_doubles * sizeof(double), h->stream));   // rows of frames that do not see the point stay zero for good: nothing ever writes them
   if ((rc = s_alloc(s, &sv.schur_next, 9 * 16))) return rc;
-  HIP_TRY(hipMemsetAsync(sv.schur_next, 0, 9 * 16 * sizeof(unsigned), h->stream));   // (every launch leaves the counters at zero: its last workgroup)
+  RSBA_HIP_TRY(hipMemsetAsync(sv.schur_next, 0, 9 * 16 * sizeof(unsigned), h->stream));   // (every launch leaves the counters at zero: its last workgroup)
   if ((rc = s_alloc(s, &sv.schur_mfma_count, 1))) return rc;
-  HIP_TRY(hipMemsetAsync(sv.schur_mfma_count, 0, sizeof(unsigned long long), h->stream));
+  RSBA_HIP_TRY(hipMemsetAsync(sv.schur_mfma_count, 0, sizeof(unsigned long long), h->stream));
 
   if ((rc = s_alloc(s, &sv.S, (size_t)sv.nslots * kTile * kTile + (size_t)sv.npad))) return rc;
   sv.rhs = sv.S + (size_t)sv.nslots * kTile * kTile;   // one buffer = exchange payload (2)
-  HIP_TRY(hipMemsetAsync(sv.S, 0, ((size_t)sv.nslots * kTile * kTile + (size_t)sv.npad) * sizeof(double), h->stream));   // fill-only tiles stay zero for good
+  RSBA_HIP_TRY(hipMemsetAsync(sv.S, 0, ((size_t)sv.nslots * kTile * kTile + (size_t)sv.npad) * sizeof(double), h->stream));   // fill-only tiles stay zero for good
   if ((rc = s_alloc(s, &sv.udiag, (size_t)F * CD))) return rc;
   if ((rc = s_alloc(s, &sv.xbuf, 2 * (size_t)F * CD + 3 + kMaxRankSlots))) return rc;   // (+ the ranks' gradient maxima)
   if ((rc = s_alloc(s, &sv.yp, (size_t)M * 3))) return rc;
@@ -1130,7 +1130,7 @@ int32_t PlanBuild::allocations() {
   if ((rc = s_alloc(s, &sv.partial_c, 2 * (((size_t)sv.n + 3 * (size_t)M + 255) / 256) + 2))) return rc;
   if ((rc = s_alloc(s, &sv.scalars, 16))) return rc;
   if ((rc = s_alloc(s, &s->d_ctl, kCtlSize))) return rc;
-  HIP_TRY(hipMemset(s->d_ctl, 0, kCtlSize * sizeof(double)));
+  RSBA_HIP_TRY(hipMemset(s->d_ctl, 0, kCtlSize * sizeof(double)));
   sv.ctl = s->d_ctl;   // (in the device copies of the plan: the persistent Cholesky looks at the status word — zero while the host decides; launches by value get null then)
   if ((rc = s_alloc(s, &sv.chol_fail, 1))) return rc;
   if ((rc = s_alloc(s, &s->d_gpose, (size_t)F * CD))) return rc;
@@ -1146,8 +1146,8 @@ int32_t PlanBuild::allocations() {
     for (int t = 0; t < nt; ++t) tds[t] = hp.slot_base[hp.iperm[t]];
     if ((rc = s_upload_const(s, &s->pp.tile_diag_slot, tds))) return rc;
   }
-  HIP_TRY(hipMemset(sv.scalars, 0, 16 * sizeof(double)));
-  HIP_TRY(hipMemset(sv.chol_fail, 0, sizeof(int)));
+  RSBA_HIP_TRY(hipMemset(sv.scalars, 0, 16 * sizeof(double)));
+  RSBA_HIP_TRY(hipMemset(sv.chol_fail, 0, sizeof(int)));
   pl.ntasks = (int)(hp.tasks.size() / 2); pl.ndiag = (int)(hp.diag_info.size() / 4);
   pl.ticket = s->d_dag_sync;
   pl.nslots = sv.nslots; pl.nparts = hp.nparts;
@@ -1165,7 +1165,7 @@ int32_t PlanBuild::allocations() {
     for (size_t i = 0; i < kNumPlanLists; ++i) for (int b = 0; b < (sharded ? 3 : 1); ++b) if (kPlanLists[i].plans & (1u << b)) plans[b]->*kPlanLists[i].field = s->d_plan_lists[i];
   }
   int cus = 0;
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+  RSBA_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
   // One persistent workgroup per CU — or two, for a WIDE task graph.  Claimed tasks that wait for their inputs hold a workgroup and the
   // schedule is short of them (192 instead of 256 workgroups cost 5 % at C4); the kernel is built so that two fit a CU (78 KB of LDS,
   // <= 256 registers per lane).  Through round 4 two per CU slowed the solve down by orders of magnitude: twice the waves polling AND every
@@ -1182,7 +1182,7 @@ int32_t PlanBuild::allocations() {
   if (const char* e = std::getenv("RSBA_CHOL_WGS")) { s->dag_workgroups = std::max(1, std::min(std::min(pl.ntasks, 2 * std::max(cus, 1)), std::atoi(e))); s->dag_one_per_cu = s->dag_workgroups <= cus; }
   if (std::getenv("RSBA_CHOL_TRACE")) {
     if ((rc = s_alloc(s, &s->d_trace, 8 * (size_t)pl.ntasks))) return rc;
-    HIP_TRY(hipMemset(s->d_trace, 0, 8 * (size_t)pl.ntasks * sizeof(long long)));
+    RSBA_HIP_TRY(hipMemset(s->d_trace, 0, 8 * (size_t)pl.ntasks * sizeof(long long)));
   }
   pl.trace = s->d_trace;
   tick("allocations");
@@ -1201,10 +1201,10 @@ int32_t PlanBuild::dag_arguments() {
   if ((rc = s_upload(s, &s->d_slot_tiles, hp.slot_tiles))) return rc;
   if ((rc = s_alloc(s, &s->d_verify, 2 * (size_t)sv.npad))) return rc;
   if ((rc = s_alloc(s, &s->verify_b, (size_t)sv.npad))) return rc;
-  HIP_TRY(dev_stream_acquire(&s->vstream));
-  HIP_TRY(dev_event_acquire(&s->ev_solved, false));
-  HIP_TRY(dev_event_acquire(&s->ev_verified, false));
-  HIP_TRY(hipMemset(s->d_verify, 0, 2 * (size_t)sv.npad * sizeof(double)));   // the check kernel leaves it zero again
+  RSBA_HIP_TRY(dev_stream_acquire(&s->vstream));
+  RSBA_HIP_TRY(dev_event_acquire(&s->ev_solved, false));
+  RSBA_HIP_TRY(dev_event_acquire(&s->ev_verified, false));
+  RSBA_HIP_TRY(hipMemset(s->d_verify, 0, 2 * (size_t)sv.npad * sizeof(double)));   // the check kernel leaves it zero again
   { const char* v = std::getenv("RSBA_CHOL_VERIFY"); s->verify_dag = !(v && v[0] == '0'); }
   { const char* v = test_hook("RSBA_CHOL_TEST_CORRUPT"); s->test_corrupt_once = v && v[0] == '1'; }
   for (int b = 0; b < 2; ++b) {   // one device copy of {sv, plan} per set of cells
@@ -1213,14 +1213,14 @@ int32_t PlanBuild::dag_arguments() {
     host_args.sv.zv = c + s->cell_off[3]; host_args.sv.yv = host_args.sv.zv + sv.npad; host_args.sv.Xpub = c + s->cell_off[4];
     if (sv.zv2) { host_args.sv.zv2 = host_args.sv.zv + 2 * sv.npad; host_args.sv.ceta = host_args.sv.zv + 3 * sv.npad; }
     if ((rc = s_alloc(s, &s->d_dag_args2[b], 1))) return rc;
-    HIP_TRY(hipMemcpy(s->d_dag_args2[b], &host_args, sizeof host_args, hipMemcpyHostToDevice));
+    RSBA_HIP_TRY(hipMemcpy(s->d_dag_args2[b], &host_args, sizeof host_args, hipMemcpyHostToDevice));
     if (sharded) {
       DagArgs a = host_args, bb = host_args;
       a.pl = s->plan_a; bb.pl = s->plan_b;
       if ((rc = s_alloc(s, &s->d_dag_args_a[b], 1))) return rc;
       if ((rc = s_alloc(s, &s->d_dag_args_b[b], 1))) return rc;
-      HIP_TRY(hipMemcpy(s->d_dag_args_a[b], &a, sizeof a, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(s->d_dag_args_b[b], &bb, sizeof bb, hipMemcpyHostToDevice));
+      RSBA_HIP_TRY(hipMemcpy(s->d_dag_args_a[b], &a, sizeof a, hipMemcpyHostToDevice));
+      RSBA_HIP_TRY(hipMemcpy(s->d_dag_args_b[b], &bb, sizeof bb, hipMemcpyHostToDevice));
     }
   }
   s->d_dag_args = s->d_dag_args2[0];
@@ -1270,7 +1270,7 @@ int32_t build_solver_impl(rsba_handle* h) {
   b.statistics();
   b.sv.ctl = nullptr;
   b.tick("statistics");
-  HIP_TRY(hipStreamSynchronize(h->stream));   // the plan's one-time fills and scatters are done whatever stream the solves will run on
+  RSBA_HIP_TRY(hipStreamSynchronize(h->stream));   // the plan's one-time fills and scatters are done whatever stream the solves will run on
   b.tick("device fills");
   if (b.dbg_plan) std::fprintf(stderr, "[rsba plan] host phases:%s\n", b.phases.c_str());
   return RSBA_OK;

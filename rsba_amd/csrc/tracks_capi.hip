@@ -8,19 +8,12 @@
 #include <cstring>
 #include <string>
 
-#include "handle.hpp"
+#include "capi_util.hpp"
 #include "tracks.hpp"
 
 using namespace rsba;
 
 namespace {
-
-#define TRACKS_TRY(expr)                                                                           \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return rsba_set_error(e_ == hipErrorOutOfMemory ? RSBA_ERR_OUT_OF_MEMORY : RSBA_ERR_HIP, \
-                                                (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
 
 inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
 
@@ -42,26 +35,26 @@ struct Arena {
   static size_t grow(size_t have, size_t need) { size_t c = std::max<size_t>(have, 1 << 16); while (c < need) c *= 2; return c; }
   int32_t reserve(int dev, size_t in_bytes, size_t out_bytes, size_t ray_bytes) {
     if (dev != device) { release(); if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; } device = dev; }
-    TRACKS_TRY(hipSetDevice(dev));
-    if (!stream) TRACKS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    RSBA_HIP_TRY(hipSetDevice(dev));
+    if (!stream) RSBA_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     if (in_bytes > in_cap) {
       (void)hipFree(d_in); (void)hipHostFree(h_in); d_in = h_in = nullptr; in_cap = 0;
       const size_t c = grow(in_cap, in_bytes);
-      TRACKS_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), c));
-      TRACKS_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), c));
+      RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), c));
       in_cap = c;
     }
     if (out_bytes > out_cap) {
       (void)hipFree(d_out); (void)hipHostFree(h_out); d_out = h_out = nullptr; out_cap = 0;
       const size_t c = grow(out_cap, out_bytes);
-      TRACKS_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), c));
-      TRACKS_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), c));
+      RSBA_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), c));
       out_cap = c;
     }
     if (ray_bytes > ray_cap) {
       (void)hipFree(d_ray); d_ray = nullptr; ray_cap = 0;
       const size_t c = grow(ray_cap, ray_bytes);
-      TRACKS_TRY(hipMalloc(reinterpret_cast<void**>(&d_ray), c));
+      RSBA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_ray), c));
       ray_cap = c;
     }
     return RSBA_OK;
@@ -116,10 +109,8 @@ extern "C" int32_t rsba_track_candidates(int32_t device, const double* cams, int
     any_rep = any_rep || (rq & RSBA_TRACK_REPROJECT);
   }
   if ((any_tri && (!tri_ok || !tri_pt)) || (any_rep && (!track_pt || !reproj_ok))) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  int32_t ndev = 0;
-  int32_t rc = rsba_device_count(&ndev);
+  int32_t rc = rsba_check_device(device);
   if (rc) return rc;
-  if (device < 0 || device >= ndev) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "device ordinal out of range");
 
   const size_t F = (size_t)num_frames, NP = (size_t)pose_offset[num_frames], M = (size_t)num_obs, N = (size_t)num_cand;
   Layout in;
@@ -143,7 +134,7 @@ extern "C" int32_t rsba_track_candidates(int32_t device, const double* cams, int
   if (any_tri) std::memcpy(A.h_in + o_cb, cand_b, N * sizeof(int32_t));
   std::memcpy(A.h_in + o_rq, request, N);
   if (any_rep) std::memcpy(A.h_in + o_tp, track_pt, 3 * N * sizeof(double));
-  TRACKS_TRY(hipMemcpyAsync(A.d_in, A.h_in, in.size, hipMemcpyHostToDevice, A.stream));
+  RSBA_HIP_TRY(hipMemcpyAsync(A.d_in, A.h_in, in.size, hipMemcpyHostToDevice, A.stream));
 
   TrackGeometryArgs a;
   a.cams = reinterpret_cast<const double*>(A.d_in + o_cams);
@@ -161,14 +152,14 @@ extern "C" int32_t rsba_track_candidates(int32_t device, const double* cams, int
   a.sq_threshold = sq_threshold; a.min_distance = min_distance;
   double* d_ray = reinterpret_cast<double*>(A.d_ray);
   uint8_t* d_ray_ok = reinterpret_cast<uint8_t*>(A.d_ray + 3 * M * sizeof(double));
-  if (any_tri) TRACKS_TRY(launch_track_rays(a, d_ray, d_ray_ok, A.stream));
-  TRACKS_TRY(launch_track_candidates(a, d_ray, d_ray_ok, reinterpret_cast<uint8_t*>(A.d_out + o_tri), reinterpret_cast<double*>(A.d_out + o_tpt),
+  if (any_tri) RSBA_HIP_TRY(launch_track_rays(a, d_ray, d_ray_ok, A.stream));
+  RSBA_HIP_TRY(launch_track_candidates(a, d_ray, d_ray_ok, reinterpret_cast<uint8_t*>(A.d_out + o_tri), reinterpret_cast<double*>(A.d_out + o_tpt),
                                      reinterpret_cast<uint8_t*>(A.d_out + o_rep), A.stream));
   // one download: the triangulation outputs only when asked for
   const size_t down = any_tri ? out.size : N;
-  if (any_tri) TRACKS_TRY(hipMemcpyAsync(A.h_out, A.d_out, down, hipMemcpyDeviceToHost, A.stream));
-  else TRACKS_TRY(hipMemcpyAsync(A.h_out + o_rep, A.d_out + o_rep, N, hipMemcpyDeviceToHost, A.stream));
-  TRACKS_TRY(hipStreamSynchronize(A.stream));
+  if (any_tri) RSBA_HIP_TRY(hipMemcpyAsync(A.h_out, A.d_out, down, hipMemcpyDeviceToHost, A.stream));
+  else RSBA_HIP_TRY(hipMemcpyAsync(A.h_out + o_rep, A.d_out + o_rep, N, hipMemcpyDeviceToHost, A.stream));
+  RSBA_HIP_TRY(hipStreamSynchronize(A.stream));
   if (tri_ok) { if (any_tri) std::memcpy(tri_ok, A.h_out + o_tri, N); else std::memset(tri_ok, 0, N); }
   if (tri_pt) { if (any_tri) std::memcpy(tri_pt, A.h_out + o_tpt, 3 * N * sizeof(double)); else std::memset(tri_pt, 0, 3 * N * sizeof(double)); }
   if (reproj_ok) std::memcpy(reproj_ok, A.h_out + o_rep, N);
