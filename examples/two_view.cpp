@@ -8,13 +8,14 @@
 //           when b == a + 1), hostHypotheses (0; 1: the RANSAC from the host definitions, for comparison), keepPoseA (0), sqrdThreshold (16),
 //           minReprojections (3), maxReprojections (10), fixFirstN (0), rolling (default: the first frame of the cache has two poses),
 //           keepPoses (0; 1: frames a and b both keep the poses of the cache and no RANSAC runs — createTracks and the bundle adjustment from
-//           a known relative geometry, what the result is compared with)
+//           a known relative geometry, what the result is compared with), solver (eight_point; five_point: TwoViewOptions::solver — the RANSAC
+//           draws five-point subsets and takes the best solution of each)
 //   out.bin (little endian): int64 ok, int64 correspondences, int64 inliers, int64 inliers in front, int64 tracks created; then the
 //     session's state in the layout of examples/new_frame.cpp: int64 F; per frame: int64 np, double poses[np][6], int64 nobs, per
 //     observation: int64 track, int64 isset_track, int64 nmatches, int64 ref_valid[nmatches]; then int64 T; per track: double pt[3] (zeros
 //     without a point), int64 valid, int64 n, n x {int64 frame, int64 obs, int64 valid}
-//   two_view ransac <scene.bin> <iterations> <threshold> <refits> <minInliers> <seed> <hostHypotheses>
-//     findEssentialRansac alone, on plain arrays.  scene.bin: int32 n, double cam_a[9], cam_b[9], float xy_a[n][2], xy_b[n][2]; stdout:
+//   two_view ransac <scene.bin> <iterations> <threshold> <refits> <minInliers> <seed> <hostHypotheses> [solver]
+//     findEssentialRansac alone, on plain arrays; solver eight_point (default) or five_point.  scene.bin: int32 n, double cam_a[9], cam_b[9], float xy_a[n][2], xy_b[n][2]; stdout:
 //     "<ok> <winner task> <inliers> <in front> <refits adopted>", E, the pose of camera B, the inlier flags — one line each
 //   exit status: 0 done, 2 bad input, 3 something threw (message on stderr)
 #include <cstdio>
@@ -53,6 +54,13 @@ static void write_state(FILE* g, const Session& sess) {
   }
 }
 
+static bool parse_solver(const std::string& name, TwoViewOptions& tv) {
+  if (name == "five_point") tv.solver = TwoViewOptions::EssentialSolver::FivePoint;
+  else if (name == "eight_point") tv.solver = TwoViewOptions::EssentialSolver::EightPoint;
+  else { std::fprintf(stderr, "solver is eight_point or five_point\n"); return false; }
+  return true;
+}
+
 static int ransac_only(int argc, char** argv) {
   if (argc < 9) { std::fprintf(stderr, "usage: %s ransac <scene.bin> <iterations> <threshold> <refits> <minInliers> <seed> <hostHypotheses>\n", argv[0]); return 2; }
   FILE* f = std::fopen(argv[2], "rb");
@@ -66,6 +74,7 @@ static int ransac_only(int argc, char** argv) {
   TwoViewOptions tv;
   tv.iterations = std::atoi(argv[3]); tv.threshold_px = std::atof(argv[4]); tv.refits = std::atoi(argv[5]); tv.min_inliers = std::atoi(argv[6]);
   tv.rng_state = std::strtoull(argv[7], nullptr, 0); tv.hypotheses_on_device = std::atoi(argv[8]) == 0;
+  if (argc > 9 && !parse_solver(argv[9], tv)) return 2;
   try {
     const TwoViewResult r = findEssentialRansac(xa.data(), xb.data(), n, cam_a, cam_b, tv, 0);
     std::printf("%d %d %d %d %d\n", r.ok ? 1 : 0, r.winner_task, r.num_inliers, r.num_front, r.refits_adopted);
@@ -106,6 +115,7 @@ int main(int argc, char** argv) {
   tv.min_inliers = (int)num("minInliers", 16);
   if (kv.count("seed")) tv.rng_state = std::strtoull(kv["seed"].c_str(), nullptr, 0);
   tv.hypotheses_on_device = num("hostHypotheses", 0) == 0;
+  if (kv.count("solver") && !parse_solver(kv["solver"], tv)) return 2;
   const bool keepPoseA = num("keepPoseA", 0) != 0, keepPoses = num("keepPoses", 0) != 0;
 
   // nothing is known but the observations and their matches

@@ -1,8 +1,8 @@
 // Two-view bootstrap: the relative pose of two frames from their 2-D / 2-D correspondences alone — what gives the first two frames of a
 // video their poses, so that createTracks, processFrame and BA (create_tracks.hpp, new_frame.hpp) have something to start from.  The
 // reference has no such step (its initialize() is a BA over frames that already carry 3-D points), so this text and rsba_amd.h
-// (rsba_epipolar_*) are the definition; epi_detail below is its host form, which the device kernels (rsba_amd/csrc/kernels_epipolar.hip)
-// restate and the tests hold both to.
+// (rsba_epipolar_*) are the definition; epi_detail below is its host form, which the device kernels (rsba_amd/csrc/kernels_epipolar.hip,
+// kernels_five_point.hip) restate and the tests hold both to.
 //
 // Conventions.  a = (xa, ya, 1), b = (xb, yb, 1) are the undistorted, normalised image points of one correspondence in frame A and frame B
 // (pnp_detail::normalised_point).  E is row-major with b^T E a = 0.  Camera A is the origin; camera B sees x_B = R x_A + t, E = [t]x R, and
@@ -23,6 +23,11 @@
 // component of v3 positive, since s1 = s2 leaves that to rounding.  A correspondence is in front for a candidate when the least-squares
 // depths of z_a R a + t = z_b b are both positive (2 x 2 normal equations, closed form).  The candidate with the most INLIERS in front wins,
 // ties go to the first.
+// five_point.  The minimal solver beside it (TwoViewOptions::solver; rsba_amd.h at rsba_epipolar_five_point states the rule): the null space
+// X, Y, Z, W of the five constraint rows by Householder reflections, the ten cubics of E = x X + y Y + z Z + W in a 10 x 20 matrix,
+// Gauss-Jordan with row pivoting, Nister's degree-10 eliminant in z, its real roots from a ladder of derivatives with fixed bisection and
+// Newton counts (|z| > 1 through the reversed polynomial), (x, y) per root, a Gauss-Newton polish on the cubics, unit norm and the sign rule
+// above; up to ten solutions in the order of fp_key.  Coplanar scene points are not declined; a pure rotation (a singular elimination) is.
 // Inlier rule.  Sampson distance in normalised coordinates, fp64: d^2 = (b^T E a)^2 / ((E a)_x^2 + (E a)_y^2 + (E^T b)_x^2 + (E^T b)_y^2);
 // inlier iff d^2 f^2 <= threshold_px^2 with f = (fx_a + fy_a + fx_b + fy_b) / 4.
 #pragma once
@@ -205,6 +210,305 @@ inline bool score(const double* na, const double* nb, int n, const double E[9], 
   return true;
 }
 
+// ---- five_point: the minimal solver (rsba_amd.h: rsba_epipolar_five_point states the rule; this is its definition and the host path) ----
+// Polynomials in (x, y, z) by coefficient arrays.  Linear: (x, y, z, 1).  Quadratic, 10: x^2 xy xz x y^2 yz y z^2 z 1 (kQuad[i][j] = the
+// product of linear terms i and j).  Cubic, 20, in the column order the elimination wants: x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy |
+// xz^2 xz x yz^2 yz y z^3 z^2 z 1 (kCubic[q][l] = quadratic term q times linear term l).
+constexpr int kQuad[4][4] = {{0, 1, 2, 3}, {1, 4, 5, 6}, {2, 5, 7, 8}, {3, 6, 8, 9}};
+constexpr int kCubic[10][4] = {{0, 2, 4, 5}, {2, 3, 8, 9}, {4, 8, 10, 11}, {5, 9, 11, 12}, {3, 1, 6, 7},
+                               {8, 6, 13, 14}, {9, 7, 14, 15}, {10, 13, 16, 17}, {11, 14, 17, 18}, {12, 15, 18, 19}};
+constexpr double kFiveRankTol = 1e-7;    // a Householder diagonal not above this times the longest constraint row: a fifth null direction
+constexpr double kFivePivotTol = 1e-7;   // an elimination pivot not above this times the largest entry of the 10 x 20 matrix: singular
+constexpr int kFiveBisections = 40, kFiveNewton = 2, kFivePolish = 2;
+
+struct FivePointDiag { double rank_ratio = -1.0, pivot_ratio = -1.0; };   // the smallest of each quantity the two tolerances are compared with
+
+// q += s a b (linear times linear), c += s q l (quadratic times linear)
+inline void fp_quad_add(double q[10], const double a[4], const double b[4], double s) {
+  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) q[kQuad[i][j]] += s * (a[i] * b[j]);
+}
+inline void fp_cubic_add(double c[20], const double q[10], const double l[4], double s) {
+  for (int k = 0; k < 10; ++k) for (int j = 0; j < 4; ++j) c[kCubic[k][j]] += s * (q[k] * l[j]);
+}
+
+// orthonormal basis N[4][9] of the null space of the five constraint rows, by Householder reflections of the 9 x 5 matrix of the rows
+// (no Gram matrix: the conditioning is that of the rows themselves); false: a fifth null direction
+inline bool fp_null_space(double a[5][9], double N[4][9], FivePointDiag* diag) {
+  double longest = 0.0, beta[5];
+  for (int k = 0; k < 5; ++k) { double s = 0.0; for (int i = 0; i < 9; ++i) s += a[k][i] * a[k][i]; longest = std::fmax(longest, std::sqrt(s)); }
+  double smallest = -1.0;
+  for (int k = 0; k < 5; ++k) {
+    double s = 0.0;
+    for (int i = k; i < 9; ++i) s += a[k][i] * a[k][i];
+    const double nrm = std::sqrt(s);
+    if (smallest < 0.0 || nrm < smallest) smallest = nrm;
+    if (diag) diag->rank_ratio = smallest / longest;
+    if (!(nrm > kFiveRankTol * longest)) return false;
+    a[k][k] -= a[k][k] >= 0.0 ? -nrm : nrm;
+    double vv = 0.0;
+    for (int i = k; i < 9; ++i) vv += a[k][i] * a[k][i];
+    beta[k] = 2.0 / vv;
+    for (int j = k + 1; j < 5; ++j) {
+      double d = 0.0;
+      for (int i = k; i < 9; ++i) d += a[k][i] * a[j][i];
+      d *= beta[k];
+      for (int i = k; i < 9; ++i) a[j][i] -= d * a[k][i];
+    }
+  }
+  for (int m = 0; m < 4; ++m) {
+    for (int i = 0; i < 9; ++i) N[m][i] = i == 5 + m ? 1.0 : 0.0;
+    for (int k = 4; k >= 0; --k) {
+      double d = 0.0;
+      for (int i = k; i < 9; ++i) d += a[k][i] * N[m][i];
+      d *= beta[k];
+      for (int i = k; i < 9; ++i) N[m][i] -= d * a[k][i];
+    }
+  }
+  return true;
+}
+
+// the ten cubics of E = x N0 + y N1 + z N2 + N3: row 0 det E, rows 1..9 (E E^T - trace_factor tr(E E^T) I) E, trace_factor = 1/2
+inline void fp_constraints(const double N[4][9], double M[10][20], double trace_factor = 0.5) {
+  double e[9][4];
+  for (int k = 0; k < 9; ++k) for (int m = 0; m < 4; ++m) e[k][m] = N[m][k];
+  for (int r = 0; r < 10; ++r) for (int c = 0; c < 20; ++c) M[r][c] = 0.0;
+  for (int i = 0; i < 3; ++i) {   // det: e[0][i] (e[1][j] e[2][k] - e[1][k] e[2][j]), (i, j, k) cyclic
+    const int j = (i + 1) % 3, k = (i + 2) % 3;
+    double q[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    fp_quad_add(q, e[3 + j], e[6 + k], 1.0); fp_quad_add(q, e[3 + k], e[6 + j], -1.0);
+    fp_cubic_add(M[0], q, e[i], 1.0);
+  }
+  double tr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 9; ++k) fp_quad_add(tr, e[k], e[k], 1.0);
+  for (int i = 0; i < 3; ++i) {
+    double L[3][10];   // row i of E E^T - trace_factor tr I
+    for (int j = 0; j < 3; ++j) {
+      for (int c = 0; c < 10; ++c) L[j][c] = i == j ? -trace_factor * tr[c] : 0.0;
+      for (int k = 0; k < 3; ++k) fp_quad_add(L[j], e[3 * i + k], e[3 * j + k], 1.0);
+    }
+    for (int c = 0; c < 3; ++c) for (int j = 0; j < 3; ++j) fp_cubic_add(M[1 + 3 * i + c], L[j], e[3 * j + c], 1.0);
+  }
+}
+
+// Gauss-Jordan on the first ten columns, partial (row) pivoting; false: singular
+inline bool fp_eliminate(double M[10][20], FivePointDiag* diag) {
+  double big = 0.0, smallest = -1.0;
+  for (int r = 0; r < 10; ++r) for (int c = 0; c < 20; ++c) big = std::fmax(big, std::fabs(M[r][c]));
+  for (int c = 0; c < 10; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < 10; ++r) if (std::fabs(M[r][c]) > std::fabs(M[piv][c])) piv = r;
+    const double p = M[piv][c];
+    if (smallest < 0.0 || std::fabs(p) < smallest) smallest = std::fabs(p);
+    if (diag) diag->pivot_ratio = smallest / big;
+    if (!(std::fabs(p) > kFivePivotTol * big)) return false;
+    for (int k = 0; k < 20; ++k) { const double t = M[piv][k]; M[piv][k] = M[c][k]; M[c][k] = t / p; }
+    for (int r = 0; r < 10; ++r) {
+      if (r == c) continue;
+      const double f = M[r][c];
+      for (int k = 0; k < 20; ++k) M[r][k] -= f * M[c][k];
+    }
+  }
+  return true;
+}
+
+// rows (4, 5), (6, 7), (8, 9) of the eliminated matrix, <upper> - z <lower>: B(z) (x, y, 1)^T = 0 with B[r] = (cubic, cubic, quartic) in z,
+// ascending powers (B[r][0][4] = B[r][1][4] = 0)
+inline void fp_reduce(const double M[10][20], double B[3][3][5]) {
+  for (int r = 0; r < 3; ++r) {
+    const double* u = M[4 + 2 * r]; const double* l = M[5 + 2 * r];
+    for (int v = 0; v < 2; ++v) {   // x: columns 10 11 12 (z^2 z 1), y: 13 14 15
+      const int c = 10 + 3 * v;
+      B[r][v][0] = u[c + 2]; B[r][v][1] = u[c + 1] - l[c + 2]; B[r][v][2] = u[c] - l[c + 1]; B[r][v][3] = -l[c]; B[r][v][4] = 0.0;
+    }
+    B[r][2][0] = u[19]; B[r][2][1] = u[18] - l[19]; B[r][2][2] = u[17] - l[18]; B[r][2][3] = u[16] - l[17]; B[r][2][4] = -l[16];
+  }
+}
+// det B(z), degree 10, ascending powers
+inline void fp_eliminant(const double B[3][3][5], double p[11]) {
+  for (int k = 0; k < 11; ++k) p[k] = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    const int i = (r + 1) % 3, j = (r + 2) % 3;
+    double C[7] = {0, 0, 0, 0, 0, 0, 0};   // bx_i by_j - bx_j by_i
+    for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) C[a + b] += B[i][0][a] * B[j][1][b] - B[j][0][a] * B[i][1][b];
+    for (int a = 0; a < 7; ++a) for (int b = 0; b < 5; ++b) p[a + b] += C[a] * B[r][2][b];
+  }
+}
+inline double fp_eval(const double* c, int deg, double t) {
+  double h = c[deg];
+  for (int k = deg - 1; k >= 0; --k) h = h * t + c[k];
+  return h;
+}
+// as pnp_detail::p3p_bisect: the root of a polynomial that is monotonic on [lo, hi], where it changes sign there; otherwise hi
+inline bool fp_bisect(const double* c, int deg, double lo, double hi, double* root) {
+  *root = hi;
+  const bool plo = fp_eval(c, deg, lo) > 0.0, phi = fp_eval(c, deg, hi) > 0.0;
+  if (plo == phi) return false;
+  for (int it = 0; it < kFiveBisections; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if ((fp_eval(c, deg, mid) > 0.0) == plo) lo = mid; else hi = mid;
+  }
+  *root = 0.5 * (lo + hi);
+  return true;
+}
+// the real roots of a degree-10 polynomial in [-1, 1], ascending: the roots of each derivative bracket those of the one above it
+inline int fp_roots_unit(const double p[11], double roots[10], int newton = kFiveNewton) {
+  double c[11][11], edge[12], next[12];
+  for (int k = 0; k < 11; ++k) c[10][k] = p[k];
+  for (int d = 10; d >= 2; --d) for (int k = 0; k < d; ++k) c[d - 1][k] = (k + 1) * c[d][k + 1];
+  edge[0] = -1.0; edge[1] = 1.0;
+  int count = 0;
+  for (int d = 1; d <= 10; ++d) {
+    next[0] = -1.0;
+    for (int i = 0; i < d; ++i) {
+      const bool found = fp_bisect(c[d], d, edge[i], edge[i + 1], &next[i + 1]);
+      if (d < 10 || !found) continue;
+      double t = next[i + 1];
+      for (int it = 0; it < newton; ++it) {   // Newton on the polynomial, a step taken only while it stays inside [-1, 1]
+        const double tn = t - fp_eval(c[10], 10, t) / fp_eval(c[9], 9, t);
+        if (tn >= -1.0 && tn <= 1.0) t = tn;
+      }
+      roots[count++] = t;
+    }
+    next[d + 1] = 1.0;
+    for (int i = 0; i <= d + 1; ++i) edge[i] = next[i];
+  }
+  return count;
+}
+// Gauss-Newton steps on the ten cubics themselves, in (x, y, z): the eliminant's coefficients went through an elimination and a 3 x 3
+// determinant of polynomials, the cubics are evaluated from the null space directly — r0 = det E, r(1 + 3i + c) = (2 E E^T E - tr(E E^T) E)_ic,
+// the Jacobian from the directional derivatives along N0, N1, N2, the 3 x 3 normal equations solved by cofactors.  A step that is not
+// finite ends the polish.
+inline void fp_polish(const double N[4][9], double v[3], int steps) {
+  for (int it = 0; it < steps; ++it) {
+    double E[9], G[3][3], r[10], J[10][3];
+    for (int m = 0; m < 9; ++m) E[m] = v[0] * N[0][m] + v[1] * N[1][m] + v[2] * N[2][m] + N[3][m];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) G[i][j] = E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1] + E[3 * i + 2] * E[3 * j + 2];
+    const double tr = G[0][0] + G[1][1] + G[2][2];
+    const double cof[9] = {E[4] * E[8] - E[5] * E[7], E[5] * E[6] - E[3] * E[8], E[3] * E[7] - E[4] * E[6],
+                           E[2] * E[7] - E[1] * E[8], E[0] * E[8] - E[2] * E[6], E[1] * E[6] - E[0] * E[7],
+                           E[1] * E[5] - E[2] * E[4], E[2] * E[3] - E[0] * E[5], E[0] * E[4] - E[1] * E[3]};
+    r[0] = E[0] * cof[0] + E[1] * cof[1] + E[2] * cof[2];
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c)
+      r[1 + 3 * i + c] = 2.0 * (G[i][0] * E[c] + G[i][1] * E[3 + c] + G[i][2] * E[6 + c]) - tr * E[3 * i + c];
+    for (int d = 0; d < 3; ++d) {
+      const double* D = N[d];
+      double dG[3][3], dtr = 0.0, dd = 0.0;
+      for (int m = 0; m < 9; ++m) { dtr += E[m] * D[m]; dd += cof[m] * D[m]; }
+      dtr *= 2.0;
+      J[0][d] = dd;
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j)
+        dG[i][j] = D[3 * i] * E[3 * j] + D[3 * i + 1] * E[3 * j + 1] + D[3 * i + 2] * E[3 * j + 2] + E[3 * i] * D[3 * j] + E[3 * i + 1] * D[3 * j + 1] + E[3 * i + 2] * D[3 * j + 2];
+      for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c)
+        J[1 + 3 * i + c][d] = 2.0 * (dG[i][0] * E[c] + dG[i][1] * E[3 + c] + dG[i][2] * E[6 + c] + G[i][0] * D[c] + G[i][1] * D[3 + c] + G[i][2] * D[6 + c])
+                              - dtr * E[3 * i + c] - tr * D[3 * i + c];
+    }
+    double A[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};   // J^T J: 00 01 02 11 12 22
+    for (int k = 0; k < 10; ++k) {
+      A[0] += J[k][0] * J[k][0]; A[1] += J[k][0] * J[k][1]; A[2] += J[k][0] * J[k][2]; A[3] += J[k][1] * J[k][1]; A[4] += J[k][1] * J[k][2]; A[5] += J[k][2] * J[k][2];
+      b[0] += J[k][0] * r[k]; b[1] += J[k][1] * r[k]; b[2] += J[k][2] * r[k];
+    }
+    const double c00 = A[3] * A[5] - A[4] * A[4], c01 = A[2] * A[4] - A[1] * A[5], c02 = A[1] * A[4] - A[2] * A[3];
+    const double c11 = A[0] * A[5] - A[2] * A[2], c12 = A[1] * A[2] - A[0] * A[4], c22 = A[0] * A[3] - A[1] * A[1];
+    const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
+    const double s0 = (c00 * b[0] + c01 * b[1] + c02 * b[2]) / det, s1 = (c01 * b[0] + c11 * b[1] + c12 * b[2]) / det, s2 = (c02 * b[0] + c12 * b[1] + c22 * b[2]) / det;
+    if (!std::isfinite(s0 + s1 + s2)) return;
+    v[0] -= s0; v[1] -= s1; v[2] -= s2;
+  }
+}
+// (x, y) of a root z from the two rows of B(z) whose 2 x 2 minor in (x, y) is largest, the polish, E = x N0 + y N1 + z N2 + N3 scaled to
+// unit Frobenius norm and signed; false: not finite
+inline bool fp_solution(const double N[4][9], const double B[3][3][5], double z, double E[9], int polish = kFivePolish) {
+  double b[3][3];
+  for (int r = 0; r < 3; ++r) for (int v = 0; v < 3; ++v) b[r][v] = fp_eval(B[r][v], 4, z);
+  const double C[3] = {b[1][0] * b[2][1] - b[2][0] * b[1][1], b[2][0] * b[0][1] - b[0][0] * b[2][1], b[0][0] * b[1][1] - b[1][0] * b[0][1]};
+  int k = 0;
+  for (int r = 1; r < 3; ++r) if (std::fabs(C[r]) > std::fabs(C[k])) k = r;
+  const int i = (k + 1) % 3, j = (k + 2) % 3;
+  const double x = (b[i][1] * b[j][2] - b[i][2] * b[j][1]) / C[k], y = (b[i][2] * b[j][0] - b[i][0] * b[j][2]) / C[k];
+  double v[3] = {x, y, z}, fro = 0.0;
+  fp_polish(N, v, polish);
+  for (int m = 0; m < 9; ++m) { E[m] = v[0] * N[0][m] + v[1] * N[1][m] + v[2] * N[2][m] + N[3][m]; fro += E[m] * E[m]; }
+  fro = std::sqrt(fro);
+  for (int m = 0; m < 9; ++m) E[m] /= fro;
+  return signed_finite(E);
+}
+// the key the solutions are ordered by: |sum_k (k + 1) E[k]|, a fixed linear form with nine different weights — free of E's sign and of the
+// null-space basis (which the roots z are not), and not zero or equal for two solutions just because the motion is along an axis
+inline double fp_key(const double E[9]) {
+  double s = 0.0;
+  for (int k = 0; k < 9; ++k) s += (k + 1) * E[k];
+  return std::fabs(s);
+}
+// every essential matrix of exactly five correspondences idx[0..5): E[s] for s < *count, ascending fp_key (the order of the roots where
+// two are equal); false: declined (E and *count untouched).  trace_factor, transpose, newton (which also switches the polish): the seeded
+// errors of the tests.
+inline bool five_point(const double* na, const double* nb, const int32_t* idx, double E[10][9], int* count, FivePointDiag* diag = nullptr,
+                       double trace_factor = 0.5, bool transpose = false, int newton = kFiveNewton) {
+  const int polish = newton > 0 ? kFivePolish : 0;
+  for (int i = 0; i < 5; ++i) for (int k = i + 1; k < 5; ++k) if (idx[i] == idx[k]) return false;
+  double a[5][9], N[4][9], M[10][20], B[3][3][5], p[11], q[11], roots[10], sol[10][9], key[10];
+  for (int i = 0; i < 5; ++i) {
+    const size_t j = 2 * (size_t)idx[i];
+    const double xa = na[j], ya = na[j + 1], xb = nb[j], yb = nb[j + 1];
+    const double r[9] = {xb * xa, xb * ya, xb, yb * xa, yb * ya, yb, xa, ya, 1.0};
+    for (int k = 0; k < 9; ++k) a[i][k] = transpose ? r[3 * (k % 3) + k / 3] : r[k];
+  }
+  if (!fp_null_space(a, N, diag)) return false;
+  fp_constraints(N, M, trace_factor);
+  if (!fp_eliminate(M, diag)) return false;
+  fp_reduce(M, B);
+  fp_eliminant(B, p);
+  for (int k = 0; k < 11; ++k) q[k] = p[10 - k];   // the roots with |z| > 1 are those of the reversed polynomial in 1 / z
+  int ns = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int nr = fp_roots_unit(pass ? q : p, roots, newton);
+    for (int s = 0; s < nr; ++s) {
+      if (pass && (roots[s] == 1.0 || roots[s] == -1.0)) continue;   // (|z| = 1 belongs to the first pass)
+      if (ns == 10) break;                                            // (a root within rounding of |z| = 1 seen by both passes)
+      if (!fp_solution(N, B, pass ? 1.0 / roots[s] : roots[s], sol[ns], polish)) return false;
+      ++ns;
+    }
+  }
+  if (ns == 0) return false;
+  for (int s = 0; s < ns; ++s) key[s] = fp_key(sol[s]);
+  for (int s = 0; s < ns; ++s) {
+    int rank = 0;
+    for (int o = 0; o < ns; ++o) if (key[o] < key[s] || (key[o] == key[s] && o < s)) ++rank;
+    for (int m = 0; m < 9; ++m) E[rank][m] = sol[s][m];
+  }
+  *count = ns;
+  return true;
+}
+
+// the chain per subset: every solution scored, the one with the most inliers kept, ties to the most in front (of its winning candidate),
+// then to the first; false: declined (no solution, or none that score() accepts)
+inline bool five_point_hypothesis(const double* na, const double* nb, int n, const int32_t* idx, double f2, double thr2, double E[9], double pose[6],
+                                  int32_t* num_inliers, int32_t num_front[4], int* num_solutions = nullptr, int* chosen = nullptr) {
+  double sol[10][9];
+  int ns = 0, best = -1;
+  int32_t best_inl = 0, best_front = 0;
+  *num_inliers = 0;
+  for (int c = 0; c < 4; ++c) num_front[c] = 0;
+  if (num_solutions) *num_solutions = 0;
+  if (!five_point(na, nb, idx, sol, &ns)) return false;
+  if (num_solutions) *num_solutions = ns;
+  for (int s = 0; s < ns; ++s) {
+    int32_t inl, front[4];
+    double ps[6];
+    if (!score(na, nb, n, sol[s], f2, thr2, &inl, front, ps)) continue;
+    int32_t most = front[0];
+    for (int c = 1; c < 4; ++c) if (front[c] > most) most = front[c];
+    if (best >= 0 && (inl < best_inl || (inl == best_inl && most <= best_front))) continue;
+    best = s; best_inl = inl; best_front = most;
+    *num_inliers = inl;
+    for (int c = 0; c < 4; ++c) num_front[c] = front[c];
+    for (int k = 0; k < 6; ++k) pose[k] = ps[k];
+    for (int k = 0; k < 9; ++k) E[k] = sol[s][k];
+  }
+  if (chosen) *chosen = best;
+  return best >= 0;
+}
+
 }  // namespace epi_detail
 
 struct TwoViewOptions {
@@ -214,6 +518,9 @@ struct TwoViewOptions {
   int min_inliers = 16;
   uint64_t rng_state = 0x9e3779b97f4a7c15ULL;
   bool hypotheses_on_device = true;   // false: the same loop from the host definitions above (what the tests compare with; no session-level code takes it)
+  // what a subset is and how it is solved: eight correspondences by eight_point, or five by five_point (every solution scored, the best
+  // kept per subset).  The refits are eight-point fits over the current inliers either way.
+  enum class EssentialSolver { EightPoint, FivePoint } solver = EssentialSolver::EightPoint;
 };
 
 struct TwoViewResult {
@@ -227,21 +534,28 @@ struct TwoViewResult {
 };
 
 namespace epi_detail {
-// The RANSAC loop over a backend: hypotheses(subsets, m, tasks, E, poses, status, num_inliers, num_front) fills the arrays of `tasks` tasks,
-// inlier_mask(E, mask) the flags [n] of one matrix.
+// The RANSAC loop over a backend: hypotheses(subsets, m, tasks, E, poses, status, num_inliers, num_front) fills the arrays of `tasks` tasks
+// (m = 5: five-point subsets, which only the first call passes; m >= 8: eight-point), inlier_mask(E, mask) the flags [n] of one matrix.
 template <class Hypotheses, class InlierMask>
 inline TwoViewResult ransac(int n, const TwoViewOptions& opt, Hypotheses&& hypotheses, InlierMask&& inlier_mask) {
   TwoViewResult res;
   res.inliers.assign((size_t)(n > 0 ? n : 0), 0);
   if (n < 8 || opt.iterations <= 0) return res;
   const int T = opt.iterations;
-  const std::vector<int32_t> subsets = pnp_detail::distinct_subsets(n, 8, T, opt.rng_state);
+  const int m = opt.solver == TwoViewOptions::EssentialSolver::FivePoint ? 5 : 8;
+  const std::vector<int32_t> subsets = pnp_detail::distinct_subsets(n, m, T, opt.rng_state);
   std::vector<double> E((size_t)T * 9), poses((size_t)T * 6);
   std::vector<uint8_t> status((size_t)T);
   std::vector<int32_t> inl((size_t)T), front((size_t)T * 4);
-  hypotheses(subsets.data(), 8, T, E.data(), poses.data(), status.data(), inl.data(), front.data());
+  hypotheses(subsets.data(), m, T, E.data(), poses.data(), status.data(), inl.data(), front.data());
   int best = -1;
-  for (int t = 0; t < T; ++t) if (status[(size_t)t] != 0 && (best < 0 || inl[(size_t)t] > inl[(size_t)best])) best = t;
+  // five-point subsets: a tie in inliers goes to the hypothesis with more of them in front, as within a subset — a scene plane gives its
+  // twin motion the same inliers and only the cheirality tells the two apart; then (and for eight-point subsets at once) to the lowest task
+  auto most_front = [&](int t) { int32_t b = front[(size_t)t * 4]; for (int c = 1; c < 4; ++c) if (front[(size_t)t * 4 + c] > b) b = front[(size_t)t * 4 + c]; return b; };
+  for (int t = 0; t < T; ++t) {
+    if (status[(size_t)t] == 0) continue;
+    if (best < 0 || inl[(size_t)t] > inl[(size_t)best] || (m == 5 && inl[(size_t)t] == inl[(size_t)best] && most_front(t) > most_front(best))) best = t;
+  }
   if (best < 0) return res;
   res.winner_task = best;
   int32_t cur_inl = inl[(size_t)best], cur_front[4];
@@ -281,7 +595,8 @@ inline TwoViewResult host_ransac(const float* xy_a, const float* xy_b, int n, co
     [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
       for (int t = 0; t < tasks; ++t) {
         double e[9];
-        status[t] = eight_point(na.data(), nb.data(), sub + (size_t)t * m, m, e) &&
+        if (m == 5) status[t] = five_point_hypothesis(na.data(), nb.data(), n, sub + (size_t)t * m, f2, thr2, e, poses + 6 * (size_t)t, &inl[t], &front[4 * (size_t)t]) ? 1 : 0;
+        else status[t] = eight_point(na.data(), nb.data(), sub + (size_t)t * m, m, e) &&
                     score(na.data(), nb.data(), n, e, f2, thr2, &inl[t], &front[4 * (size_t)t], poses + 6 * (size_t)t) ? 1 : 0;
         if (status[t]) for (int k = 0; k < 9; ++k) E[9 * (size_t)t + k] = e[k];
         else { inl[t] = 0; for (int c = 0; c < 4; ++c) front[4 * (size_t)t + c] = 0; }
@@ -295,7 +610,10 @@ inline TwoViewResult host_ransac(const float* xy_a, const float* xy_b, int n, co
 }  // namespace epi_detail
 
 // RANSAC over eight-point hypotheses: `iterations` subsets from pnp_detail::distinct_subsets(n, 8, ...), all scored in one device call
-// (rsba_epipolar_hypotheses); the most inliers win, ties go to the lowest task.  Then up to `refits` rounds of "eight-point over the current
+// (rsba_epipolar_hypotheses); the most inliers win, ties go to the lowest task.  With opt.solver = FivePoint the subsets are
+// distinct_subsets(n, 5, ...) and the call is rsba_epipolar_hypotheses_five_point, which hands back each subset's best solution; a tie in
+// inliers between subsets then goes to the one with more of them in front before it goes to the lowest task, and the rest of the loop is
+// the same (n >= 8 still: the refits are eight-point fits).  Then up to `refits` rounds of "eight-point over the current
 // inliers (one task, m = their number), recount", a refit adopted only when its count is not lower.  ok iff the final inliers in front of
 // both cameras number at least min_inliers.  xy_a / xy_b [n][2] are pixel coordinates (float, as everywhere in solve_rs_pnp.hpp).
 inline TwoViewResult findEssentialRansac(const float* xy_a, const float* xy_b, int n, const double cam_a[NUM_CAM_PARAMS], const double cam_b[NUM_CAM_PARAMS],
@@ -303,7 +621,8 @@ inline TwoViewResult findEssentialRansac(const float* xy_a, const float* xy_b, i
   if (!opt.hypotheses_on_device) return epi_detail::host_ransac(xy_a, xy_b, n, cam_a, cam_b, opt);
   return epi_detail::ransac(n, opt,
     [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
-      pnp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
+      if (m == 5) pnp_detail::check(rsba_epipolar_hypotheses_five_point(device, cam_a, cam_b, xy_a, xy_b, n, sub, tasks, opt.threshold_px, E, poses, status, inl, front, nullptr));
+      else pnp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
     },
     [&](const double E[9], uint8_t* mask) { pnp_detail::check(rsba_epipolar_inliers(device, cam_a, cam_b, xy_a, xy_b, n, E, opt.threshold_px, mask)); });
 }

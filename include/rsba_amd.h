@@ -595,6 +595,49 @@ int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a, const doub
 int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                               const double* E /* [9] */, double threshold_px, uint8_t* inlier_mask /* [n] */);
 
+/* == the minimal solver of the two-view bootstrap: every essential matrix of five correspondences.  Beside the eight-point rule, not in its
+ * place (TwoViewOptions::solver chooses; the default is the eight-point).  The reference has no such step, so this text is the definition;
+ * epi_detail::five_point (include/rsba/two_view.hpp) is its host form.  Inputs and conventions as above: both sides undistorted and
+ * normalised once per call, b^T E a = 0, E = [t]x R, row-major.
+ *   Five-point (exactly five indices per subset).
+ *     Null space.  The five rows (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1) as the columns of a 9 x 5 matrix, triangularised by five
+ *       Householder reflections (no column exchange, no Gram matrix: the conditioning is that of the rows); the reflections applied to the
+ *       unit vectors 5..8 give an orthonormal basis X, Y, Z, W of the null space.  E = x X + y Y + z Z + W.
+ *     Cubics.  det E = 0 and (E E^T - 1/2 tr(E E^T) I) E = 0 expanded by polynomial arithmetic into a 10 x 20 matrix over the monomials
+ *       x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1, Gauss-Jordan on the first ten columns with row pivoting.
+ *     Eliminant (Nister).  Rows (x^2z, x^2), (y^2z, y^2), (xyz, xy) of the result, each pair as <first> - z <second>, give B(z) (x, y, 1)^T = 0
+ *       with B 3 x 3, its columns cubic, cubic and quartic in z; p(z) = det B(z) has degree 10.
+ *     Roots.  Those with |z| <= 1 from p on [-1, 1], those with |z| > 1 as 1 / w from the reversed polynomial w^10 p(1 / w) on (-1, 1): no
+ *       division by a leading coefficient.  On [-1, 1] the roots of each derivative bracket the roots of the polynomial above it (degree 1 up
+ *       to 10); an interval whose ends differ in sign is bisected 40 times, a root of the polynomial itself then takes two Newton steps (a
+ *       step is taken only while it stays in [-1, 1]).  55 intervals per pass, two passes: every loop has a fixed bound.
+ *     Solutions.  Per root, (x, y) from the two rows of B(z) whose 2 x 2 minor in (x, y) is largest (the first such); then two Gauss-Newton
+ *       steps in (x, y, z) on the ten cubics themselves, evaluated from X..W directly (3 x 3 normal equations by cofactors; a step that is
+ *       not finite ends them) — the eliminant's coefficients went through the elimination and a determinant of polynomials, the cubics did
+ *       not; E scaled to unit Frobenius norm and signed as the eight-point result (the entry of largest magnitude, the first such, positive).
+ *     Order.  Ascending |sum_k (k + 1) E[k]|, k = 0..8 row-major: a fixed linear form with nine different weights, free of E's sign and of the
+ *       basis X..W (which the roots z are not), and not equal for two solutions just because the motion runs along an axis; summed in the
+ *       order of k, every product and sum rounded on its own.  Equal keys in the order found (the first pass ascending z, then the second ascending w).
+ *     Declined (status 0, the task's outputs untouched, num_solutions 0): a repeated index; a Householder diagonal not above 1e-7 of the longest
+ *       row (a null space of more than four dimensions: coincident correspondences); an elimination pivot not above 1e-7 of the largest entry
+ *       of the 10 x 20 matrix (a pure rotation: the cubics then hold on a continuum); no real root; a solution that is not finite.  Coplanar
+ *       scene points are NOT declined: five points of a plane have their (up to ten) essential matrices like any others.
+ * rsba_epipolar_five_point: one lane per subset, fp64; a subset's bytes do not depend on where it sits in the call.  E_out[t][s] for
+ *   s < num_solutions[t]; the other slots of an accepted task are untouched too.
+ * rsba_epipolar_hypotheses_five_point: the chain — normalise, five-point, the score of rsba_epipolar_score for EVERY solution of every
+ *   subset, then per subset the solution with the most inliers; ties go to the one with more inliers in front (of its winning candidate),
+ *   then to the first in the order above.  The solutions never leave the device between the steps.  Outputs as rsba_epipolar_hypotheses, so a
+ *   RANSAC loop can take either: status[t] 1 solved and scored; 0 declined, or no solution that the score accepts (zero counts, E_out[t] and
+ *   poses_out[t] untouched).  num_solutions (may be NULL) as the first call's.
+ * n >= 5.  All pointers are host arrays. */
+int32_t rsba_epipolar_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                 const int32_t* subsets /* [num_tasks][5] */, int32_t num_tasks, double* E_out /* [num_tasks][10][9] */,
+                                 int32_t* num_solutions /* [num_tasks], 0..10 */, uint8_t* status);
+int32_t rsba_epipolar_hypotheses_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                            const int32_t* subsets /* [num_tasks][5] */, int32_t num_tasks, double threshold_px,
+                                            double* E_out /* [num_tasks][9] */, double* poses_out /* [num_tasks][6] */, uint8_t* status,
+                                            int32_t* num_inliers, int32_t* num_front /* [num_tasks][4] */, int32_t* num_solutions /* may be NULL */);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

@@ -23,7 +23,8 @@ EXPORTS = [
     "rsba_set_exchange", "rsba_get_block_structure", "rsba_set_block_structure",
     "rsba_validate_observations", "rsba_reproject", "rsba_pose_covariance", "rsba_set_motion_priors",
     "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p",
-    "rsba_epipolar_eight_point", "rsba_epipolar_score", "rsba_epipolar_hypotheses", "rsba_epipolar_inliers", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
+    "rsba_epipolar_eight_point", "rsba_epipolar_score", "rsba_epipolar_hypotheses", "rsba_epipolar_inliers",
+    "rsba_epipolar_five_point", "rsba_epipolar_hypotheses_five_point", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
@@ -161,6 +162,8 @@ def lib():
         _lib.rsba_phase_name.restype = C.c_char_p
         _lib.rsba_rccl_comm_destroy.restype = None
         _lib.rsba_rccl_comm_destroy.argtypes = [C.c_void_p]
+        _lib.rsba_epipolar_five_point.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+        _lib.rsba_epipolar_hypotheses_five_point.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 6
     return _lib
 
 
@@ -741,6 +744,36 @@ def epipolar_hypotheses(cam_a, cam_b, xy_a, xy_b, subsets, threshold_px=4.0, E_o
     _check(lib().rsba_epipolar_hypotheses(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(sub), C.c_int32(m), C.c_int32(H),
                                           C.c_double(float(threshold_px)), _ptr(E), _ptr(poses), _ptr(status), _ptr(inl), _ptr(front)))
     return dict(E=E, poses=poses, status=status, num_inliers=inl, num_front=front)
+
+
+def epipolar_five_point(cam_a, cam_b, xy_a, xy_b, subsets, E_out=None, device=0):
+    """Every essential matrix of every subset of exactly five correspondences, on the device (rsba_amd.h: rsba_epipolar_five_point).
+    -> dict(E [H,10,9] (the slots below num_solutions; the others keep what E_out held, zeros without it), num_solutions [H] 0..10,
+    status [H]: 0 declined, 1 solved)"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    assert m == 5
+    E = np.zeros((H, 10, 9)) if E_out is None else E_out
+    assert E.dtype == np.float64 and E.shape == (H, 10, 9) and E.flags.c_contiguous
+    count = np.zeros(H, dtype=np.int32); status = np.zeros(H, dtype=np.uint8)
+    _check(lib().rsba_epipolar_five_point(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(sub), H, _ptr(E), _ptr(count), _ptr(status)))
+    return dict(E=E, num_solutions=count, status=status)
+
+
+def epipolar_hypotheses_five_point(cam_a, cam_b, xy_a, xy_b, subsets, threshold_px=4.0, E_out=None, poses_out=None, device=0):
+    """Five-point, the score of every solution and the best solution per subset in one call (rsba_amd.h: rsba_epipolar_hypotheses_five_point).
+    -> dict(E [H,9], poses [H,6], status [H]: 0 declined or nothing scored, 1 solved and scored; num_inliers [H], num_front [H,4], num_solutions [H])"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); H, m = sub.shape
+    assert m == 5
+    E = np.zeros((H, 9)) if E_out is None else E_out
+    poses = np.zeros((H, 6)) if poses_out is None else poses_out
+    assert E.dtype == np.float64 and E.shape == (H, 9) and E.flags.c_contiguous
+    assert poses.dtype == np.float64 and poses.shape == (H, 6) and poses.flags.c_contiguous
+    inl = np.zeros(H, dtype=np.int32); front = np.zeros((H, 4), dtype=np.int32); status = np.zeros(H, dtype=np.uint8); count = np.zeros(H, dtype=np.int32)
+    _check(lib().rsba_epipolar_hypotheses_five_point(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(sub), H, float(threshold_px), _ptr(E), _ptr(poses),
+                                                     _ptr(status), _ptr(inl), _ptr(front), _ptr(count)))
+    return dict(E=E, poses=poses, status=status, num_inliers=inl, num_front=front, num_solutions=count)
 
 
 def epipolar_inliers(cam_a, cam_b, xy_a, xy_b, E, threshold_px=4.0, device=0):

@@ -1,6 +1,7 @@
 // C-ABI of the two-view bootstrap (include/rsba_amd.h: rsba_epipolar_eight_point, rsba_epipolar_score, rsba_epipolar_hypotheses,
-// rsba_epipolar_inliers).  Host-side glue only: argument checks (the codes rsba_pnp_dlt returns for the same mistakes), staging of the
-// caller's arrays and the launches; every number comes from kernels_epipolar.hip and pnp_normalise_kernel (kernels_pnp_dlt.hip).
+// rsba_epipolar_inliers, rsba_epipolar_five_point, rsba_epipolar_hypotheses_five_point).  Host-side glue only: argument checks (the codes
+// rsba_pnp_dlt returns for the same mistakes), staging of the caller's arrays and the launches; every number comes from kernels_epipolar.hip,
+// kernels_five_point.hip and pnp_normalise_kernel (kernels_pnp_dlt.hip).
 #include "../../include/rsba_amd.h"
 
 #include <string>
@@ -154,4 +155,92 @@ extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, co
   RSBA_HIP_TRY(launch_epipolar_inliers(S, d_mask, nullptr));
   RSBA_HIP_TRY(hipMemcpy(inlier_mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
   return RSBA_OK;
+}
+
+// ---- the five-point solver beside the eight-point: the same order of argument checks, n >= 5, exactly five indices per subset ----
+namespace {
+
+int32_t check_points_five(const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
+  if (!cam_a || !cam_b || !xy_a || !xy_b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 5) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (the five-point solver takes at least 5 correspondences)");
+  return RSBA_OK;
+}
+int32_t check_subsets_five(int32_t n, const int32_t* subsets, int32_t num_tasks) {
+  if (!subsets) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_tasks <= 0)");
+  for (size_t k = 0; k < (size_t)num_tasks * 5; ++k)
+    if (subsets[k] < 0 || subsets[k] >= n) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "subset index out of range");
+  return RSBA_OK;
+}
+
+int32_t run_five_point(DeviceBuffers& B, EpiFiveArgs& F, const Normalised& N, int32_t n, const int32_t* subsets, int32_t num_tasks) {
+  F.n = n; F.num_tasks = num_tasks; F.na = N.na; F.nb = N.nb;
+  RSBA_HIP_TRY(B.upload(&F.subsets, subsets, (size_t)num_tasks * 5));
+  RSBA_HIP_TRY(B.alloc(&F.E_out, (size_t)num_tasks * 90));
+  RSBA_HIP_TRY(B.alloc(&F.num_solutions, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&F.slot_status, (size_t)num_tasks * 10));
+  RSBA_HIP_TRY(B.alloc(&F.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(F.E_out, 0, (size_t)num_tasks * 90 * sizeof(double)));
+  RSBA_HIP_TRY(launch_epipolar_five_point(F, nullptr));
+  return RSBA_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t rsba_epipolar_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                            const int32_t* subsets, int32_t num_tasks, double* E_out, int32_t* num_solutions, uint8_t* status) {
+  int32_t rc = check_points_five(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E_out || !num_solutions || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = check_subsets_five(n, subsets, num_tasks))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiFiveArgs F{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  if ((rc = run_five_point(B, F, N, n, subsets, num_tasks))) return rc;
+  std::vector<double> values((size_t)num_tasks * 90);
+  std::vector<int32_t> counts((size_t)num_tasks);
+  RSBA_HIP_TRY(hipMemcpy(values.data(), F.E_out, values.size() * sizeof(double), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(counts.data(), F.num_solutions, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(status, F.status, (size_t)num_tasks, hipMemcpyDeviceToHost));
+  for (size_t t = 0; t < (size_t)num_tasks; ++t) {   // the written slots only: the rest of E_out stays the caller's
+    num_solutions[t] = counts[t];
+    for (size_t k = 0; k < (size_t)counts[t] * 9; ++k) E_out[t * 90 + k] = values[t * 90 + k];
+  }
+  return RSBA_OK;
+}
+
+extern "C" int32_t rsba_epipolar_hypotheses_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                                       const int32_t* subsets, int32_t num_tasks, double threshold_px, double* E_out, double* poses_out,
+                                                       uint8_t* status, int32_t* num_inliers, int32_t* num_front, int32_t* num_solutions) {
+  int32_t rc = check_points_five(cam_a, cam_b, xy_a, xy_b, n);
+  if (rc) return rc;
+  if (!E_out || !poses_out || !status || !num_inliers || !num_front) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = check_subsets_five(n, subsets, num_tasks))) return rc;
+  if ((rc = rsba_select_device(device))) return rc;
+  DeviceBuffers B;
+  Normalised N;
+  EpiFiveArgs F{};
+  EpiScoreArgs S{};
+  EpiPickArgs P{};
+  if ((rc = normalise_both(B, N, cam_a, cam_b, xy_a, xy_b, n))) return rc;
+  if ((rc = run_five_point(B, F, N, n, subsets, num_tasks))) return rc;
+  S.E = F.E_out; S.status_in = F.slot_status;   // every slot is a task of the score kernel; the solutions stay on the device
+  if ((rc = run_score(B, S, N, cam_a, cam_b, n, num_tasks * 10, threshold_px))) return rc;
+  P.num_tasks = num_tasks; P.slot_status = S.status; P.slot_inliers = S.num_inliers; P.slot_front = S.num_front; P.slot_E = F.E_out; P.slot_poses = S.poses_out;
+  RSBA_HIP_TRY(B.alloc(&P.E_out, (size_t)num_tasks * 9));
+  RSBA_HIP_TRY(B.alloc(&P.poses_out, (size_t)num_tasks * 6));
+  RSBA_HIP_TRY(B.alloc(&P.num_inliers, (size_t)num_tasks));
+  RSBA_HIP_TRY(B.alloc(&P.num_front, (size_t)num_tasks * 4));
+  RSBA_HIP_TRY(B.alloc(&P.status, (size_t)num_tasks));
+  RSBA_HIP_TRY(hipMemset(P.E_out, 0, (size_t)num_tasks * 9 * sizeof(double)));
+  RSBA_HIP_TRY(hipMemset(P.poses_out, 0, (size_t)num_tasks * 6 * sizeof(double)));
+  RSBA_HIP_TRY(launch_epipolar_pick(P, nullptr));
+  RSBA_HIP_TRY(hipMemcpy(num_inliers, P.num_inliers, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(num_front, P.num_front, (size_t)num_tasks * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (num_solutions) RSBA_HIP_TRY(hipMemcpy(num_solutions, F.num_solutions, (size_t)num_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> st;
+  if ((rc = download_accepted(P.status, P.poses_out, 6, num_tasks, status, poses_out, st))) return rc;
+  return download_accepted(nullptr, P.E_out, 9, num_tasks, status, E_out, st);
 }

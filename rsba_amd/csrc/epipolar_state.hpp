@@ -1,4 +1,4 @@
-// Arguments of the two-view kernels (kernels_epipolar.hip); all pointers are device pointers.
+// Arguments of the two-view kernels (kernels_epipolar.hip, kernels_five_point.hip); all pointers are device pointers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -29,6 +29,35 @@ struct EpiScoreArgs {
   uint8_t* status;               // [num_tasks] 0 declined, 1 scored (may alias status_in)
 };
 
+// epipolar_five_point_kernel
+struct EpiFiveArgs {
+  int n, num_tasks;
+  const double* na;              // [n][2]
+  const double* nb;              // [n][2]
+  const int32_t* subsets;        // [num_tasks][5]
+  double* E_out;                 // [num_tasks][10][9]; only the slots below num_solutions are written
+  int32_t* num_solutions;        // [num_tasks] 0 (declined) .. 10
+  uint8_t* slot_status;          // [num_tasks][10] 1 for a written slot: the score kernel's status_in over the 10 num_tasks slots
+  uint8_t* status;               // [num_tasks] 0 declined, 1 solved
+};
+
+// epipolar_pick_kernel: per task the best of its ten scored slots
+struct EpiPickArgs {
+  int num_tasks;
+  const uint8_t* slot_status;    // [num_tasks][10] the score kernel's status
+  const int32_t* slot_inliers;   // [num_tasks][10]
+  const int32_t* slot_front;     // [num_tasks][10][4]
+  const double* slot_E;          // [num_tasks][10][9]
+  const double* slot_poses;      // [num_tasks][10][6]
+  double* E_out;                 // [num_tasks][9]; declined tasks are not written
+  double* poses_out;             // [num_tasks][6]; declined tasks are not written
+  int32_t* num_inliers;          // [num_tasks]
+  int32_t* num_front;            // [num_tasks][4]
+  uint8_t* status;               // [num_tasks] 0: no slot that the score accepted
+};
+
+hipError_t launch_epipolar_five_point(const EpiFiveArgs& args, hipStream_t st);
+hipError_t launch_epipolar_pick(const EpiPickArgs& args, hipStream_t st);
 hipError_t launch_epipolar_eight_point(const EpiEightArgs& args, hipStream_t st);
 hipError_t launch_epipolar_score(const EpiScoreArgs& args, hipStream_t st);
 // mask[i] = correspondence i is an inlier of E [9]

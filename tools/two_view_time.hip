@@ -6,6 +6,9 @@
 //   * the whole rsba_epipolar_hypotheses call (upload, normalise, eight-point, score, download), wall clock around the synchronous call,
 //   * beside it the same batch from the host definitions (epi_detail::eight_point + score, one thread), once.
 // One JSON line per workload.  Also counts the subsets the device and the host definitions disagree on (status or inlier count).
+// Then the same for the five-point chain on the same views ("solver": "five_point" lines): T five-point subsets, the five-point kernel, the
+// score kernel over the 10 T solution slots and the pick kernel alone, the whole rsba_epipolar_hypotheses_five_point call, the host chain
+// (epi_detail::five_point_hypothesis) once.  -DRSBA_FIVE_LANES=64 builds the five-point kernel with 64 subsets per workgroup.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +18,7 @@
 #include "../rsba_amd/csrc/kernels_epipolar.hip"
 #include "../rsba_amd/csrc/pnp_state.hpp"   // launch_pnp_normalise: the library's
 #include "rsba/two_view.hpp"
+#include "../rsba_amd/csrc/kernels_five_point.hip"   // (last: the file switches contraction off for what follows it)
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 #define CALL(x) do { int32_t r_ = (x); if (r_ != 0) { std::fprintf(stderr, "%s: %s\n", #x, rsba_last_error()); return 1; } } while (0)
@@ -102,6 +106,62 @@ int main() {
                   "\"best_inliers_device\": %d, \"best_inliers_host\": %d, \"format\": \"[median, min, max] of 10 after 3 warm-ups\"}\n",
                   T, n, a.med, a.lo, a.hi, b.med, b.lo, b.hi, c.med, c.lo, c.hi, host_ms, accepted, mismatch, best_dev, best_host);
       CHECK(hipFree(d_sub)); CHECK(hipFree(d_E)); CHECK(hipFree(d_poses)); CHECK(hipFree(d_st)); CHECK(hipFree(d_st2)); CHECK(hipFree(d_inl)); CHECK(hipFree(d_front));
+    }
+    for (int T : {1024, 16384}) {   // ---- the five-point chain ----
+      const std::vector<int32_t> sub = rsba_amd::pnp_detail::distinct_subsets(n, 5, T, 0x9e3779b97f4a7c15ULL);
+      const size_t slots = (size_t)T * 10;
+      int32_t* d_sub; double *d_E, *d_poses, *d_E1, *d_p1; uint8_t *d_st, *d_slot, *d_st2, *d_st3; int32_t *d_cnt, *d_inl, *d_front, *d_inl1, *d_front1;
+      CHECK(hipMalloc(&d_sub, sizeof(int32_t) * sub.size())); CHECK(hipMalloc(&d_E, sizeof(double) * 9 * slots)); CHECK(hipMalloc(&d_poses, sizeof(double) * 6 * slots));
+      CHECK(hipMalloc(&d_E1, sizeof(double) * 9 * T)); CHECK(hipMalloc(&d_p1, sizeof(double) * 6 * T)); CHECK(hipMalloc(&d_st, T)); CHECK(hipMalloc(&d_slot, slots));
+      CHECK(hipMalloc(&d_st2, slots)); CHECK(hipMalloc(&d_st3, T)); CHECK(hipMalloc(&d_cnt, sizeof(int32_t) * T)); CHECK(hipMalloc(&d_inl, sizeof(int32_t) * slots));
+      CHECK(hipMalloc(&d_front, sizeof(int32_t) * 4 * slots)); CHECK(hipMalloc(&d_inl1, sizeof(int32_t) * T)); CHECK(hipMalloc(&d_front1, sizeof(int32_t) * 4 * T));
+      CHECK(hipMemcpy(d_sub, sub.data(), sizeof(int32_t) * sub.size(), hipMemcpyHostToDevice));
+      CHECK(hipMemset(d_E, 0, sizeof(double) * 9 * slots));
+      rsba::EpiFiveArgs F{};
+      F.n = n; F.num_tasks = T; F.na = d_n[0]; F.nb = d_n[1]; F.subsets = d_sub; F.E_out = d_E; F.num_solutions = d_cnt; F.slot_status = d_slot; F.status = d_st;
+      rsba::EpiScoreArgs S{};
+      S.n = n; S.num_tasks = (int)slots; S.f2 = 800.0 * 800.0; S.thr2 = 16.0; S.na = d_n[0]; S.nb = d_n[1]; S.E = d_E; S.status_in = d_slot;
+      S.num_inliers = d_inl; S.num_front = d_front; S.poses_out = d_poses; S.status = d_st2;
+      rsba::EpiPickArgs P{};
+      P.num_tasks = T; P.slot_status = d_st2; P.slot_inliers = d_inl; P.slot_front = d_front; P.slot_E = d_E; P.slot_poses = d_poses;
+      P.E_out = d_E1; P.poses_out = d_p1; P.num_inliers = d_inl1; P.num_front = d_front1; P.status = d_st3;
+      std::vector<double> k5, ksc, kpick, call;
+      for (int rep = -warm; rep < reps; ++rep) {
+        float ms5 = 0, mssc = 0, mspick = 0;
+        CHECK(hipEventRecord(e0, nullptr)); CHECK(rsba::launch_epipolar_five_point(F, nullptr)); CHECK(hipEventRecord(e1, nullptr)); CHECK(hipEventSynchronize(e1));
+        CHECK(hipEventElapsedTime(&ms5, e0, e1));
+        CHECK(hipEventRecord(e0, nullptr)); CHECK(rsba::launch_epipolar_score(S, nullptr)); CHECK(hipEventRecord(e1, nullptr)); CHECK(hipEventSynchronize(e1));
+        CHECK(hipEventElapsedTime(&mssc, e0, e1));
+        CHECK(hipEventRecord(e0, nullptr)); CHECK(rsba::launch_epipolar_pick(P, nullptr)); CHECK(hipEventRecord(e1, nullptr)); CHECK(hipEventSynchronize(e1));
+        CHECK(hipEventElapsedTime(&mspick, e0, e1));
+        if (rep >= 0) { k5.push_back(ms5); ksc.push_back(mssc); kpick.push_back(mspick); }
+      }
+      std::vector<double> E((size_t)T * 9), poses((size_t)T * 6); std::vector<uint8_t> st((size_t)T); std::vector<int32_t> inl((size_t)T), front((size_t)T * 4), cnt((size_t)T);
+      for (int rep = -warm; rep < reps; ++rep) {
+        const double t0 = now_ms();
+        CALL(rsba_epipolar_hypotheses_five_point(0, cam, cam, xa.data(), xb.data(), n, sub.data(), T, 4.0, E.data(), poses.data(), st.data(), inl.data(), front.data(), cnt.data()));
+        if (rep >= 0) call.push_back(now_ms() - t0);
+      }
+      int mismatch = 0, accepted = 0, best_dev = 0, best_host = 0;
+      long solutions = 0;
+      const double h0 = now_ms();
+      for (int t = 0; t < T; ++t) {
+        double e[9], p[6]; int32_t hi = 0, hf[4]; int ns = 0;
+        const bool ok = rsba_amd::epi_detail::five_point_hypothesis(na.data(), nb.data(), n, &sub[(size_t)t * 5], 800.0 * 800.0, 16.0, e, p, &hi, hf, &ns);
+        mismatch += ok != (st[(size_t)t] != 0) || ns != cnt[(size_t)t] || (ok && hi != inl[(size_t)t]);
+        accepted += ok; solutions += ns;
+        if (ok) best_host = std::max(best_host, (int)hi);
+        if (st[(size_t)t]) best_dev = std::max(best_dev, (int)inl[(size_t)t]);
+      }
+      const double host_ms = now_ms() - h0;
+      const Stat a = stat(k5), b = stat(ksc), c = stat(kpick), d = stat(call);
+      std::printf("{\"solver\": \"five_point\", \"lanes_per_workgroup\": %d, \"subsets\": %d, \"correspondences\": %d, \"five_point_kernel_ms\": [%.4f, %.4f, %.4f], "
+                  "\"score_kernel_ms\": [%.4f, %.4f, %.4f], \"pick_kernel_ms\": [%.4f, %.4f, %.4f], \"hypotheses_call_ms\": [%.4f, %.4f, %.4f], "
+                  "\"host_definitions_ms\": %.1f, \"accepted\": %d, \"solutions\": %ld, \"mismatches_with_host\": %d, \"best_inliers_device\": %d, "
+                  "\"best_inliers_host\": %d, \"format\": \"[median, min, max] of 10 after 3 warm-ups\"}\n",
+                  rsba::kFiveLanes, T, n, a.med, a.lo, a.hi, b.med, b.lo, b.hi, c.med, c.lo, c.hi, d.med, d.lo, d.hi, host_ms, accepted, solutions, mismatch, best_dev, best_host);
+      CHECK(hipFree(d_sub)); CHECK(hipFree(d_E)); CHECK(hipFree(d_poses)); CHECK(hipFree(d_E1)); CHECK(hipFree(d_p1)); CHECK(hipFree(d_st)); CHECK(hipFree(d_slot));
+      CHECK(hipFree(d_st2)); CHECK(hipFree(d_st3)); CHECK(hipFree(d_cnt)); CHECK(hipFree(d_inl)); CHECK(hipFree(d_front)); CHECK(hipFree(d_inl1)); CHECK(hipFree(d_front1));
     }
     CHECK(hipFree(d_n[0])); CHECK(hipFree(d_n[1]));
   }

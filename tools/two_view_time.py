@@ -2,7 +2,8 @@
 """Times the essential-matrix hypotheses of the two-view bootstrap on the device, for 1 024 and 16 384 eight-point subsets of 500 and 8 000
 correspondences (tools/two_view_time.hip): the eight-point and the score kernel alone in HIP-event time, the whole
 rsba_epipolar_hypotheses call, and beside it the same batch from the host definitions on the same box — three warm-ups, ten timed
-repetitions, the median with min .. max.
+repetitions, the median with min .. max.  Then the five-point chain on the same views: the five-point kernel, the score kernel over the
+ten solution slots per subset and the pick kernel alone, the whole rsba_epipolar_hypotheses_five_point call, the host chain.
 Builds the program when it is missing (hipcc), runs it, prints its JSON lines and, with --out, writes them to a file.
 Needs a GPU: there is no fallback."""
 import argparse
@@ -32,7 +33,7 @@ def main():
     exe = build(a.rebuild)
     if a.build_only:
         return 0
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=280)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=560)
     sys.stderr.write(r.stderr)
     if r.returncode != 0:
         return r.returncode
