@@ -37,14 +37,13 @@ int main(int argc, char** argv) {
     if (p3p) {
       double pose[6];
       p3p_inliers = solveGsPnPRansacP3P(op.data(), ip.data(), n, cam, pose, hd[4], err, state, 0, true);
-      if (p3p_inliers > 0) { pnp_detail::from_pose(pose, v, v + 3); pnp_detail::from_pose(pose, v + 6, v + 9); }
+      if (p3p_inliers > 0) { hyp_detail::from_pose(pose, v, v + 3); hyp_detail::from_pose(pose, v + 6, v + 9); }
     } else if (hd[4] == -1) {  // iterations -1: the direct linear transform of the global-shutter initialisation alone (host glue; no device)
-      const std::vector<double> nrm = pnp_detail::normalised_points(cam, ip.data(), n);
-      std::vector<int32_t> all((size_t)n);
-      for (int i = 0; i < n; ++i) all[(size_t)i] = i;
+      const std::vector<double> nrm = hyp_detail::normalised_points(cam, ip.data(), n);
+      const std::vector<int32_t> all = hyp_detail::all_indices(n);
       double pose[6];
       if (!pnp_detail::dlt_pose(op.data(), nrm.data(), all.data(), n, pose)) inliers.assign(1, -1);
-      else { pnp_detail::from_pose(pose, v, v + 3); pnp_detail::from_pose(pose, v + 6, v + 9); }
+      else { hyp_detail::from_pose(pose, v, v + 3); hyp_detail::from_pose(pose, v + 6, v + 9); }
     } else if (hd[4] == 0) {   // iterations 0: the single solve (solveRsPnP); -1 inliers = the solution is not usable
       if (!solveRsPnP(op.data(), ip.data(), n, cam, v, v + 3, v + 6, v + 9, (SHUTTER)hd[1], scan)) inliers.assign(1, -1);
     } else

@@ -66,13 +66,13 @@ inline bool solveRsPnP(Session& sess, const SfmOptions& opt, const int32_t maxIt
   bool two_starts = false;
   if (f.__isset.priorPoses && !f.priorPoses.empty()) {                    // :694-696 (and the start of the solve, see the header)
     f.poses = f.priorPoses;
-    pnp_detail::from_pose(f.poses[0].data(), rvec, tvec);
-    if (f.poses.size() > 1) { pnp_detail::from_pose(f.poses[1].data(), rvec2, tvec2); two_starts = true; }
+    hyp_detail::from_pose(f.poses[0].data(), rvec, tvec);
+    if (f.poses.size() > 1) { hyp_detail::from_pose(f.poses[1].data(), rvec2, tvec2); two_starts = true; }
   } else if (opt.mod_init.reuseLastPose && frameKey > 0) {                // :697-711
     const std::vector<double>* pose = nullptr;
     if (f.poses.size() > 1) pose = &f.poses[0];
     else if (!sess.frames[frameKey - 1].poses.empty()) pose = &sess.frames[frameKey - 1].poses.back();   // the last pose
-    if (pose) pnp_detail::from_pose(pose->data(), rvec, tvec);
+    if (pose) hyp_detail::from_pose(pose->data(), rvec, tvec);
   }
 
   int inliers = 0;
@@ -81,38 +81,28 @@ inline bool solveRsPnP(Session& sess, const SfmOptions& opt, const int32_t maxIt
     const float threshold = (float)(std::sqrt(opt.tracks.sqrdThreshold) * 2);
     const uint64_t seed = 0x9e3779b97f4a7c15ULL;
     if (opt.mod_init.reuseLastPose && n >= m) {   // useExtrinsicGuess: every sampled subset refined from the shared guess
-      pnp_detail::Rng gen(seed);
-      std::vector<int32_t> subsets((size_t)iterations * m), pick((size_t)m);
-      for (int it = 0; it < iterations; ++it) {
-        for (int k = 0; k < m;) {
-          const int c = gen.uniform(0, n); bool dup = false;
-          for (int j = 0; j < k; ++j) dup = dup || pick[(size_t)j] == c;
-          if (!dup) pick[(size_t)k++] = c;
-        }
-        for (int k = 0; k < m; ++k) subsets[(size_t)it * m + k] = pick[(size_t)k];
-      }
+      const std::vector<int32_t> subsets = hyp_detail::distinct_subsets(n, m, iterations, seed);
       double init[12];
-      pnp_detail::to_pose(rvec, tvec, init);
+      hyp_detail::to_pose(rvec, tvec, init);
       for (int k = 0; k < 6; ++k) init[6 + k] = init[k];
       std::vector<double> poses((size_t)iterations * 12);
       std::vector<uint8_t> status((size_t)iterations);
       std::vector<int32_t> count((size_t)iterations);
       const int32_t sl[2] = {0, 1};
-      pnp_detail::check(rsba_pnp_tasks(device, cam, (int32_t)GLOBAL, sl, pts.data(), obs.data(), n, subsets.data(), m, iterations, init, 0, 5, 0, threshold,
+      hyp_detail::check(rsba_pnp_tasks(device, cam, (int32_t)GLOBAL, sl, pts.data(), obs.data(), n, subsets.data(), m, iterations, init, 0, 5, 0, threshold,
                                        poses.data(), status.data(), nullptr, count.data()));
-      int best = -1;
-      for (int t = 0; t < iterations; ++t) if (status[(size_t)t] == 1 && (best < 0 || count[(size_t)t] > count[(size_t)best])) best = t;
-      if (best >= 0 && count[(size_t)best] > 4) { inliers = count[(size_t)best]; pnp_detail::from_pose(&poses[(size_t)best * 12], rvec, tvec); }
+      const int best = hyp_detail::most_inliers(status.data(), count.data(), iterations, [](uint8_t st) { return st == 1; });
+      if (best >= 0 && count[(size_t)best] > 4) { inliers = count[(size_t)best]; hyp_detail::from_pose(&poses[(size_t)best * 12], rvec, tvec); }
     }
     if (inliers <= 4) {                           // no extrinsic guess: hypotheses from the DLT, on the device
       double gs[6];
       const int found = solveGsPnPRansac(pts.data(), obs.data(), n, cam, gs, iterations, threshold, m, seed, device, true);
-      if (found > 4) { inliers = found; pnp_detail::from_pose(gs, rvec, tvec); }
+      if (found > 4) { inliers = found; hyp_detail::from_pose(gs, rvec, tvec); }
     }
     if (inliers <= 4) {                           // :726-731, CV_P3P without a guess: hypotheses from the minimal solver, on the device
       double gs[6];
       const int found = solveGsPnPRansacP3P(pts.data(), obs.data(), n, cam, gs, iterations, threshold, seed, device, true);
-      if (found > 4) { inliers = found; pnp_detail::from_pose(gs, rvec, tvec); }
+      if (found > 4) { inliers = found; hyp_detail::from_pose(gs, rvec, tvec); }
     }
     two_starts = false;
   }
@@ -128,10 +118,10 @@ inline bool solveRsPnP(Session& sess, const SfmOptions& opt, const int32_t maxIt
 
   if (!(inliers > 4 || (!opt.mod_init.solveGsPnP && !opt.mod_init.solveRsPnP))) return false;   // :748, :795-797
   std::vector<double> pose(NUM_POSE_PARAMS);
-  pnp_detail::to_pose(rvec, tvec, pose.data());
+  hyp_detail::to_pose(rvec, tvec, pose.data());
   f.poses.assign(opt.model.rolling_shutter ? 2 : 1, pose);               // :751-759
   f.__isset.poses = true;
-  if (f.poses.size() == 2) pnp_detail::to_pose(rvec2, tvec2, f.poses[1].data());   // :761-767
+  if (f.poses.size() == 2) hyp_detail::to_pose(rvec2, tvec2, f.poses[1].data());   // :761-767
 
   if (opt.mod_init.refinePnP) {                                           // :769-792
     createTracks(sess, frameKey, opt, device);

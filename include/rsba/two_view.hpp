@@ -5,13 +5,13 @@
 // kernels_five_point.hip) restate and the tests hold both to.
 //
 // Conventions.  a = (xa, ya, 1), b = (xb, yb, 1) are the undistorted, normalised image points of one correspondence in frame A and frame B
-// (pnp_detail::normalised_point).  E is row-major with b^T E a = 0.  Camera A is the origin; camera B sees x_B = R x_A + t, E = [t]x R, and
-// the pose of B in A's frame is pnp_detail::pose_from_rt(R, t) with |t| = 1: the length of the baseline is the unit of the reconstruction.
+// (hyp_detail::normalised_point).  E is row-major with b^T E a = 0.  Camera A is the origin; camera B sees x_B = R x_A + t, E = [t]x R, and
+// the pose of B in A's frame is hyp_detail::pose_from_rt(R, t) with |t| = 1: the length of the baseline is the unit of the reconstruction.
 //
 // eight_point.  Hartley normalisation of each side's m points (centroid, mean distance scaled to sqrt 2), the 9 x 9 Gram matrix of the rows
-// (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1), its smallest eigenvector by pnp_detail::smallest_eigenvector12 with three idle unknowns
-// at twice the trace (as planar_pose does; zero off-diagonals are skipped, so the rotations are those of a 9 x 9 sweep) under the DLT's two
-// gap tests, the normalisation undone, then the projection onto the essential manifold: V and the singular values s1 >= s2 from eigen3 of
+// (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1), its null vector by hyp_detail::null_vector9 (smallest_eigenvector12 with three idle unknowns
+// at twice the trace, as planar_pose takes it; zero off-diagonals are skipped, so the rotations are those of a 9 x 9 sweep; the DLT's two
+// gap tests), the normalisation undone, then the projection onto the essential manifold: V and the singular values s1 >= s2 from eigen3 of
 // E^T E, u_i = E v_i / s_i for the two largest, u3 = u1 x u2, v3 = v1 x v2 (so det U = det V = +1), result u1 v1^T + u2 v2^T.
 // Declined: m < 8, a repeated index, a Hartley scale that is not positive, a second null direction (coplanar scene points, a pure rotation),
 // s2 not above 1e-6 s1, a result that is not finite.
@@ -43,9 +43,6 @@ namespace rsba_amd {
 
 namespace epi_detail {
 
-using pnp_detail::eigen3;
-using pnp_detail::pose_from_rt;
-
 // V (columns v1 v2 v3, singular values descending), U (columns u1 u2 u3) and s1, s2 of a 3 x 3 matrix that has rank two (or nearly);
 // false: s2 is not above 1e-6 s1
 inline bool essential_svd(const double E[9], double U[3][3] /* [column][row] */, double V[3][3] /* [column][row] */, double s[2]) {
@@ -55,14 +52,14 @@ inline bool essential_svd(const double E[9], double U[3][3] /* [column][row] */,
     sym[3] += E[3 * r + 1] * E[3 * r + 1]; sym[4] += E[3 * r + 1] * E[3 * r + 2]; sym[5] += E[3 * r + 2] * E[3 * r + 2];
   }
   double val[3], vec[3][3];
-  eigen3(sym, val, vec);
+  hyp_detail::eigen3(sym, val, vec);
   s[0] = std::sqrt(std::fmax(0.0, val[2])); s[1] = std::sqrt(std::fmax(0.0, val[1]));
   if (!(s[1] > 1e-6 * s[0])) return false;
   for (int k = 0; k < 3; ++k) { V[0][k] = vec[2][k]; V[1][k] = vec[1][k]; }
   for (int c = 0; c < 2; ++c)
     for (int r = 0; r < 3; ++r) U[c][r] = (E[3 * r] * V[c][0] + E[3 * r + 1] * V[c][1] + E[3 * r + 2] * V[c][2]) / s[c];
-  U[2][0] = U[0][1] * U[1][2] - U[0][2] * U[1][1]; U[2][1] = U[0][2] * U[1][0] - U[0][0] * U[1][2]; U[2][2] = U[0][0] * U[1][1] - U[0][1] * U[1][0];
-  V[2][0] = V[0][1] * V[1][2] - V[0][2] * V[1][1]; V[2][1] = V[0][2] * V[1][0] - V[0][0] * V[1][2]; V[2][2] = V[0][0] * V[1][1] - V[0][1] * V[1][0];
+  hyp_detail::cross3(U[0], U[1], U[2]);
+  hyp_detail::cross3(V[0], V[1], V[2]);
   // s1 = s2 for an essential matrix, so (v1, v2) is any orthonormal pair of their plane and rounding alone decides which way round it
   // runs — which swaps (R1, +t) with (R2, -t).  Fixed here: the component of v3 with the largest magnitude (the first such) is positive.
   int lead = 0;
@@ -74,35 +71,20 @@ inline bool essential_svd(const double E[9], double U[3][3] /* [column][row] */,
 // the pieces of eight_point, apart so that the tests can seed errors between them
 struct Hartley { double ca[2], cb[2], sa, sb; };   // x' = (x - c) / s per side
 inline bool hartley(const double* na, const double* nb, const int32_t* idx, int m, Hartley& H) {
-  H.ca[0] = H.ca[1] = H.cb[0] = H.cb[1] = 0.0; H.sa = H.sb = 0.0;
-  for (int i = 0; i < m; ++i) {
-    const size_t j = 2 * (size_t)idx[i];
-    H.ca[0] += na[j] / m; H.ca[1] += na[j + 1] / m; H.cb[0] += nb[j] / m; H.cb[1] += nb[j + 1] / m;
-  }
-  for (int i = 0; i < m; ++i) {
-    const size_t j = 2 * (size_t)idx[i];
-    H.sa += std::hypot(na[j] - H.ca[0], na[j + 1] - H.ca[1]) / m; H.sb += std::hypot(nb[j] - H.cb[0], nb[j + 1] - H.cb[1]) / m;
-  }
-  if (!(H.sa > 0.0) || !(H.sb > 0.0)) return false;
-  H.sa /= 1.4142135623730951; H.sb /= 1.4142135623730951;
-  return true;
+  const bool a = hyp_detail::hartley_side(na, idx, m, H.ca, &H.sa), b = hyp_detail::hartley_side(nb, idx, m, H.cb, &H.sb);
+  return a && b;
 }
 // the null direction of the m epipolar constraints in the coordinates of H, taken back to the normalised image coordinates; false: ambiguous
 inline bool null_matrix(const double* na, const double* nb, const int32_t* idx, int m, const Hartley& H, double F[9]) {
-  double ata[12][12] = {};
+  double ata[9][9] = {};
   for (int i = 0; i < m; ++i) {
     const size_t j = 2 * (size_t)idx[i];
     const double xa = (na[j] - H.ca[0]) / H.sa, ya = (na[j + 1] - H.ca[1]) / H.sa, xb = (nb[j] - H.cb[0]) / H.sb, yb = (nb[j + 1] - H.cb[1]) / H.sb;
     const double r[9] = {xb * xa, xb * ya, xb, yb * xa, yb * ya, yb, xa, ya, 1.0};
     for (int a = 0; a < 9; ++a) for (int b = 0; b < 9; ++b) ata[a][b] += r[a] * r[b];
   }
-  double big = 0.0;
-  for (int a = 0; a < 9; ++a) big += ata[a][a];
-  if (!(big > 0.0)) return false;
-  for (int a = 9; a < 12; ++a) ata[a][a] = 2.0 * big;   // three idle unknowns far from the null space
-  double ev[12], gap[3];
-  pnp_detail::smallest_eigenvector12(ata, ev, gap);
-  if (!(gap[1] > 1e-9 * gap[2]) || !(gap[0] < 0.05 * gap[1])) return false;   // a second null direction: a plane, or no baseline
+  double ev[9];
+  if (!hyp_detail::null_vector9(ata, ev)) return false;   // a second null direction: a plane, or no baseline
   // undo the normalisation: F = Tb^T Fn Ta, T = [[1/s 0 -cx/s] [0 1/s -cy/s] [0 0 1]]
   double M[9];
   for (int r = 0; r < 3; ++r) {
@@ -202,7 +184,7 @@ inline bool score(const double* na, const double* nb, int n, const double E[9], 
   for (int c = 1; c < 4; ++c) if (front[c] > front[best]) best = c;
   const double tb[3] = {(best & 1) ? -C.t[0] : C.t[0], (best & 1) ? -C.t[1] : C.t[1], (best & 1) ? -C.t[2] : C.t[2]};
   double out[6];
-  if (!pose_from_rt(C.R[best >> 1], tb, out)) return false;
+  if (!hyp_detail::pose_from_rt(C.R[best >> 1], tb, out)) return false;
   for (int k = 0; k < 6; ++k) pose[k] = out[k];
   *num_inliers = inl;
   for (int c = 0; c < 4; ++c) num_front[c] = front[c];
@@ -219,7 +201,7 @@ constexpr int kCubic[10][4] = {{0, 2, 4, 5}, {2, 3, 8, 9}, {4, 8, 10, 11}, {5, 9
                                {8, 6, 13, 14}, {9, 7, 14, 15}, {10, 13, 16, 17}, {11, 14, 17, 18}, {12, 15, 18, 19}};
 constexpr double kFiveRankTol = 1e-7;    // a Householder diagonal not above this times the longest constraint row: a fifth null direction
 constexpr double kFivePivotTol = 1e-7;   // an elimination pivot not above this times the largest entry of the 10 x 20 matrix: singular
-constexpr int kFiveBisections = 40, kFiveNewton = 2, kFivePolish = 2;
+constexpr int kFiveNewton = 2, kFivePolish = 2;
 
 struct FivePointDiag { double rank_ratio = -1.0, pivot_ratio = -1.0; };   // the smallest of each quantity the two tolerances are compared with
 
@@ -333,24 +315,8 @@ inline void fp_eliminant(const double B[3][3][5], double p[11]) {
     for (int a = 0; a < 7; ++a) for (int b = 0; b < 5; ++b) p[a + b] += C[a] * B[r][2][b];
   }
 }
-inline double fp_eval(const double* c, int deg, double t) {
-  double h = c[deg];
-  for (int k = deg - 1; k >= 0; --k) h = h * t + c[k];
-  return h;
-}
-// as pnp_detail::p3p_bisect: the root of a polynomial that is monotonic on [lo, hi], where it changes sign there; otherwise hi
-inline bool fp_bisect(const double* c, int deg, double lo, double hi, double* root) {
-  *root = hi;
-  const bool plo = fp_eval(c, deg, lo) > 0.0, phi = fp_eval(c, deg, hi) > 0.0;
-  if (plo == phi) return false;
-  for (int it = 0; it < kFiveBisections; ++it) {
-    const double mid = 0.5 * (lo + hi);
-    if ((fp_eval(c, deg, mid) > 0.0) == plo) lo = mid; else hi = mid;
-  }
-  *root = 0.5 * (lo + hi);
-  return true;
-}
 // the real roots of a degree-10 polynomial in [-1, 1], ascending: the roots of each derivative bracket those of the one above it
+// (hyp_detail::poly_bisect, its fixed kBisections halvings per bracket)
 inline int fp_roots_unit(const double p[11], double roots[10], int newton = kFiveNewton) {
   double c[11][11], edge[12], next[12];
   for (int k = 0; k < 11; ++k) c[10][k] = p[k];
@@ -360,11 +326,11 @@ inline int fp_roots_unit(const double p[11], double roots[10], int newton = kFiv
   for (int d = 1; d <= 10; ++d) {
     next[0] = -1.0;
     for (int i = 0; i < d; ++i) {
-      const bool found = fp_bisect(c[d], d, edge[i], edge[i + 1], &next[i + 1]);
+      const bool found = hyp_detail::poly_bisect(c[d], d, edge[i], edge[i + 1], &next[i + 1]);
       if (d < 10 || !found) continue;
       double t = next[i + 1];
       for (int it = 0; it < newton; ++it) {   // Newton on the polynomial, a step taken only while it stays inside [-1, 1]
-        const double tn = t - fp_eval(c[10], 10, t) / fp_eval(c[9], 9, t);
+        const double tn = t - hyp_detail::poly_eval(c[10], 10, t) / hyp_detail::poly_eval(c[9], 9, t);
         if (tn >= -1.0 && tn <= 1.0) t = tn;
       }
       roots[count++] = t;
@@ -419,7 +385,7 @@ inline void fp_polish(const double N[4][9], double v[3], int steps) {
 // unit Frobenius norm and signed; false: not finite
 inline bool fp_solution(const double N[4][9], const double B[3][3][5], double z, double E[9], int polish = kFivePolish) {
   double b[3][3];
-  for (int r = 0; r < 3; ++r) for (int v = 0; v < 3; ++v) b[r][v] = fp_eval(B[r][v], 4, z);
+  for (int r = 0; r < 3; ++r) for (int v = 0; v < 3; ++v) b[r][v] = hyp_detail::poly_eval(B[r][v], 4, z);
   const double C[3] = {b[1][0] * b[2][1] - b[2][0] * b[1][1], b[2][0] * b[0][1] - b[0][0] * b[2][1], b[0][0] * b[1][1] - b[1][0] * b[0][1]};
   int k = 0;
   for (int r = 1; r < 3; ++r) if (std::fabs(C[r]) > std::fabs(C[k])) k = r;
@@ -543,7 +509,7 @@ inline TwoViewResult ransac(int n, const TwoViewOptions& opt, Hypotheses&& hypot
   if (n < 8 || opt.iterations <= 0) return res;
   const int T = opt.iterations;
   const int m = opt.solver == TwoViewOptions::EssentialSolver::FivePoint ? 5 : 8;
-  const std::vector<int32_t> subsets = pnp_detail::distinct_subsets(n, m, T, opt.rng_state);
+  const std::vector<int32_t> subsets = hyp_detail::distinct_subsets(n, m, T, opt.rng_state);
   std::vector<double> E((size_t)T * 9), poses((size_t)T * 6);
   std::vector<uint8_t> status((size_t)T);
   std::vector<int32_t> inl((size_t)T), front((size_t)T * 4);
@@ -589,7 +555,7 @@ inline TwoViewResult ransac(int n, const TwoViewOptions& opt, Hypotheses&& hypot
 inline TwoViewResult host_ransac(const float* xy_a, const float* xy_b, int n, const double cam_a[NUM_CAM_PARAMS], const double cam_b[NUM_CAM_PARAMS],
                                  const TwoViewOptions& opt) {
   if (n < 8) return ransac(n, opt, [](auto&&...) {}, [](auto&&...) {});
-  const std::vector<double> na = pnp_detail::normalised_points(cam_a, xy_a, n), nb = pnp_detail::normalised_points(cam_b, xy_b, n);
+  const std::vector<double> na = hyp_detail::normalised_points(cam_a, xy_a, n), nb = hyp_detail::normalised_points(cam_b, xy_b, n);
   const double f2 = mean_focal2(cam_a, cam_b), thr2 = opt.threshold_px * opt.threshold_px;
   return ransac(n, opt,
     [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
@@ -609,7 +575,7 @@ inline TwoViewResult host_ransac(const float* xy_a, const float* xy_b, int n, co
 }
 }  // namespace epi_detail
 
-// RANSAC over eight-point hypotheses: `iterations` subsets from pnp_detail::distinct_subsets(n, 8, ...), all scored in one device call
+// RANSAC over eight-point hypotheses: `iterations` subsets from hyp_detail::distinct_subsets(n, 8, ...), all scored in one device call
 // (rsba_epipolar_hypotheses); the most inliers win, ties go to the lowest task.  With opt.solver = FivePoint the subsets are
 // distinct_subsets(n, 5, ...) and the call is rsba_epipolar_hypotheses_five_point, which hands back each subset's best solution; a tie in
 // inliers between subsets then goes to the one with more of them in front before it goes to the lowest task, and the rest of the loop is
@@ -621,26 +587,26 @@ inline TwoViewResult findEssentialRansac(const float* xy_a, const float* xy_b, i
   if (!opt.hypotheses_on_device) return epi_detail::host_ransac(xy_a, xy_b, n, cam_a, cam_b, opt);
   return epi_detail::ransac(n, opt,
     [&](const int32_t* sub, int m, int tasks, double* E, double* poses, uint8_t* status, int32_t* inl, int32_t* front) {
-      if (m == 5) pnp_detail::check(rsba_epipolar_hypotheses_five_point(device, cam_a, cam_b, xy_a, xy_b, n, sub, tasks, opt.threshold_px, E, poses, status, inl, front, nullptr));
-      else pnp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
+      if (m == 5) hyp_detail::check(rsba_epipolar_hypotheses_five_point(device, cam_a, cam_b, xy_a, xy_b, n, sub, tasks, opt.threshold_px, E, poses, status, inl, front, nullptr));
+      else hyp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
     },
-    [&](const double E[9], uint8_t* mask) { pnp_detail::check(rsba_epipolar_inliers(device, cam_a, cam_b, xy_a, xy_b, n, E, opt.threshold_px, mask)); });
+    [&](const double E[9], uint8_t* mask) { hyp_detail::check(rsba_epipolar_inliers(device, cam_a, cam_b, xy_a, xy_b, n, E, opt.threshold_px, mask)); });
 }
 
 namespace epi_detail {
 // the pose of a camera that sees x = R_rel x_A + t_rel, where camera A has pose_a: x = R_rel R_A (X - c_A) + t_rel
 inline bool compose_pose(const double pose_a[6], const double rel[6], double out[6]) {
   double rvec[3], tvec[3], R[9];
-  pnp_detail::from_pose(rel, rvec, tvec);
+  hyp_detail::from_pose(rel, rvec, tvec);
   for (int k = 0; k < 3; ++k) {
     const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
     double ra[3], rb[3];
-    pnp_detail::rotate(pose_a, e, ra);
-    pnp_detail::rotate(rvec, ra, rb);
+    hyp_detail::rotate(pose_a, e, ra);
+    hyp_detail::rotate(rvec, ra, rb);
     for (int r = 0; r < 3; ++r) R[3 * r + k] = rb[r];
   }
   for (int r = 0; r < 3; ++r) tvec[r] -= R[3 * r] * pose_a[3] + R[3 * r + 1] * pose_a[4] + R[3 * r + 2] * pose_a[5];
-  return pose_from_rt(R, tvec, out);
+  return hyp_detail::pose_from_rt(R, tvec, out);
 }
 }  // namespace epi_detail
 

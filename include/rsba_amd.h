@@ -499,7 +499,7 @@ int32_t rsba_pnp_inliers(int32_t device, const double* cam, int32_t shutter, con
 
 /* == the start poses of the global-shutter RANSAC hypotheses (include/rsba/solve_rs_pnp.hpp: solveGsPnPRansac, what cv::solvePnPRansac
  * does at solveRSpnp.cpp:437-449 and VideoSfMHandler.cc:715-730): pnp_detail::dlt_pose for every subset, on the device.  The image points
- * are undistorted and normalised once per call (pnp_detail::normalised_point), then one lane per subset runs the whole of dlt_pose: the
+ * are undistorted and normalised once per call (hyp_detail::normalised_point, include/rsba/hyp_host.hpp), then one lane per subset runs the whole of dlt_pose: the
  * collinear / planar tests on the 3 x 3 scatter, the homography of a planar target or the 12 x 12 Gram matrix with its two gap tests, the
  * nearest rotation, the pose.  m >= 6.  poses_out are rsba's 6-vectors.
  * status[t]: 0 declined (degenerate subset; poses_out[t] untouched), 1 general DLT, 2 planar branch. */
@@ -517,7 +517,7 @@ int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* o
 /* == the minimal solver of the global-shutter RANSAC (what cv::solvePnPRansac(..., CV_P3P) runs per sample, VideoSfMHandler.cc:726-731;
  * OpenCV is not in the reference tree, so this text is the definition; include/rsba/solve_rs_pnp.hpp: pnp_detail::p3p_pose is its host form).
  * A subset has four indices: the first three are solved, the fourth chooses among the solutions.
- *   Inputs.  Image points undistorted and normalised as pnp_detail::normalised_point does; bearings j_i = (x, y, 1) / |(x, y, 1)|.
+ *   Inputs.  Image points undistorted and normalised as hyp_detail::normalised_point does; bearings j_i = (x, y, 1) / |(x, y, 1)|.
  *   Solve.  Grunert's formulation: with depths s_i along j_i, sides a = |P2 P3|, b = |P1 P3|, c = |P1 P2| and the cosines of the angles
  *     between the bearings, s2 = u s1, s3 = v s1 turn the three cosine laws into u = N(v) / (2 D(v)), D(v) = j1.j2 - v j2.j3, and a
  *     quartic in v.  All of its roots with three positive depths are looked for, in t = v / (1 + v) in (0, 1): the four intervals between
@@ -531,7 +531,7 @@ int32_t rsba_pnp_gs_hypotheses(int32_t device, const double* cam, const float* o
  *     with |D| <= 1e-12 (in units of s1 + s3) is dropped.
  *   Pose per solution.  The rigid motion that takes the three world points onto s_i j_i: the two triangles are congruent, so it is
  *     F E^T for their orthonormal triads (first edge, normal, their cross product) and maps centroid to centroid; converted to
- *     rsba's 6-vector by pnp_detail::pose_from_rt.
+ *     rsba's 6-vector by hyp_detail::pose_from_rt.
  *   Choice.  A solution is admissible when its three depths are positive (above 1e-9 b: the camera centre in a world point, where the
  *     lost root ends up under rounding, is no solution) and it puts the fourth point in front of the camera (z > 0).
  *     Among the admissible ones the smallest distance between the fourth point's projection and its normalised image point wins; ties go to
@@ -556,7 +556,7 @@ int32_t rsba_pnp_gs_hypotheses_p3p(int32_t device, const double* cam, const floa
  * poses for createTracks / PnP to start from.  The reference has no such step, so this text is the definition; include/rsba/two_view.hpp
  * (epi_detail::eight_point, decompose, score) is its host form and findEssentialRansac / initializeTwoView the callers.
  *   Inputs.  xy_a, xy_b [n][2] float: pixel coordinates of correspondence i in frame A and frame B; cam_a, cam_b the 9 sfm intrinsics of the two
- *     frames.  Both sides are undistorted and normalised once per call (pnp_detail::normalised_point): a = (xa, ya, 1), b = (xb, yb, 1).
+ *     frames.  Both sides are undistorted and normalised once per call (hyp_detail::normalised_point): a = (xa, ya, 1), b = (xb, yb, 1).
  *     E is row-major, b^T E a = 0; camera A is the origin, camera B sees x_B = R x_A + t, E = [t]x R.
  *   Eight-point (m >= 8 indices per subset).  Hartley normalisation of each side's m points (centroid; mean distance scaled to sqrt 2); the
  *     9 x 9 Gram matrix of the rows (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1); its smallest eigenvector by cyclic Jacobi (60 sweeps at
@@ -574,7 +574,7 @@ int32_t rsba_pnp_gs_hypotheses_p3p(int32_t device, const double* cam, const floa
  *     inlier iff d^2 f^2 <= threshold_px^2, f = (fx_a + fy_a + fx_b + fy_b) / 4.  Both deciding comparisons are evaluated with the host form's
  *     operations in the host form's order, every product and sum rounded on its own.
  *   Score.  num_inliers[t]; num_front[t][c] = the inliers in front for candidate c; the candidate with the most wins, ties go to the first;
- *     poses_out[t] = pnp_detail::pose_from_rt(R, t) of the winner — camera B in A's frame, rsba's 6-vector, unit baseline.
+ *     poses_out[t] = hyp_detail::pose_from_rt(R, t) of the winner — camera B in A's frame, rsba's 6-vector, unit baseline.
  *     Declined (status 0; the counts are zero, poses_out[t] untouched): s2 not above 1e-6 s1, or a pose that is not finite.
  * rsba_epipolar_eight_point: one lane per subset, fp64; a subset's result does not depend on where it sits in the call.
  * rsba_epipolar_score: scores the given matrices E [num_tasks][9], one wave per matrix; the counts are integer sums.

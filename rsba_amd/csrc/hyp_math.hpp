@@ -1,6 +1,6 @@
 // The small algebra the hypothesis kernels share (kernels_pnp_dlt.hip, kernels_pnp_p3p.hip, kernels_epipolar.hip): the device restatement of
-// include/rsba/solve_rs_pnp.hpp's pnp_detail::rotate, pose_from_rt, eigen3 and smallest_eigenvector12, which include/rsba/two_view.hpp calls
-// too.  The host functions are the definition; fp64 throughout, every loop with the host's fixed bound (40 / 60 Jacobi sweeps).  No anonymous
+// include/rsba/hyp_host.hpp's hyp_detail::rotate, pose_from_rt, eigen3 and smallest_eigenvector12, which solve_rs_pnp.hpp and two_view.hpp call
+// alike.  The host functions are the definition; fp64 throughout, every loop with the host's fixed bound (40 / 60 Jacobi sweeps).  No anonymous
 // namespace: a tool that includes two kernel files into one translation unit sees one definition.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@ namespace rsba {
 // entry (a, b) of a symmetric matrix kept as its lower triangle, row by row
 __device__ __forceinline__ int sym(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
 
-// ceres::AngleAxisRotatePoint, as pnp_detail::rotate
+// ceres::AngleAxisRotatePoint, as hyp_detail::rotate
 __device__ __forceinline__ void rotate(const double w[3], const double p[3], double out[3]) {
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   const double wxp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
@@ -27,7 +27,7 @@ __device__ __forceinline__ void rotate(const double w[3], const double p[3], dou
   }
 }
 
-// pnp_detail::pose_from_rt: x_cam = R X + tvec as the pose (rvec, -R(rvec)^T tvec); false where one of the six numbers is not finite
+// hyp_detail::pose_from_rt: x_cam = R X + tvec as the pose (rvec, -R(rvec)^T tvec); false where one of the six numbers is not finite
 __device__ __forceinline__ bool pose_from_rt(const double R[9], const double tvec[3], double pose[6]) {
   double rvec[3];
   const double tr = R[0] + R[4] + R[8], csn = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0))), th = acos(csn);
@@ -52,7 +52,7 @@ __device__ __forceinline__ bool pose_from_rt(const double R[9], const double tve
   return finite;
 }
 
-// pnp_detail::eigen3 in registers (every index is a compile-time constant after unrolling): values ascending, v[r][k] = component r of the
+// hyp_detail::eigen3 in registers (every index is a compile-time constant after unrolling): values ascending, v[r][k] = component r of the
 // unit eigenvector of val[k]
 __device__ __forceinline__ void eigen3(const double s[6], double val[3], double v[3][3]) {
   double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
@@ -94,7 +94,7 @@ __device__ __forceinline__ void eigen3(const double s[6], double val[3], double 
   for (int r = 0; r < 3; ++r) val[r] = d[r];
 }
 
-// pnp_detail::smallest_eigenvector12 on N unknowns, one lane per matrix: cyclic Jacobi on the lower triangle G (N (N + 1) / 2 entries) with the
+// hyp_detail::smallest_eigenvector12 on N unknowns, one lane per matrix: cyclic Jacobi on the lower triangle G (N (N + 1) / 2 entries) with the
 // accumulated rotations V (N x N), both in LDS and lane-interleaved (entry e of this lane at [e * BLOCK]: conflict-free, and indexable by the
 // run-time (p, q) of a rotation, which registers are not).  The rotation is applied in its symmetric form (rows and columns at once on the
 // triangle, the pivot set to zero) — the same rotation angles as the host's column-then-row update, a different operation order.  `largest` starts

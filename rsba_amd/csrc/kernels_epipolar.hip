@@ -1,5 +1,5 @@
 // Essential-matrix hypotheses of the two-view bootstrap (include/rsba/two_view.hpp: epi_detail::eight_point, decompose, score and what they
-// call — hartley, null_matrix, essential_svd, sampson_inlier, in_front, pnp_detail::eigen3, smallest_eigenvector12, pose_from_rt), for every
+// call — hartley, null_matrix, essential_svd, sampson_inlier, in_front, hyp_detail::eigen3, smallest_eigenvector12, pose_from_rt), for every
 // subset at once.  The host functions are the definition; this file restates them for the device, fp64 throughout, every loop with the
 // host's fixed bound (60 / 40 Jacobi sweeps).
 //   epipolar_eight_point_kernel  one lane per subset, one wave per workgroup.  The 9 x 9 Gram matrix (lower triangle, 45 entries) and the

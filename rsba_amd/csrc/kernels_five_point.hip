@@ -1,5 +1,5 @@
 // The five-point solver of the two-view bootstrap (include/rsba_amd.h: rsba_epipolar_five_point; include/rsba/two_view.hpp:
-// epi_detail::five_point and what it calls — fp_null_space, fp_constraints, fp_eliminate, fp_reduce, fp_eliminant, fp_roots_unit, fp_bisect,
+// epi_detail::five_point and what it calls — fp_null_space, fp_constraints, fp_eliminate, fp_reduce, fp_eliminant, fp_roots_unit, hyp_detail::poly_bisect,
 // fp_polish, fp_solution, fp_key), for every subset at once.  The host functions are the definition; this file restates them for the
 // device, fp64 throughout, every loop with the host's fixed bound, and — the whole file — without contraction: every product and sum is
 // rounded on its own, in the host's order, so the pivots, the brackets of the roots, the minor that gives (x, y), the sign and the order
@@ -58,14 +58,14 @@ template <int LANES>
 struct Lane {
   double* S;   // this lane's column of the workgroup's LDS
   __device__ __forceinline__ double& operator()(int e) const { return S[e * LANES]; }
-  // epi_detail::fp_eval on coefficients at offset c
+  // hyp_detail::poly_eval on coefficients at offset c
   __device__ __forceinline__ double eval(int c, int deg, double t) const {
     double h = (*this)(c + deg);
 #pragma unroll 1
     for (int k = deg - 1; k >= 0; --k) h = h * t + (*this)(c + k);
     return h;
   }
-  // epi_detail::fp_bisect
+  // hyp_detail::poly_bisect
   __device__ __forceinline__ bool bisect(int c, int deg, double lo, double hi, double* root) const {
     *root = hi;
     const bool plo = eval(c, deg, lo) > 0.0, phi = eval(c, deg, hi) > 0.0;

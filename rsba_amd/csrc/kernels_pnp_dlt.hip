@@ -1,5 +1,5 @@
-// Start poses of the global-shutter RANSAC hypotheses (include/rsba/solve_rs_pnp.hpp: pnp_detail::normalised_point, dlt_pose and
-// what dlt_pose calls — eigen3, planar_pose, smallest_eigenvector12, nearest_rotation, pose_from_rt), for every subset at once.
+// Start poses of the global-shutter RANSAC hypotheses (include/rsba/hyp_host.hpp: hyp_detail::normalised_point; solve_rs_pnp.hpp: pnp_detail::dlt_pose and
+// what dlt_pose calls — planar_pose and hyp_detail::eigen3, smallest_eigenvector12, nearest_rotation, pose_from_rt), for every subset at once.
 // The host functions are the definition; this file restates them for the device, fp64 throughout, every loop with the host's
 // fixed bound (60 / 40 Jacobi sweeps, 30 nearest-rotation steps, 20 undistortion steps).
 //   pnp_normalise_kernel  one lane per image point, once per call

@@ -1,5 +1,5 @@
 // The minimal solver of the global-shutter RANSAC hypotheses (include/rsba_amd.h: rsba_pnp_p3p; include/rsba/solve_rs_pnp.hpp:
-// pnp_detail::p3p_pose and what it calls — p3p_bearing, p3p_setup, p3p_roots, p3p_depths, p3p_polish, p3p_rt, p3p_fourth, pose_from_rt),
+// pnp_detail::p3p_pose and what it calls — p3p_bearing, p3p_setup, p3p_roots, p3p_depths, p3p_polish, p3p_rt, p3p_fourth, hyp_detail::pose_from_rt),
 // for every four-point subset at once.  The host functions are the definition; this file restates them for the device, fp64 throughout,
 // every loop with the host's fixed bound (40 bisection steps per interval, two Newton steps per root, two per depth triple).
 //   pnp_p3p_kernel   one lane per subset, one wave per workgroup.  Everything lives in registers: every array below is indexed by

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
     std::printf("\n");
     for (uint8_t b : r.inliers) std::printf("%d ", (int)b);
     std::printf("\n");
-    const std::vector<double> na = pnp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = pnp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
+    const std::vector<double> na = hyp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = hyp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
     const double f2 = mean_focal2(S.cam_a, S.cam_b), thr2 = opt.threshold_px * opt.threshold_px;
     for (int i = 0; i < S.n; ++i) {
       double d2 = 0.0;
@@ -81,8 +81,8 @@ int main(int argc, char** argv) {
     const int T = std::atoi(argv[3]);
     const double thr = std::atof(argv[4]);
     if (S.n < 5 || T <= 0) return 2;
-    const std::vector<int32_t> sub = pnp_detail::distinct_subsets(S.n, 5, T, std::strtoull(argv[5], nullptr, 0));
-    const std::vector<double> na = pnp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = pnp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
+    const std::vector<int32_t> sub = hyp_detail::distinct_subsets(S.n, 5, T, std::strtoull(argv[5], nullptr, 0));
+    const std::vector<double> na = hyp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = hyp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
     for (int t = 0; t < T; ++t) {
       double E[9] = {}, pose[6] = {};
       int32_t inl = 0, front[4] = {0, 0, 0, 0};
@@ -110,7 +110,7 @@ int main(int argc, char** argv) {
     std::vector<float> xa((size_t)n * 2), xb((size_t)n * 2); std::vector<int32_t> sub((size_t)T * m);
     if (std::fread(xa.data(), 4, xa.size(), f) != xa.size() || std::fread(xb.data(), 4, xb.size(), f) != xb.size() || std::fread(sub.data(), 4, sub.size(), f) != sub.size()) return 2;
     for (int32_t s : sub) if (s < 0 || s >= n) return 2;
-    const std::vector<double> na = pnp_detail::normalised_points(cam_a, xa.data(), n), nb = pnp_detail::normalised_points(cam_b, xb.data(), n);
+    const std::vector<double> na = hyp_detail::normalised_points(cam_a, xa.data(), n), nb = hyp_detail::normalised_points(cam_b, xb.data(), n);
     for (int t = 0; t < T; ++t) print_subset(na, nb, n, &sub[(size_t)t * m], mode, mean_focal2(cam_a, cam_b), thr * thr);
   }
   std::fclose(f);

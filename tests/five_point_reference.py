@@ -323,16 +323,6 @@ def outlier_draw(fb, rolling, draw, _cache={}):
 
 
 # ------------------------------------------- the host program (tests/five_point_host.cpp), for the tests and make_five_point_bound.py -------------------------------------------
-def build_host(directory, extra_flags=()):
-    """compiles tests/five_point_host.cpp (host code only: nothing of the library is linked) -> the program's path"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(str(directory), "five_point_host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", *extra_flags, "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "five_point_host.cpp"), "-o", exe], check=True)
-    return exe
-
-
 def _per_subset(r):
     r = np.array(r)
     return dict(status=r[:, 0].astype(int), count=r[:, 1].astype(int), rank_ratio=r[:, 2], pivot_ratio=r[:, 3], E=r[:, 4:94].reshape(-1, 10, 9),
@@ -377,7 +367,7 @@ def run_host_ransac(exe, directory, scene, solver, name="scene5"):
 
 
 def distinct_subsets(n, m, iterations, state):
-    """pnp_detail::distinct_subsets restated (test_two_view_reference.py holds the C++ to this generator)"""
+    """hyp_detail::distinct_subsets restated (test_two_view_reference.py holds the C++ to this generator)"""
     out = []
     for _ in range(iterations):
         pick = []

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import five_point_reference as F  # noqa: E402
 import two_view_reference as R  # noqa: E402
+from helpers import build_host_program  # noqa: E402
 
 
 def successes(exe, d, solver):
@@ -37,7 +38,7 @@ def successes(exe, d, solver):
 def measure():
     cs = F.cases()
     with tempfile.TemporaryDirectory() as d:
-        exe = F.build_host(d)
+        exe = build_host_program("five_point_host", d)
         got = F.run_host(exe, d, list(cs.values()))
         per_case = {name: F.worst_error(F.reference(name), h["status"], h["count"], h["E"], h["poses"]) for name, h in zip(cs, got)}
         ransac = {}

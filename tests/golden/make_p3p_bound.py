@@ -16,7 +16,9 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import p3p_reference as R  # noqa: E402
+from helpers import build_host_program  # noqa: E402
 
 
 APART = ("half_turn", "sliver")   # recorded apart, each bounds only itself
@@ -25,7 +27,7 @@ APART = ("half_turn", "sliver")   # recorded apart, each bounds only itself
 def measure():
     cs = R.cases()
     with tempfile.TemporaryDirectory() as d:
-        got = R.run_host(R.build_host(d), d, list(cs.values()))
+        got = R.run_host(build_host_program("p3p_host", d), d, list(cs.values()))
     return {name: R.worst_error(R.reference(name), st, poses) for name, (st, _, poses) in zip(cs, got)}
 
 

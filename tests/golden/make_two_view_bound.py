@@ -20,12 +20,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import two_view_reference as R  # noqa: E402
+from helpers import build_host_program  # noqa: E402
 
 
 def measure():
     cs = R.cases()
     with tempfile.TemporaryDirectory() as d:
-        exe = R.build_host(d)
+        exe = build_host_program("two_view_host", d)
         got = R.run_host(exe, d, list(cs.values()))
         per_case = {name: R.worst_error(R.reference(name), h["status"], h["E"], h["poses"]) for name, h in zip(cs, got)}
         ransac = {}

@@ -14,6 +14,16 @@ def load_golden(name):
         return json.load(f)
 
 
+def build_host_program(name, directory, extra_flags=()):
+    """compiles tests/<name>.cpp over the headers of include/ (host code only: nothing of the library is linked) into `directory`
+    -> the program's path"""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(str(directory), name)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", *extra_flags, "-I" + os.path.join(root, "include"), os.path.join(root, "tests", name + ".cpp"), "-o", exe], check=True)
+    return exe
+
+
 def problem_from_case(c) -> BAProblem:
     """One-observation problem for a per_observation.json case."""
     poses = [c["pose0"]] if c["pose1"] is None else [c["pose0"], c["pose1"]]

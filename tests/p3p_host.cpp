@@ -3,7 +3,7 @@
 //   p3p_host <cases.bin> [mode]   cases.bin: int32 count; per case int32 n, T, double cam[9], float X[n][3], float xy[n][2], int32 subsets[T][4]
 //     mode 0 (default) p3p_pose as it is; the seeded errors of the test, composed from the same pieces:
 //     mode 1 the runner-up solution is chosen, mode 2 the polish of the depths is dropped, mode 3 the bearing (x, y, 1) is not normalised
-//   p3p_host subsets <n> <m> <iterations> <rng_state>   prints pnp_detail::distinct_subsets, one subset per line
+//   p3p_host subsets <n> <m> <iterations> <rng_state>   prints hyp_detail::distinct_subsets, one subset per line
 //   stdout, per subset: "<status 0|1> <num_solutions> <pose[0..6) %.17g>"
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +43,7 @@ static bool seeded(const float* X, const double* nrm, const int32_t idx[4], int 
   for (int i = 0; i < found; ++i) if (i != best && (second < 0 || dist[i] < dist[second])) second = i;
   double R[9], tvec[3];
   p3p_rt(S, depth_of[mode == 1 && second >= 0 ? second : best], R, tvec);
-  if (!pose_from_rt(R, tvec, pose)) return false;
+  if (!rsba_amd::hyp_detail::pose_from_rt(R, tvec, pose)) return false;
   *num = found;
   return true;
 }
@@ -51,7 +51,7 @@ static bool seeded(const float* X, const double* nrm, const int32_t idx[4], int 
 int main(int argc, char** argv) {
   if (argc >= 6 && std::string(argv[1]) == "subsets") {
     const int n = std::atoi(argv[2]), m = std::atoi(argv[3]), it = std::atoi(argv[4]);
-    const std::vector<int32_t> s = distinct_subsets(n, m, it, std::strtoull(argv[5], nullptr, 0));
+    const std::vector<int32_t> s = rsba_amd::hyp_detail::distinct_subsets(n, m, it, std::strtoull(argv[5], nullptr, 0));
     for (int t = 0; t < it; ++t) { for (int k = 0; k < m; ++k) std::printf("%d ", s[(size_t)t * m + k]); std::printf("\n"); }
     return 0;
   }
@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
     std::vector<float> X((size_t)n * 3), xy((size_t)n * 2); std::vector<int32_t> sub((size_t)T * 4);
     if (std::fread(X.data(), 4, X.size(), f) != X.size() || std::fread(xy.data(), 4, xy.size(), f) != xy.size() || std::fread(sub.data(), 4, sub.size(), f) != sub.size()) return 2;
     for (int32_t s : sub) if (s < 0 || s >= n) return 2;
-    const std::vector<double> nrm = normalised_points(cam, xy.data(), n);
+    const std::vector<double> nrm = rsba_amd::hyp_detail::normalised_points(cam, xy.data(), n);
     for (int t = 0; t < T; ++t) {
       double p[6] = {0, 0, 0, 0, 0, 0};
       int num = 0;

@@ -67,7 +67,7 @@ def _rotate(w, p):
 
 
 def _pose_from_rt(R, tvec):
-    """pnp_detail::pose_from_rt with its three branches, in extended precision"""
+    """hyp_detail::pose_from_rt with its three branches, in extended precision"""
     tr = R[0, 0] + R[1, 1] + R[2, 2]
     cs = min(mpf(1), max(mpf(-1), (tr - 1) / 2))
     th = acos(cs)
@@ -343,16 +343,6 @@ def write_case_file(path, case_list):
         for c in case_list:
             f.write(struct.pack("<2i", len(c["X"]), len(c["subsets"]))); f.write(np.asarray(c["cam"], dtype="<f8").tobytes())
             f.write(c["X"].astype("<f4").tobytes()); f.write(c["xy"].astype("<f4").tobytes()); f.write(np.asarray(c["subsets"]).astype("<i4").tobytes())
-
-
-def build_host(directory, extra_flags=()):
-    """compiles tests/p3p_host.cpp (host code only: nothing of the library is linked) -> the program's path"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(str(directory), "p3p_host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", *extra_flags, "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "p3p_host.cpp"), "-o", exe], check=True)
-    return exe
 
 
 def run_host(exe, directory, case_list, mode=0):

@@ -19,7 +19,7 @@ int main(int argc, char** argv) {
     const int n = hdr[0], m = hdr[1], T = hdr[2];
     std::vector<float> X((size_t)n * 3), xy((size_t)n * 2); std::vector<int32_t> sub((size_t)T * m);
     if (std::fread(X.data(), 4, X.size(), f) != X.size() || std::fread(xy.data(), 4, xy.size(), f) != xy.size() || std::fread(sub.data(), 4, sub.size(), f) != sub.size()) return 2;
-    const std::vector<double> nrm = rsba_amd::pnp_detail::normalised_points(cam, xy.data(), n);
+    const std::vector<double> nrm = rsba_amd::hyp_detail::normalised_points(cam, xy.data(), n);
     for (int t = 0; t < T; ++t) {
       double p[6] = {0, 0, 0, 0, 0, 0};
       const bool ok = rsba_amd::pnp_detail::dlt_pose(X.data(), nrm.data(), &sub[(size_t)t * m], m, p);

@@ -1,5 +1,5 @@
 """Extended-precision restatement of the DLT start pose of a RANSAC hypothesis (include/rsba/solve_rs_pnp.hpp:
-pnp_detail::normalised_point and dlt_pose with what it calls), in mpmath at 60 digits, and the fixed case list the host
+hyp_detail::normalised_point and pnp_detail::dlt_pose with what it calls), in mpmath at 60 digits, and the fixed case list the host
 test (test_pnp_dlt_reference.py) and the device test (test_gpu_pnp_dlt.py) share.  It shares no code with the C++: the
 eigen-decompositions are mpmath's (eigsy), not cyclic Jacobi; the nearest rotation is the limit of R <- (R + R^-T) / 2.
 Where the C++ computes in float because its operands are (the quotients point / m that make the centroid), so does this: the

@@ -16,7 +16,7 @@ import pytest
 
 import five_point_reference as F
 import two_view_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 
 MODES = {1: "the factor 1/2 of the trace term dropped", 2: "E transposed", 3: "the Newton steps and the polish removed"}
 
@@ -25,7 +25,7 @@ MODES = {1: "the factor 1/2 of the trace term dropped", 2: "E transposed", 3: "t
 def host(tmp_path_factory):
     """mode -> {case name: per-subset results} from tests/five_point_host.cpp, compiled here"""
     d = tmp_path_factory.mktemp("five_point")
-    exe = F.build_host(d)
+    exe = build_host_program("five_point_host", d)
     cs = F.cases()
     return {mode: dict(zip(cs, F.run_host(exe, d, list(cs.values()), mode))) for mode in (0, 1, 2, 3)}, exe, d
 

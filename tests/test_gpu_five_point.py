@@ -15,7 +15,7 @@ import pytest
 
 import five_point_reference as F
 import two_view_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +42,7 @@ def exe():
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("five_point_gpu")
-    return F.build_host(d), d
+    return build_host_program("five_point_host", d), d
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import pnp_dlt_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 from rsba_amd.problem import GLOBAL
 
 pytestmark = pytest.mark.gpu
@@ -67,8 +67,7 @@ def test_results_do_not_depend_on_where_a_subset_sits_in_the_launch(capi):
 
 def host_dlt(tmp_path, cam, X, xy, subs):
     """(accepted [T], poses [T,6]) of the C++ pnp_detail::dlt_pose (tests/pnp_dlt_host.cpp, host code only)"""
-    exe = str(tmp_path / "pnp_dlt_host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "pnp_dlt_host.cpp"), "-o", exe], check=True)
+    exe = build_host_program("pnp_dlt_host", tmp_path)
     T, m = subs.shape
     with open(tmp_path / "cases.bin", "wb") as f:
         f.write(struct.pack("<i", 1)); f.write(struct.pack("<3i", len(X), m, T)); f.write(np.asarray(cam, dtype="<f8").tobytes())

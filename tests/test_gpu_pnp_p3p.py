@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import p3p_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 from rsba_amd.problem import GLOBAL
 from test_gpu_new_frame import F, Sess, exe, run  # noqa: F401  (exe: the fixture that builds examples/new_frame)
 
@@ -70,7 +70,7 @@ def test_gs_hypotheses_p3p_equal_the_two_step_form(capi, oracle, tmp_path):
     subs = random_subsets(np.random.default_rng(4), len(sc["X"]), 60, 4)
     subs[7] = subs[7][[0, 1, 2, 0]]                              # one degenerate subset: declined by both
     err = 6.0
-    ok, _, starts = R.run_host(R.build_host(tmp_path), tmp_path, [dict(cam=CAM, X=sc["X"], xy=sc["xy"], subsets=subs)])[0]
+    ok, _, starts = R.run_host(build_host_program("p3p_host", tmp_path), tmp_path, [dict(cam=CAM, X=sc["X"], xy=sc["xy"], subsets=subs)])[0]
     acc = np.flatnonzero(ok)
     two = capi.pnp_tasks(CAM, GLOBAL, sc["scan"], sc["X"], sc["xy"], subs[acc], np.concatenate([starts[acc], starts[acc]], axis=1),
                          max_num_iterations=5, reprojection_error=err, drop_coincident=False)

@@ -16,7 +16,7 @@ import pytest
 
 import thrift_encode as T
 import two_view_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 from rsba_amd.scene import make_scene
 from test_gpu_new_frame import average_reprojection_error
 
@@ -45,7 +45,7 @@ def exe():
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("two_view_gpu")
-    return R.build_host(d), d
+    return build_host_program("two_view_host", d), d
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import p3p_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 
 RANDOM_CASES = ("main_pinhole", "main_distorted")
 APART = ("half_turn", "sliver")   # recorded apart in p3p_bound.json (tests/golden/make_p3p_bound.py says why)
@@ -25,7 +25,7 @@ def record(name):
 def host(tmp_path_factory):
     """mode -> {case name: (status, num_solutions, poses)} from tests/p3p_host.cpp, compiled here"""
     d = tmp_path_factory.mktemp("p3p")
-    exe = R.build_host(d)
+    exe = build_host_program("p3p_host", d)
     cs = R.cases()
     return {mode: dict(zip(cs, R.run_host(exe, d, list(cs.values()), mode))) for mode in (0, 1, 2, 3)}, exe, d
 
@@ -114,7 +114,7 @@ def test_a_seeded_error_exceeds_the_device_bound(host, mode, what):
 
 
 def test_the_subset_generator_is_the_restated_one(host):
-    """solveGsPnPRansacP3P scores through the device, so only its sampling is checked here: pnp_detail::distinct_subsets against cv::RNG's
+    """solveGsPnPRansacP3P scores through the device, so only its sampling is checked here: hyp_detail::distinct_subsets against cv::RNG's
     multiply-with-carry and the distinct-index loop of solveGsPnPRansac, restated"""
     _, exe, _ = host
     for n, m, it, state in ((5, 4, 40, 0x9e3779b97f4a7c15), (200, 4, 500, 0x9e3779b97f4a7c15), (24, 6, 30, 0xffffffff)):

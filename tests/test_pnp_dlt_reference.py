@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import pnp_dlt_reference as R
-from helpers import GOLDEN
+from helpers import GOLDEN, build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUND_FILE = os.path.join(GOLDEN, "pnp_dlt_bound.json")
@@ -25,8 +25,7 @@ BOUND_FILE = os.path.join(GOLDEN, "pnp_dlt_bound.json")
 def host_results(tmp_path_factory):
     """name -> [(accepted, pose)] from the C++ dlt_pose, compiled here (host code only: nothing of the library is linked)"""
     d = tmp_path_factory.mktemp("pnp_dlt")
-    exe = str(d / "pnp_dlt_host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "pnp_dlt_host.cpp"), "-o", exe], check=True)
+    exe = build_host_program("pnp_dlt_host", d)
     cs = R.cases()
     with open(d / "cases.bin", "wb") as f:
         f.write(struct.pack("<i", len(cs)))

@@ -20,14 +20,14 @@ import numpy as np
 import pytest
 
 import two_view_reference as R
-from helpers import load_golden
+from helpers import build_host_program, load_golden
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """mode -> {case name: per-subset results} from tests/two_view_host.cpp, compiled here"""
     d = tmp_path_factory.mktemp("two_view")
-    exe = R.build_host(d)
+    exe = build_host_program("two_view_host", d)
     cs = R.cases()
     return {mode: dict(zip(cs, R.run_host(exe, d, list(cs.values()), mode))) for mode in (0, 1, 2, 3)}, exe, d
 

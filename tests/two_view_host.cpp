@@ -10,7 +10,7 @@
 //     scene.bin: int32 n, double cam_a[9], cam_b[9], float xy_a[n][2], xy_b[n][2]
 //     stdout: "<ok> <winner_task> <num_inliers> <num_front> <refits_adopted>", E, pose_b, the inlier flags, d^2 f^2 / thr^2 per correspondence
 //   two_view_host hypotheses <scene.bin> <T> <threshold_px> <rng_state>   the per-subset lines above for the first T subsets of the RANSAC
-//   two_view_host subsets <n> <m> <iterations> <rng_state>   prints pnp_detail::distinct_subsets, one subset per line
+//   two_view_host subsets <n> <m> <iterations> <rng_state>   prints hyp_detail::distinct_subsets, one subset per line
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -78,7 +78,7 @@ static bool read_scene(const char* path, Scene& S) {
 int main(int argc, char** argv) {
   if (argc >= 6 && std::string(argv[1]) == "subsets") {
     const int n = std::atoi(argv[2]), m = std::atoi(argv[3]), it = std::atoi(argv[4]);
-    const std::vector<int32_t> s = pnp_detail::distinct_subsets(n, m, it, std::strtoull(argv[5], nullptr, 0));
+    const std::vector<int32_t> s = hyp_detail::distinct_subsets(n, m, it, std::strtoull(argv[5], nullptr, 0));
     for (int t = 0; t < it; ++t) { for (int k = 0; k < m; ++k) std::printf("%d ", s[(size_t)t * m + k]); std::printf("\n"); }
     return 0;
   }
@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
     std::printf("\n");
     for (uint8_t b : r.inliers) std::printf("%d ", (int)b);
     std::printf("\n");
-    const std::vector<double> na = pnp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = pnp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
+    const std::vector<double> na = hyp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = hyp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
     const double f2 = mean_focal2(S.cam_a, S.cam_b), thr2 = opt.threshold_px * opt.threshold_px;
     for (int i = 0; i < S.n; ++i) {
       double d2 = 0.0;
@@ -112,8 +112,8 @@ int main(int argc, char** argv) {
     const int T = std::atoi(argv[3]);
     const double thr = std::atof(argv[4]);
     if (S.n < 8 || T <= 0) return 2;
-    const std::vector<int32_t> sub = pnp_detail::distinct_subsets(S.n, 8, T, std::strtoull(argv[5], nullptr, 0));
-    const std::vector<double> na = pnp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = pnp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
+    const std::vector<int32_t> sub = hyp_detail::distinct_subsets(S.n, 8, T, std::strtoull(argv[5], nullptr, 0));
+    const std::vector<double> na = hyp_detail::normalised_points(S.cam_a, S.xa.data(), S.n), nb = hyp_detail::normalised_points(S.cam_b, S.xb.data(), S.n);
     for (int t = 0; t < T; ++t) print_subset(na, nb, S.n, &sub[(size_t)t * 8], 8, 0, mean_focal2(S.cam_a, S.cam_b), thr * thr);
     return 0;
   }
@@ -132,7 +132,7 @@ int main(int argc, char** argv) {
     std::vector<float> xa((size_t)n * 2), xb((size_t)n * 2); std::vector<int32_t> sub((size_t)T * m);
     if (std::fread(xa.data(), 4, xa.size(), f) != xa.size() || std::fread(xb.data(), 4, xb.size(), f) != xb.size() || std::fread(sub.data(), 4, sub.size(), f) != sub.size()) return 2;
     for (int32_t s : sub) if (s < 0 || s >= n) return 2;
-    const std::vector<double> na = pnp_detail::normalised_points(cam_a, xa.data(), n), nb = pnp_detail::normalised_points(cam_b, xb.data(), n);
+    const std::vector<double> na = hyp_detail::normalised_points(cam_a, xa.data(), n), nb = hyp_detail::normalised_points(cam_b, xb.data(), n);
     for (int t = 0; t < T; ++t) print_subset(na, nb, n, &sub[(size_t)t * m], m, mode, mean_focal2(cam_a, cam_b), thr * thr);
   }
   std::fclose(f);

@@ -355,16 +355,6 @@ def write_scene_file(path, scene):
         f.write(scene["xy_a"].astype("<f4").tobytes()); f.write(scene["xy_b"].astype("<f4").tobytes())
 
 
-def build_host(directory, extra_flags=()):
-    """compiles tests/two_view_host.cpp (host code only: nothing of the library is linked) -> the program's path"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(str(directory), "two_view_host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", *extra_flags, "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "two_view_host.cpp"), "-o", exe], check=True)
-    return exe
-
-
 def _rows(text):
     return [[float(x) for x in line.split()] for line in text.strip().split("\n")]
 

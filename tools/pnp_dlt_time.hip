@@ -31,7 +31,7 @@ int main() {
     double host_ms = 1e30;
     for (int rep = 0; rep < 5; ++rep) {
       const auto t0 = std::chrono::steady_clock::now();
-      const std::vector<double> nrm = rsba_amd::pnp_detail::normalised_points(sc.cam, sc.xy.data(), n);
+      const std::vector<double> nrm = rsba_amd::hyp_detail::normalised_points(sc.cam, sc.xy.data(), n);
       for (int t = 0; t < T; ++t) hs[(size_t)t] = rsba_amd::pnp_detail::dlt_pose(sc.X.data(), nrm.data(), &subs[(size_t)t * m], m, &hp[(size_t)t * 6]);
       host_ms = std::fmin(host_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }

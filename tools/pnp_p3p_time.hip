@@ -27,7 +27,7 @@ int main() {
   CHECK(hipMemcpy(d_op, sc.X.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice)); CHECK(hipMemcpy(d_ip, sc.xy.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
   D.n = n; D.object_points = d_op; D.image_points = d_ip; D.normalised = d_nrm;
   CHECK(rsba::launch_pnp_normalise(D, nullptr));
-  const std::vector<double> nrm = rsba_amd::pnp_detail::normalised_points(sc.cam, sc.xy.data(), n);
+  const std::vector<double> nrm = rsba_amd::hyp_detail::normalised_points(sc.cam, sc.xy.data(), n);
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   const int reps = 20;

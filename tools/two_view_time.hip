@@ -44,7 +44,7 @@ int main() {
       const double X[3] = {-4 + 8 * uni(), -3 + 6 * uni(), 6 + 6 * uni()};
       const double d[3] = {X[0] - pose_b[3], X[1] - pose_b[4], X[2] - pose_b[5]};
       double q[3];
-      rsba_amd::pnp_detail::rotate(pose_b, d, q);
+      rsba_amd::hyp_detail::rotate(pose_b, d, q);
       xa[2 * (size_t)i] = (float)(800 * X[0] / X[2] + 640 + uni() - 0.5); xa[2 * (size_t)i + 1] = (float)(800 * X[1] / X[2] + 360 + uni() - 0.5);
       xb[2 * (size_t)i] = (float)(800 * q[0] / q[2] + 640 + uni() - 0.5); xb[2 * (size_t)i + 1] = (float)(800 * q[1] / q[2] + 360 + uni() - 0.5);
     }
@@ -60,9 +60,9 @@ int main() {
       CHECK(rsba::launch_pnp_normalise(D, nullptr));
       CHECK(hipDeviceSynchronize()); CHECK(hipFree(d_xy));
     }
-    const std::vector<double> na = rsba_amd::pnp_detail::normalised_points(cam, xa.data(), n), nb = rsba_amd::pnp_detail::normalised_points(cam, xb.data(), n);
+    const std::vector<double> na = rsba_amd::hyp_detail::normalised_points(cam, xa.data(), n), nb = rsba_amd::hyp_detail::normalised_points(cam, xb.data(), n);
     for (int T : {1024, 16384}) {
-      const std::vector<int32_t> sub = rsba_amd::pnp_detail::distinct_subsets(n, 8, T, 0x9e3779b97f4a7c15ULL);
+      const std::vector<int32_t> sub = rsba_amd::hyp_detail::distinct_subsets(n, 8, T, 0x9e3779b97f4a7c15ULL);
       int32_t* d_sub; double *d_E, *d_poses; uint8_t *d_st, *d_st2; int32_t *d_inl, *d_front;
       CHECK(hipMalloc(&d_sub, sizeof(int32_t) * sub.size())); CHECK(hipMalloc(&d_E, sizeof(double) * 9 * T)); CHECK(hipMalloc(&d_poses, sizeof(double) * 6 * T));
       CHECK(hipMalloc(&d_st, T)); CHECK(hipMalloc(&d_st2, T)); CHECK(hipMalloc(&d_inl, sizeof(int32_t) * T)); CHECK(hipMalloc(&d_front, sizeof(int32_t) * 4 * T));
@@ -108,7 +108,7 @@ int main() {
       CHECK(hipFree(d_sub)); CHECK(hipFree(d_E)); CHECK(hipFree(d_poses)); CHECK(hipFree(d_st)); CHECK(hipFree(d_st2)); CHECK(hipFree(d_inl)); CHECK(hipFree(d_front));
     }
     for (int T : {1024, 16384}) {   // ---- the five-point chain ----
-      const std::vector<int32_t> sub = rsba_amd::pnp_detail::distinct_subsets(n, 5, T, 0x9e3779b97f4a7c15ULL);
+      const std::vector<int32_t> sub = rsba_amd::hyp_detail::distinct_subsets(n, 5, T, 0x9e3779b97f4a7c15ULL);
       const size_t slots = (size_t)T * 10;
       int32_t* d_sub; double *d_E, *d_poses, *d_E1, *d_p1; uint8_t *d_st, *d_slot, *d_st2, *d_st3; int32_t *d_cnt, *d_inl, *d_front, *d_inl1, *d_front1;
       CHECK(hipMalloc(&d_sub, sizeof(int32_t) * sub.size())); CHECK(hipMalloc(&d_E, sizeof(double) * 9 * slots)); CHECK(hipMalloc(&d_poses, sizeof(double) * 6 * slots));
