@@ -7,10 +7,15 @@
 // potrf + blocked triangular inverse of round 1, round 2's second wave).
 // Checks |W D W^T - I| and |W - W_ref| against a host factorisation, prints microseconds per tile (wall_clock64, 100 MHz).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics tools/tile_factor_bench.hip -o tools/tile_factor_bench
+// tile_factor_bench --check IN OUT times nothing: it runs the two forms the library runs (plain, and publishing W as diag_factor does) on
+// every tile of a file, one workgroup per tile in ONE launch, and writes ok and W of each back (check_kernel and run_check below;
+// tests/test_gpu_tile_factor.py holds them against the extended-precision reference of tests/tile_factor_reference.py).
 #include "tile_factor_baselines.hpp"
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace rsba {
@@ -47,6 +52,30 @@ __global__ __launch_bounds__(256, 2) void tile_kernel(const double* __restrict__
   if (tid == 0) ticks[0] = total;
 }
 
+
+// --check: workgroup b factors tile b twice, as the library does and with nothing of tools/tile_factor_baselines.hpp —
+//   form 0  factor_invert_tile<false, false>: W stays in LDS;
+//   form 1  factor_invert_tile<false, true> with wout, as diag_factor (chol_tasks.hpp) calls it: W also leaves by row blocks to Wout + 2 T T.
+// Per tile Wout holds three T x T copies: W of form 0 and of form 1 read out of LDS, and what form 1 published (the host filled it with
+// the empty pattern).  The LDS copies are read the way publish_rows reads them — the 16-blocks on and below the diagonal; the blocks above
+// it are not the function's to write — from a W buffer that held the empty pattern in every cell before the call.  ok is tid 0's (wave 0's), as in diag_factor.
+__global__ __launch_bounds__(256, 2) void check_kernel(const double* __restrict__ Din, double* __restrict__ Wout, int* __restrict__ okout) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int tid = threadIdx.x;
+  double* D = smem; double* Wl = smem + kBuf; double* Tm = smem + 2 * kBuf; double* Lp = smem + 3 * kBuf;
+  const double* Dt = Din + (size_t)blockIdx.x * (T * T);
+  double* Wt = Wout + (size_t)blockIdx.x * (3 * T * T);
+  for (int form = 0; form < 2; ++form) {
+    for (int e = tid; e < T * T; e += 256) { const int r = e / T, c = e % T; D[r * TP + c] = (c <= r) ? Dt[e] : 0.0; }
+    for (int e = tid; e < kBuf; e += 256) Wl[e] = __longlong_as_double(-1ll);
+    arm_pivot_messages(smem, tid);
+    __syncthreads();
+    const bool ok = form == 0 ? factor_invert_tile<false, false>(D, Wl, Tm, Lp, tid) : factor_invert_tile<false, true>(D, Wl, Tm, Lp, tid, nullptr, Wt + 2 * T * T);
+    if (tid == 0) okout[2 * blockIdx.x + form] = ok ? 1 : 0;
+    for (int e = tid; e < T * T; e += 256) { const int r = e / T, c = e % T; Wt[form * T * T + e] = (c < 16 * (r / 16 + 1)) ? Wl[r * TP + c] : 0.0; }
+    __syncthreads();
+  }
+}
 
 // the two waves of one 16 x 16 diagonal block step on their own: MODE 0 both, 1 the eliminating wave alone, 2 the following wave alone
 // on messages that are already there.  FW = which wave of the workgroup follows.
@@ -125,8 +154,49 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* __restrict__ Di
 }  // namespace
 }  // namespace rsba
 
-int main() {
+// IN: int32 n, then n tiles of T x T doubles (row-major, symmetric; the lower triangle is read).  OUT: int32 n, then per tile
+// { int32 ok of form 0, int32 ok of form 1, W of form 0, W of form 1, the published copy of form 1 } — T x T doubles each, as they lie in HBM.
+#define CHECK_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) { std::fprintf(stderr, "tile_factor_bench --check: %s: %s\n", #call, hipGetErrorString(e_)); return 1; } } while (0)
+static int run_check(const char* in_path, const char* out_path) {
   using namespace rsba;
+  constexpr size_t tile = (size_t)T * T;
+  std::FILE* f = std::fopen(in_path, "rb");
+  if (!f) { std::fprintf(stderr, "tile_factor_bench --check: cannot open %s\n", in_path); return 1; }
+  int32_t n = 0;
+  if (std::fread(&n, sizeof n, 1, f) != 1 || n < 1 || n > 4096) { std::fprintf(stderr, "tile_factor_bench --check: %s: bad tile count\n", in_path); std::fclose(f); return 1; }
+  std::vector<double> A(n * tile);
+  const bool whole = std::fread(A.data(), sizeof(double), A.size(), f) == A.size() && std::fgetc(f) == EOF;
+  std::fclose(f);
+  if (!whole) { std::fprintf(stderr, "tile_factor_bench --check: %s does not hold exactly %d tiles\n", in_path, (int)n); return 1; }
+  double *dA = nullptr, *dW = nullptr; int* dOk = nullptr;
+  CHECK_HIP(hipMalloc(&dA, n * tile * sizeof(double)));
+  CHECK_HIP(hipMalloc(&dW, 3 * n * tile * sizeof(double)));
+  CHECK_HIP(hipMalloc(&dOk, 2 * n * sizeof(int)));
+  CHECK_HIP(hipMemcpy(dA, A.data(), n * tile * sizeof(double), hipMemcpyHostToDevice));
+  CHECK_HIP(hipMemset(dW, 0xFF, 3 * n * tile * sizeof(double)));   // the empty pattern of chol_cells.hpp: a cell nobody wrote shows afterwards
+  CHECK_HIP(hipMemset(dOk, 0xFF, 2 * n * sizeof(int)));
+  const size_t lds = kCholLds * sizeof(double);
+  CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(check_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(check_kernel, dim3(n), dim3(256), lds, 0, dA, dW, dOk);
+  CHECK_HIP(hipGetLastError());
+  CHECK_HIP(hipDeviceSynchronize());
+  std::vector<double> W(3 * n * tile); std::vector<int32_t> ok(2 * n);
+  CHECK_HIP(hipMemcpy(W.data(), dW, W.size() * sizeof(double), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(ok.data(), dOk, ok.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipFree(dA)); CHECK_HIP(hipFree(dW)); CHECK_HIP(hipFree(dOk));
+  f = std::fopen(out_path, "wb");
+  if (!f) { std::fprintf(stderr, "tile_factor_bench --check: cannot write %s\n", out_path); return 1; }
+  bool written = std::fwrite(&n, sizeof n, 1, f) == 1;
+  for (int b = 0; b < n && written; ++b) written = std::fwrite(&ok[2 * b], sizeof(int32_t), 2, f) == 2 && std::fwrite(&W[3 * b * tile], sizeof(double), 3 * tile, f) == 3 * tile;
+  written = (std::fclose(f) == 0) && written;
+  if (!written) { std::fprintf(stderr, "tile_factor_bench --check: short write to %s\n", out_path); return 1; }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  using namespace rsba;
+  if (argc == 4 && std::strcmp(argv[1], "--check") == 0) return run_check(argv[2], argv[3]);
+  if (argc != 1) { std::fprintf(stderr, "usage: tile_factor_bench [--check IN OUT]\n"); return 2; }
   constexpr int n = T;
   // SPD tile with the conditioning of a damped reduced camera block: A = B B^T + 0.1 I
   std::vector<double> B(n * n), A(n * n, 0.0), L(n * n, 0.0), Wref(n * n, 0.0);
