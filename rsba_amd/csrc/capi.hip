@@ -15,6 +15,7 @@
 
 #include "capi_util.hpp"
 #include "devmem.hpp"
+#include "switches.hpp"
 
 using namespace rsba;
 
@@ -146,7 +147,7 @@ int32_t rsba_create(const rsba_problem_desc* d, int32_t device, rsba_handle** ou
     return fail(RSBA_ERR_INVALID_ARGUMENT, "scanlines[0] == scanlines[1]");
   if (d->num_intrinsics > 1 && !d->frame_intrinsics) return fail(RSBA_ERR_INVALID_ARGUMENT, "frame_intrinsics required when num_intrinsics > 1");
   const int64_t N = d->num_observations;
-  const bool dbg = std::getenv("RSBA_DEBUG_PLAN") != nullptr;
+  const bool dbg = rsba::debug_plan();
   auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_mark = dbg ? now_ms() : 0.0; char stages[256] = ""; int stages_n = 0;
   auto stage = [&](const char* name) { if (!dbg) return; const double t = now_ms(); stages_n += std::snprintf(stages + stages_n, sizeof stages - stages_n, " %s %.2f;", name, t - t_mark); t_mark = t; };
@@ -279,7 +280,7 @@ int32_t rsba_create(const rsba_problem_desc* d, int32_t device, rsba_handle** ou
 void rsba_destroy(rsba_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  const bool dbg = std::getenv("RSBA_DEBUG_PLAN") != nullptr;
+  const bool dbg = rsba::debug_plan();
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = dbg ? now() : 0.0;
   rsba_destroy_solver(h);

@@ -1,4 +1,5 @@
 #include "devmem.hpp"
+#include "switches.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -43,9 +44,7 @@ size_t round_size(size_t bytes) {
 void read_cap(Cache& c) {   // (under the lock)
   if (c.cap_read) return;
   c.cap_read = true;
-  size_t mb = 2048;
-  if (const char* e = std::getenv("RSBA_DEVICE_CACHE_MB")) mb = (size_t)std::strtoull(e, nullptr, 10);
-  c.cap_bytes = mb << 20;
+  c.cap_bytes = (size_t)device_cache_mb() << 20;
 }
 // hipFree every cached block of every device (the pools of streams, events and pinned blocks are not touched)
 void release_blocks(Cache& c) {

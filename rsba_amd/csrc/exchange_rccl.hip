@@ -35,6 +35,7 @@ const char* ncclGetErrorString(ncclResult_t result);
 #include <string>
 
 #include "handle.hpp"
+#include "switches.hpp"
 
 namespace {
 
@@ -56,8 +57,8 @@ Rccl& rccl() {
   static std::once_flag once;
   std::call_once(once, [] {
     void* lib = nullptr;
-    if (const char* path = std::getenv("RSBA_RCCL_LIB")) {
-      lib = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (const auto path = rsba::rccl_lib_path()) {
+      lib = dlopen(path->c_str(), RTLD_NOW | RTLD_LOCAL);
       if (!lib) { r.error = std::string("RSBA_RCCL_LIB: ") + dlerror(); return; }
     } else if (dlsym(RTLD_DEFAULT, "ncclAllReduce")) {
       lib = RTLD_DEFAULT;   // the process already carries an RCCL in its global scope

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void point_blocks_kernel(const DeviceProblem d
 // (mostly) whole 128-B lines.
 constexpr int kProjectChunks = 2;   // consecutive 64-slot chunks per wave of the projection kernel at most (one when the scene is small: project_chunks).  Round 6: 8 until then — swept again on the slim (all-factored, three workgroups per CU) form: C4 project phase 0.096 / 0.096 / 0.101 / 0.112 / 0.113 / 0.150 ms for 1 / 2 / 4 / 8 / 16 / 32
 inline int project_chunks(int64_t N) {   // ~2 k waves or more
-  static const int forced = [] { const char* e = std::getenv("RSBA_PROJECT_CHUNKS"); const int v = e ? std::atoi(e) : 0; return v >= 1 && v <= 64 ? v : 0; }();   // (tuning aid)
+  static const int forced = project_chunks_override();   // (tuning aid: switches.hpp)
   const int64_t c = N / 64 / 2048;
   return forced ? forced : (int)(c < 1 ? 1 : c > kProjectChunks ? kProjectChunks : c);
 }

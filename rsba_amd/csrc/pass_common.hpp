@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "solver_state.hpp"
+#include "switches.hpp"
 
 namespace rsba {
 
@@ -64,7 +65,7 @@ constexpr int kSweepPoints = 16;
 // so what a pass takes is what ONE wave takes — its points' slots, 64 at a time — and a wave with four points is done in a third of
 // the time of a wave with sixteen.  sweep_points(M): 16 from 32 k points, 8 from 16 k, 4 below.
 inline int sweep_points(int64_t M) {
-  static const int forced = [] { const char* e = std::getenv("RSBA_SWEEP_POINTS"); const int v = e ? std::atoi(e) : 0; return v >= 1 && v <= kSweepPoints ? v : 0; }();   // (tuning aid)
+  static const int forced = sweep_points_override(kSweepPoints);   // (tuning aid: switches.hpp)
   return forced ? forced : M >= 32768 ? 16 : M >= 16384 ? 8 : 4;
 }
 // workgroups of the back-substitution (kernels_point.hip), whose partials the model cost change sums (kernels_lm.hip)

@@ -367,7 +367,7 @@ hipError_t device_plan_lists(const DevicePlanIn& in, DevicePlanOut* out) {
   const int M = in.M, nt = in.nt;
   const int64_t N = in.N;
   Geo g{in.FR, in.NPF, in.FT, nt, M, in.NIB == 1 ? 1 : 0, N};
-  const bool dbg = std::getenv("RSBA_DEBUG_PLAN") != nullptr;
+  const bool dbg = in.debug;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_last = now(); char stages[256] = ""; int stages_n = 0;
   auto stage = [&](const char* name) { if (!dbg) return; (void)hipStreamSynchronize(st); const double t = now(); stages_n += std::snprintf(stages + stages_n, sizeof stages - stages_n, " %s %.2f;", name, t - t_last); t_last = t; };

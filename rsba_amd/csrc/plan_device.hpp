@@ -19,6 +19,7 @@ struct DevicePlanIn {
   int64_t num_struct_keys;
   int64_t chunk_block;           // > 0: the chunk numbering by blocks of so many points wants the SEGMENTS of the entry list — maximal runs of one tile pair inside one block
   bool want_slot_frame_host;
+  bool debug;                    // the stages' times on stderr (the plan's RSBA_DEBUG_PLAN)
   hipStream_t stream;
 };
 

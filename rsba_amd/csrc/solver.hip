@@ -139,7 +139,7 @@ int32_t reduce_system(rsba_handle* h, double radius) {
     PhaseScope ps(h, RSBA_PHASE_PROJECT);
     // A shared intrinsics block at scale (4k cameras: projection 1.03 ms of stores, virtual-record sweep 0.57 ms of fp64): the two passes
     // read the same point factors and write different records — side by side, the sweep on the arming stream (idle here), two events.
-    const bool beside = sv.NPF > 0 && sv.nvgroups > 0 && s->mstream && s->ev_fork && h->dp.N >= 2000000 && !std::getenv("RSBA_NO_SIDE_SWEEP") && !project_covers_virtual_records(h->dp, sv);   // (round 5: one fused sweep does both where it applies)
+    const bool beside = sv.NPF > 0 && sv.nvgroups > 0 && s->mstream && s->ev_fork && h->dp.N >= 2000000 && !s->solve_sw.no_side_sweep && !project_covers_virtual_records(h->dp, sv);   // (round 5: one fused sweep does both where it applies)
     if (beside) {
       RSBA_HIP_TRY(hipEventRecord(s->ev_fork, st));
       RSBA_HIP_TRY(hipStreamWaitEvent(s->mstream, s->ev_fork, 0));
@@ -228,7 +228,7 @@ int32_t solve_reduced_system(rsba_handle* h, bool rhs_stays) {
     } else
     RSBA_HIP_TRY(launch_chol_dag(sv, s->plan, s->d_dag_args, s->dag_workgroups, s->dag_one_per_cu, st));
     if (s->test_corrupt_once) { s->test_corrupt_once = false; RSBA_HIP_TRY(hipMemsetAsync(sv.yv + (sv.n / 2 / 6) * 6 + 1, 0, sizeof(double), st)); }   // test hook: one entry of the solution (a pose coordinate in mid-video) lost
-    if (s->verify_dag) {
+    if (s->sw.chol_verify) {
       // (rhs_stays: nobody writes sv.rhs before the check has been waited for — the LM iteration without a free ratio; otherwise the check gets a copy)
       const double* b_rhs = sv.rhs;
       if (s->hp.two_rhs) { RSBA_HIP_TRY(launch_border_combine(s->verify_b, sv.rhs, s->border, 0.0, sv.npad, st, s->ratio4 + kRtC)); b_rhs = s->verify_b; }   // what was solved for: g - (s eta) b
@@ -270,7 +270,7 @@ int32_t solve_again(rsba_handle* h, const double* b2, const double** v_out) {
     for (int l = s->hp.nlev - 1; l >= 0; --l) RSBA_HIP_TRY(launch_chol_solve_level(sv, s->plan, true, s->hp.lev_diag_ptr[l], s->hp.lev_diag_ptr[l + 1] - s->hp.lev_diag_ptr[l], b2, s->zy2, st));
   }
   *v_out = s->zy2 + sv.npad;
-  if (!s->use_levels && s->verify_dag) {
+  if (!s->use_levels && s->sw.chol_verify) {
     if (int32_t rc = await_verification(h)) return rc;   // (the accumulators of the check are shared)
     SolverDev sv2 = sv;
     sv2.yv = s->zy2 + sv.npad;
@@ -602,11 +602,10 @@ int32_t LmRun::finish(int32_t term) {
   if (s->xtimer.on) { s->xtimer.resolve(); s->xtimer.on = false; }
   h->prior_ratio_result = dp.prior_ratio;
   sum->total_time_s = now_s() - t_start;
-  if (const char* path = h->solver->d_trace ? std::getenv("RSBA_CHOL_TRACE") : nullptr) {   // debugging aid, off by default
-    Solver* sl = h->solver;
+  if (Solver* sl = h->solver; sl->d_trace && sl->sw.chol_trace) {   // debugging aid, off by default
     std::vector<long long> tr(8 * (size_t)sl->plan.ntasks);
     RSBA_HIP_TRY(hipMemcpy(tr.data(), sl->d_trace, tr.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    if (FILE* f = std::fopen(path, "wb")) {
+    if (FILE* f = std::fopen(sl->sw.chol_trace->c_str(), "wb")) {
       const int32_t n = sl->plan.ntasks;
       std::fwrite(&n, sizeof(n), 1, f);
       std::fwrite(sl->hp.tasks.data(), sizeof(int32_t), sl->hp.tasks.size(), f);
@@ -635,7 +634,7 @@ int32_t LmRun::exchange_problem_size() {
   int32_t rc;
   const double npri = sv.lead ? (double)h->prior_frames.size() + (double)h->pp_blocks.size() + (dp.pp_spherical >= 0 ? 1.0 : 0.0) : 0.0;
   // (+ how many ranks cannot run the loop without the host — no observations, or phase timers on: every rank must take the same form of the loop)
-  const bool host_form_only = dp.N == 0 || s->timer.on || s->pcg.on || test_hook("RSBA_DEVICE_LM_OFF_ON_THIS_RANK") != nullptr;   // (the iterative linear solver reads its convergence flag on the host)
+  const bool host_form_only = dp.N == 0 || s->timer.on || s->pcg.on || s->solve_sw.test_device_lm_off_on_this_rank;   // (the iterative linear solver reads its convergence flag on the host)
   double cnt[4] = {(double)dp.N + npri, (double)(s->num_reduced_blocks + s->num_priors_reduced), (double)s->num_reduced_params, host_form_only ? 1.0 : 0.0};
   if (h->allreduce) {
     RSBA_HIP_TRY(hipMemcpyAsync(sv.scalars + 8, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
@@ -677,8 +676,7 @@ int32_t LmRun::initial_evaluation() {
   // A candidate is evaluated in LM mode straight away (residuals, Jacobian, per-wave camera blocks) when the problem keeps no
   // records (they would be overwritten and a rejected step needs the old ones): an accepted step — the rule — then re-uses that
   // evaluation for its linearisation instead of evaluating twice, a rejected one has computed Jacobians for nothing.
-  speculate = dp.rec == nullptr || dp.rec_alt != nullptr;   // (records: only with a second set for the candidate's)
-  if (const char* e = std::getenv("RSBA_SPECULATE")) speculate = speculate && e[0] != '0';
+  speculate = (dp.rec == nullptr || dp.rec_alt != nullptr) && s->solve_sw.speculate;   // (records: only with a second set for the candidate's)
   return RSBA_OK;
 }
 
@@ -694,9 +692,7 @@ int32_t LmRun::initial_evaluation() {
 // candidates' records go to a second set), GoodPosePrior blocks on several ranks.  What goes through the host form: phase timing, a rank that
 // asks for it (no observations), RSBA_DEVICE_LM=0 / RSBA_RECORDS_ALT=0, and a suspect factorisation (the level schedule repeats the iteration).
 bool LmRun::choose_device_loop() {
-  bool device_ctl = speculate && !s->use_levels &&
-                    !any_rank_needs_host && opt->max_num_iterations > 0;
-  if (const char* e = std::getenv("RSBA_DEVICE_LM")) device_ctl = device_ctl && e[0] != '0';   // A/B switch: 0 = the host decides
+  const bool device_ctl = speculate && !s->use_levels && !any_rank_needs_host && opt->max_num_iterations > 0 && s->solve_sw.device_lm;   // (the switch: A/B, 0 = the host decides)
   if (device_ctl) ++s->stats.device_loop_solves; else ++s->stats.host_loop_solves;
   return device_ctl;
 }
@@ -797,8 +793,7 @@ int32_t LmRun::run_device_loop() {
   // enqueued beyond the one whose outcome the host has seen (those behind a termination fall through: every kernel looks at the
   // status word); measured at 100 and 1 000 cameras the queue does not need it — 0.492 / 0.498 / 0.500 ms per iteration for
   // k = 0 / 1 / 2 (profiles/r04/iteration_gaps.txt) — so the default enqueues nothing that might not be wanted.
-  int ahead = 0;
-  if (const char* e = std::getenv("RSBA_LM_AHEAD")) ahead = std::min(Solver::kCtlRing - 2, std::max(0, std::atoi(e)));   // (a slot is written again only after the host has moved on from it)
+  const int ahead = s->solve_sw.lm_ahead;
   const double* hc = hc0;
   int enqueued = 0, looked = 0;
   bool stopped = false;
@@ -970,6 +965,7 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
   int32_t rc = build_solver(h);
   if (rc) return rc;
   Solver* s = h->solver;
+  s->solve_sw = SolveSwitches::read(Solver::kCtlRing);   // (once per solve: the loop and its steps read the fields)
   s->cov.valid = false;   // (rsba_covariance_compute: the parameters move)
   LmRun run(h, opt, sum, trace, trace_cap, t_start);
   if ((rc = run.refuse_unsupported_pcg())) return rc;
@@ -982,7 +978,7 @@ extern "C" int32_t rsba_solve(rsba_handle* h, const rsba_solver_options* opt, rs
     PhaseTimer& t; PhaseTimer& x;
     ~TimerGuard() { for (PhaseTimer* q : {&t, &x}) if (q->on) { q->on = false; q->pending.clear(); q->next = 0; } }
   } timer_guard{s->timer, s->xtimer};
-  { const char* lv = std::getenv("RSBA_CHOL_LEVELS"); s->use_levels = opt->level_scheduled_cholesky != 0 || (lv && lv[0] == '1'); }
+  s->use_levels = opt->level_scheduled_cholesky != 0 || s->solve_sw.chol_levels;
   if ((rc = run.exchange_problem_size())) return rc;
   if ((rc = run.initial_evaluation()) || run.done) return rc;
   if (run.choose_device_loop()) { if ((rc = run.run_device_loop()) || run.done) return rc; }

@@ -13,6 +13,7 @@
 #include "solver_state.hpp"
 #include "chol_plan.hpp"
 #include "pcg.hpp"
+#include "switches.hpp"
 
 namespace rsba {
 
@@ -58,6 +59,8 @@ constexpr size_t kNumPlanLists = sizeof kPlanLists / sizeof kPlanLists[0];
 struct Solver {
   PhaseTimer timer;
   PhaseTimer xtimer;   // the same for the collectives of a sharded solve, by kind (RSBA_EXCHANGE_*)
+  PlanSwitches sw;          // the environment as the plan saw it (switches.hpp): what the handle decided then stays decided
+  SolveSwitches solve_sw;   // ... and as the last rsba_solve saw it (before the first one: as the plan did)
   rsba_plan_stats stats{};
   SolverDev sv{};
   std::vector<void*> allocs;
@@ -71,15 +74,14 @@ struct Solver {
   // The verification runs on a stream of its own, beside the back-substitution / candidate / trial evaluation of the iteration: it
   // only has to be done when the step scalars are packed.  verify_b = the right-hand side of the solve (sv.rhs is overwritten by the step).
   hipStream_t vstream = nullptr; hipEvent_t ev_solved = nullptr, ev_verified = nullptr; double* verify_b = nullptr; bool verify_pending = false;
-  bool verify_dag = true;                                             // RSBA_CHOL_VERIFY=0 switches the check off
   bool test_corrupt_once = false;                                     // RSBA_CHOL_TEST_CORRUPT=1 (tests): the first DAG solve loses one entry of y
   int dag_fallbacks = 0;                                              // solves repeated on the level schedule after a failed check                                      // device copy of {sv, plan} for the persistent kernel
   unsigned int* d_dag_sync = nullptr;                                 // [ticket, pad x3]
-  long long* d_trace = nullptr;                                       // RSBA_CHOL_TRACE=<file>: task time stamps of the last factorisation
+  long long* d_trace = nullptr;                                       // sw.chol_trace: task time stamps of the last factorisation
   CholPlan plan{};
   int dag_workgroups = 0;
   bool dag_one_per_cu = true;                                         // LDS request above half a CU's: two persistent workgroups never share a CU (RSBA_CHOL_WGS above the CU count lifts it)
-  bool use_levels = false;                                            // RSBA_CHOL_LEVELS=1: one launch per (level, kind)
+  bool use_levels = false;                                            // one launch per (level, kind): sw.chol_levels_before_solve, then every solve's solve_sw.chol_levels | its option; a suspect solve sets it
   uint8_t* d_row_sep = nullptr;                                       // [nt] tile columns (old index) in the separators
   int32_t* d_obs_slot = nullptr;
   double *d_gpose = nullptr, *d_gpoint = nullptr;

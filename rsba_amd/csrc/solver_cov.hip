@@ -99,7 +99,7 @@ void rsba_covariance_invalidate(rsba_handle* h) { if (h && h->solver) h->solver-
 
 namespace {
 // RSBA_COV_TIMES=1: HIP events around the covariance kernels (rsba_covariance_times; tools/cov_time.py).  Off, no event is created.
-bool cov_times_on() { static const bool on = [] { const char* e = std::getenv("RSBA_COV_TIMES"); return e && e[0] == '1'; }(); return on; }
+bool cov_times_on() { static const bool on = cov_times_switch(); return on; }
 // one kernel between two events, where the times are asked for
 struct CovStopwatch {
   hipEvent_t t0 = nullptr, t1 = nullptr; bool on = cov_times_on();

@@ -21,7 +21,6 @@
 #include "solver.hpp"
 #include "tile_order.hpp"
 #include "plan_device.hpp"
-#include "test_hooks.hpp"
 
 using namespace rsba;
 
@@ -135,8 +134,9 @@ struct PlanBuild {
     if (!local_fail) { local_fail = code; local_why = why; }
     return RSBA_OK;
   }
+  const PlanSwitches& sw;   // the environment, read once (build_solver_impl)
   // RSBA_DEBUG_PLAN: host time of every stage
-  const bool dbg_plan = std::getenv("RSBA_DEBUG_PLAN") != nullptr;
+  const bool dbg_plan = sw.debug_plan;
   std::string phases; double t_phase = now_s();
   void tick(const char* name) {
     if (!dbg_plan) return;
@@ -158,7 +158,7 @@ struct PlanBuild {
   std::vector<int64_t>& pt_goff;   // doubles of the groups of the points before j
   std::vector<int32_t>& ent_pt;   // (host passes only; the device plan hands the chunk numbering the entry list's segments instead)
   std::vector<std::vector<int32_t>>& thread_cnt;
-  // the switches (settle_switches)
+  // what the switches come to on this problem (settle_switches)
   int plan_threads = 1; bool recompute = false, factored = false, dev_plan = false;
   std::vector<uint8_t> tile_factored;
   // the lists of slots, groups, tile pairs and entries (lists_on_host / lists_on_device)
@@ -192,7 +192,7 @@ struct PlanBuild {
       : h(h_), s(s_), dp(h_->dp), sv(s_->sv), hp(s_->hp), pl(s_->plan), lay(h_->dp.P, h_->dp.F, h_->dp.calibrated != 0, h_->dp.NI),
         FR(lay.FR), M(h_->dp.M), CD(lay.CD), NIB(lay.NIB), NPF(lay.NPF), F(lay.F), FT(lay.FT), nt(lay.nt), N(h_->dp.N),
         fi(h_->frame_intr), of(h_->obs_frame), op(h_->obs_point), lead(h_->rank == 0),
-        plan_votes(h_->allreduce && h_->world > 1 && !h_->union_mask.empty()),
+        plan_votes(h_->allreduce && h_->world > 1 && !h_->union_mask.empty()), sw(s_->sw),
         scratch_lock(g_plan_scratch_mutex, std::try_to_lock), scr(pick_scratch(scratch_lock.owns_lock(), own_scratch)),
         point_ptr(scr.point_ptr), obs_slot(scr.obs_slot), real_frame(scr.real_frame), vgroup_ptr(scr.vgroup_ptr), vgroup_point(scr.vgroup_point),
         vgroup_intr(scr.vgroup_intr), slot_frame_host(scr.slot_frame), slot_point(scr.slot_point), pt_group(scr.pt_group), g_tile(scr.g_tile),
@@ -242,22 +242,19 @@ void PlanBuild::settle_switches() {
   // 3.4 ms on 1 / 2 / 4 / 8 threads (RSBA_PLAN_THREADS overrides: A/B)
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
   plan_threads = N >= 400000 ? (int)std::min(16u, hw) : N >= 50000 ? (int)std::min(4u, hw) : 1;
-  if (const char* e = std::getenv("RSBA_PLAN_THREADS")) plan_threads = std::max(1, std::min(64, std::atoi(e)));
+  plan_threads = sw.plan_threads.value_or(plan_threads);
   // Which frame tiles store their groups FACTORED (solver_state.hpp: kGroupFactored): two-pose frames of a problem whose point-side passes
   // recompute the records — the 12 camera-side rows of a frame are (1 - tau) q | tau q, so 6 rows and tau say it all —
   // except a tile that holds an intrinsics pseudo frame (its virtual records have no such structure).  RSBA_FACTORED=0: none (A/B).
-  recompute = dp.calibrated != 0 || NIB == 1;
-  if (const char* e = std::getenv("RSBA_RECORDS")) recompute = recompute && e[0] != '1';
-  factored = recompute && dp.P == 2;
-  if (const char* e = std::getenv("RSBA_FACTORED")) factored = factored && e[0] != '0';
+  recompute = (dp.calibrated != 0 || NIB == 1) && !sw.keep_records;
+  factored = recompute && dp.P == 2 && sw.factored;
   tile_factored.assign((size_t)nt, 0);
   for (int t = 0; t < nt && factored; ++t) tile_factored[t] = !((int64_t)(t + 1) * FT > FR && (int64_t)t * FT < F && F > FR);   // (no pseudo frame in [t FT, (t + 1) FT))
   // The passes over observations, points and entries run ON THE DEVICE (plan_device.hip: stable sorts and prefix sums — the lists come
   // out as from the host passes below, which stay as the path for what the device form leaves out: several intrinsics blocks (their
   // per-point block lists), more than 8 192 tile columns (a dense pair map), and RSBA_PLAN_DEVICE=0 for A/B runs and the test that
   // compares the two).  The host keeps the O(tiles) part: ordering, symbolic factorisation, task lists, chunk numbering.
-  dev_plan = N > 0 && NIB <= 1 && (int64_t)nt * nt <= ((int64_t)1 << 26) && N < ((int64_t)1 << 31);
-  if (const char* e = std::getenv("RSBA_PLAN_DEVICE")) dev_plan = dev_plan && e[0] != '0';
+  dev_plan = N > 0 && NIB <= 1 && (int64_t)nt * nt <= ((int64_t)1 << 26) && N < ((int64_t)1 << 31) && sw.plan_device;
   frame_ptr.assign((size_t)FR + 1, 0);
 }
 
@@ -267,7 +264,7 @@ void PlanBuild::start_uploads() {
 }
 
 int32_t PlanBuild::plan_test_hook() {   // (after the uploader has started)
-  return test_hook("RSBA_TEST_FAIL_PLAN") ? fail(RSBA_ERR_UNSUPPORTED, "RSBA_TEST_FAIL_PLAN: the plan was made to fail (test hook)") : RSBA_OK;
+  return kTestHooks && sw.test_fail_plan ? fail(RSBA_ERR_UNSUPPORTED, "RSBA_TEST_FAIL_PLAN: the plan was made to fail (test hook)") : RSBA_OK;
 }
 // (more than 2^32 doubles of groups: the offsets of the group pass wrap; the plan is given up right behind it)
 int32_t PlanBuild::check_group_doubles() {
@@ -459,7 +456,7 @@ void PlanBuild::for_each_entry(int j, Fn&& fn) {
 // host_entry_count: how many entries every tile pair has; host_entry_index: the pairs in (I, J) order and where their entries start;
 // host_entry_fill: the entries.
 void PlanBuild::host_entry_count() {
-  const bool small_keys = dense_keys && (int64_t)nt * nt <= ((int64_t)1 << 22) && !std::getenv("RSBA_PLAN_LISTED_KEYS");   // (the variable: the large-problem path at any size — its plan must be the same)
+  const bool small_keys = dense_keys && (int64_t)nt * nt <= ((int64_t)1 << 22) && !sw.listed_keys;   // (the variable: the large-problem path at any size — its plan must be the same)
   listed_keys = dense_keys && !small_keys && plan_threads > 1;
   nthreads = (small_keys || listed_keys) && M >= 4096 ? plan_threads : 1;   // (small_keys: per-thread counters of 4 nt^2 bytes)
   thread_cnt.resize(nthreads > 1 ? nthreads : 0);
@@ -624,12 +621,11 @@ int32_t PlanBuild::lists_on_device() {
   }
   bool any_const_point = false;
   for (int j = 0; j < M && !any_const_point; ++j) any_const_point = h->mask_point[(size_t)j * 3] == 0.0;
-  int64_t chunk_block = nt > 500 ? 2048 : 0;   // (the chunk numbering by blocks of points, below: it gets the entry list's segments instead of the list)
-  if (const char* e = std::getenv("RSBA_SCHUR_BLOCK")) chunk_block = std::atoi(e) > 0 ? std::max(16, std::atoi(e)) : 0;
+  int64_t chunk_block = sw.schur_block != PlanSwitches::kSchurBlockUnset ? sw.schur_block : nt > 500 ? 2048 : 0;   // (the chunk numbering by blocks of points, below: it gets the entry list's segments instead of the list)
   if (chunk_block >= M) chunk_block = 0;
-  DevicePlanIn din{dp.obs_frame, dp.obs_point, N, M, FR, NPF, NIB, FT, CD, nt, d_tf, struct_keys.data(), (int64_t)struct_keys.size(), chunk_block, any_const_point, h->stream};
+  DevicePlanIn din{dp.obs_frame, dp.obs_point, N, M, FR, NPF, NIB, FT, CD, nt, d_tf, struct_keys.data(), (int64_t)struct_keys.size(), chunk_block, any_const_point, sw.debug_plan, h->stream};
   hipError_t pe = local_fail ? hipSuccess : device_plan_lists(din, &dpo);
-  if (pe == hipSuccess && !local_fail && test_hook("RSBA_TEST_FAIL_DEVICE_PLAN")) pe = hipErrorOutOfMemory;   // (test hook: the lists' allocations fail on this rank)
+  if (pe == hipSuccess && !local_fail && kTestHooks && sw.test_fail_device_plan) pe = hipErrorOutOfMemory;   // (test hook: the lists' allocations fail on this rank)
   s->allocs.insert(s->allocs.end(), dpo.owned.begin(), dpo.owned.end());
   if (pe != hipSuccess) {
     (void)hipGetLastError();
@@ -679,8 +675,7 @@ void PlanBuild::order_and_symbolic() {
 // checks both), and the tile's replicated terms — damping, identity padding, the gradient after exchange (1) — follow frame_lead like
 // any frame tile's.
 int32_t PlanBuild::vote() {
-  sharded = plan_votes && tord.parts_ok;
-  if (const char* e = std::getenv("RSBA_SHARDED")) sharded = sharded && e[0] != '0';   // A/B switch
+  sharded = plan_votes && tord.parts_ok && sw.sharded;   // (the switch: A/B)
   if (plan_votes) {
     double bad = sharded ? 0.0 : 1.0;
     // an observation adds to its frame's tile and to the pseudo frames' tiles of the block its frame is seen through: every one of them
@@ -736,10 +731,9 @@ void PlanBuild::task_graph() {
   CholTaskInput tin;
   tin.order = &tord; tin.sharded = sharded; tin.rank = h->rank; tin.pair_I = &tp_I; tin.pair_J = &tp_J;
   tin.two_rhs = h->prior_free && !h->prior_frames.empty();   // a free interFrameRatio: its column of the normal equations rides through the factorisation
-  if (const char* e = std::getenv("RSBA_CHOL_FUSE")) tin.opt.fuse_last = e[0] != '0';
+  tin.opt.fuse_last = sw.chol_fuse;
   // (the defaults: swept on C4 / C5 after the look-ahead — fewer, longer UPDATE tasks and a short own share, 2.45 -> 2.36 ms per C4 iteration)
-  if (const char* e = std::getenv("RSBA_CHOL_TAIL")) tin.opt.tail = std::max(1, std::atoi(e));       // tuning aids
-  if (const char* e = std::getenv("RSBA_CHOL_CHUNK")) tin.opt.chunk = std::max(tin.opt.tail, std::atoi(e));
+  tin.opt.tail = sw.chol_tail; tin.opt.chunk = sw.chol_chunk;   // tuning aids
   chol_tasks(tin, &hp);
   two_rhs = hp.two_rhs;
   tick("tasks");
@@ -815,10 +809,10 @@ int32_t PlanBuild::schur_chunks() {
   {
     int64_t pair_major = 0;
     for (int t = 0; t < ntp; ++t) pair_major += (tp_ptr[t + 1] - tp_ptr[t] + kSchurChunk - 1) / kSchurChunk;
-    int64_t kBlock = nt > 500 ? 2048 : std::max<int64_t>(M, 1);
-    if (const char* e = std::getenv("RSBA_SCHUR_BLOCK")) kBlock = std::atoi(e) > 0 ? std::max(16, std::atoi(e)) : std::max<int64_t>(M, 1);   // tuning aid (0: tile pair by tile pair)
+    const bool by_size = sw.schur_block == PlanSwitches::kSchurBlockUnset;   // (RSBA_SCHUR_BLOCK: tuning aid, 0 = tile pair by tile pair)
+    const int64_t kBlock = by_size ? (nt > 500 ? 2048 : std::max<int64_t>(M, 1)) : sw.schur_block > 0 ? sw.schur_block : std::max<int64_t>(M, 1);
     number_chunks(kBlock);
-    if (kBlock < M && !std::getenv("RSBA_SCHUR_BLOCK") && (int64_t)chunk_tp.size() > pair_major + pair_major / 3) number_chunks(std::max<int64_t>(M, 1));
+    if (kBlock < M && by_size && (int64_t)chunk_tp.size() > pair_major + pair_major / 3) number_chunks(std::max<int64_t>(M, 1));
   }
   // A pair with very many chunks (the diagonal pair of the intrinsics pseudo tile has one per 512 points of the whole
   // problem) would be summed by a single workgroup of the merge kernel: its chunk list is pre-reduced in groups of
@@ -838,10 +832,10 @@ int32_t PlanBuild::schur_chunks() {
   tp_chunk0[ntp] = (int32_t)tp_chunk_list.size();
   sv.npremerge = (int)pm_ptr.size() - 1;
   sv.nchunk = (int)chunk_tp.size(); sv.ntp = ntp; sv.FT = FT;
-  { const char* e = std::getenv("RSBA_SCHUR_LINEAR"); sv.schur_linear = e && e[0] == '1'; }
-  { const char* e = std::getenv("RSBA_SCHUR_VARIANT"); sv.schur_variant = e ? std::atoi(e) : 0; if (!kTestHooks && sv.schur_variant >= 4) sv.schur_variant = 0; }   // (4 / 5: ablations, instrumented build only)
+  sv.schur_linear = sw.schur_linear;
+  sv.schur_variant = sw.schur_variant;   // (4 / 5: ablations, instrumented build only)
   sv.schur_trace = nullptr;
-  if (std::getenv("RSBA_SCHUR_TRACE")) { if (int32_t rc_ = s_alloc(s, &sv.schur_trace, 8 * (size_t)std::max(sv.nchunk, 1))) return rc_; }
+  if (sw.schur_trace) { if (int32_t rc_ = s_alloc(s, &sv.schur_trace, 8 * (size_t)std::max(sv.nchunk, 1))) return rc_; }
   return RSBA_OK;
 }
 
@@ -1065,10 +1059,9 @@ int32_t PlanBuild::allocations() {
     // ... and a second set for a candidate's records (device_state.hpp: rec_alt): with it the candidate is evaluated in LM mode like everybody
     // else's, and problems that keep records — several intrinsics blocks (per-frame f.cam, CeresHandler.h:260,277) — run the loop whose
     // decisions are taken on the device.  RSBA_RECORDS_ALT=0: one set, candidates residual-only, the host decides (round 5's form; A/B)
-    const char* e = std::getenv("RSBA_RECORDS_ALT");
-    if (!(e && e[0] == '0')) { if ((rc = s_alloc(s, &h->dp.rec_alt, (size_t)N * REC))) return rc; }
+    if (sw.records_alt) { if ((rc = s_alloc(s, &h->dp.rec_alt, (size_t)N * REC))) return rc; }
   }
-  sv.fused_sweep = sv.slot_xy && !h->dp.calibrated && sv.CD == 12 && sv.all_real_factored != 0 && sv.NPF > 0 && sv.nvgroups > 0 && sv.NIB == 1 && !std::getenv("RSBA_NO_FUSED_SWEEP");
+  sv.fused_sweep = sv.slot_xy && !h->dp.calibrated && sv.CD == 12 && sv.all_real_factored != 0 && sv.NPF > 0 && sv.nvgroups > 0 && sv.NIB == 1 && !sw.no_fused_sweep;
   if (N > 0) {
     // camera (and intrinsics border) blocks inside the evaluation kernel: per (64-observation wave, frame it touches)
     // the 16 x 16 blocks on and below the diagonal of [Ji | Jc | r]^T [Ji | Jc | r]
@@ -1179,8 +1172,8 @@ int32_t PlanBuild::allocations() {
   // A small plan (100 cameras: 267 tasks, ~15 per elimination level) is served better by a quarter as many workgroups as tasks — fewer
   // pollers around the chain: 0.428 -> 0.418 ms per iteration, three runs each — and leaves the rest of the chip to other streams.
   if (pl.ntasks <= 512) s->dag_workgroups = std::max(1, std::min(s->dag_workgroups, std::max(64, pl.ntasks / 4)));
-  if (const char* e = std::getenv("RSBA_CHOL_WGS")) { s->dag_workgroups = std::max(1, std::min(std::min(pl.ntasks, 2 * std::max(cus, 1)), std::atoi(e))); s->dag_one_per_cu = s->dag_workgroups <= cus; }
-  if (std::getenv("RSBA_CHOL_TRACE")) {
+  if (sw.chol_wgs) { s->dag_workgroups = std::max(1, std::min(std::min(pl.ntasks, 2 * std::max(cus, 1)), *sw.chol_wgs)); s->dag_one_per_cu = s->dag_workgroups <= cus; }
+  if (sw.chol_trace) {
     if ((rc = s_alloc(s, &s->d_trace, 8 * (size_t)pl.ntasks))) return rc;
     RSBA_HIP_TRY(hipMemset(s->d_trace, 0, 8 * (size_t)pl.ntasks * sizeof(long long)));
   }
@@ -1195,8 +1188,7 @@ int32_t PlanBuild::dag_arguments() {
   if (dbg_plan)
     std::fprintf(stderr, "[rsba plan] tiles %d, factor tiles %d, levels %d, tasks %d (partials %d); tile pairs %d, entries %lld, schur chunks %d\n", nt, sv.nslots,
                  hp.nlev, pl.ntasks, hp.nparts, sv.ntp, (long long)s->num_pairs, sv.nchunk);
-  const char* lv = std::getenv("RSBA_CHOL_LEVELS");
-  s->use_levels = lv && lv[0] == '1';
+  s->use_levels = sw.chol_levels_before_solve;   // (for covariance calls before any solve: rsba_solve settles it again)
   DagArgs host_args{sv, pl};
   if ((rc = s_upload(s, &s->d_slot_tiles, hp.slot_tiles))) return rc;
   if ((rc = s_alloc(s, &s->d_verify, 2 * (size_t)sv.npad))) return rc;
@@ -1205,8 +1197,7 @@ int32_t PlanBuild::dag_arguments() {
   RSBA_HIP_TRY(dev_event_acquire(&s->ev_solved, false));
   RSBA_HIP_TRY(dev_event_acquire(&s->ev_verified, false));
   RSBA_HIP_TRY(hipMemset(s->d_verify, 0, 2 * (size_t)sv.npad * sizeof(double)));   // the check kernel leaves it zero again
-  { const char* v = std::getenv("RSBA_CHOL_VERIFY"); s->verify_dag = !(v && v[0] == '0'); }
-  { const char* v = test_hook("RSBA_CHOL_TEST_CORRUPT"); s->test_corrupt_once = v && v[0] == '1'; }
+  s->test_corrupt_once = sw.test_chol_corrupt;
   for (int b = 0; b < 2; ++b) {   // one device copy of {sv, plan} per set of cells
     double* c = s->cells[b];
     host_args.sv.Lf = c + s->cell_off[0]; host_args.sv.chol_part = c + s->cell_off[1]; host_args.sv.Winv = c + s->cell_off[2];
@@ -1253,6 +1244,8 @@ void PlanBuild::statistics() {
 int32_t build_solver_impl(rsba_handle* h) {
   Solver* s = new Solver();
   h->solver = s;   // owned by the handle from here on (freed by rsba_destroy_solver)
+  s->sw = PlanSwitches::read();   // the environment, once: every stage reads the fields (switches.hpp)
+  s->solve_sw = SolveSwitches::read(Solver::kCtlRing);   // (what a step called before any solve goes by)
   PlanBuild b(h, s);
   int32_t rc;
   b.settle_switches();
@@ -1298,7 +1291,7 @@ void rsba_release_plan_scratch() {
 
 void rsba_destroy_solver(rsba_handle* h) {
   if (!h || !h->solver) return;
-  const bool dbg = std::getenv("RSBA_DEBUG_PLAN") != nullptr;
+  const bool dbg = h->solver->sw.debug_plan;
   const double td0 = dbg ? now_s() : 0.0;
   // streams, events and the pinned block go back to the pool (devmem.hpp): idle first — the main stream too, whose last waits name these events
   if (h->stream) (void)hipStreamSynchronize(h->stream);
@@ -1306,10 +1299,10 @@ void rsba_destroy_solver(rsba_handle* h) {
   if (h->solver->mstream) { (void)hipStreamSynchronize(h->solver->mstream); dev_stream_release(h->solver->mstream); }
   for (hipEvent_t e : {h->solver->ev_armed[0], h->solver->ev_armed[1], h->solver->ev_released, h->solver->ev_solved, h->solver->ev_verified, h->solver->ev_fork, h->solver->ev_join}) dev_event_release(e, false);
   dev_pinned_release(h->solver->h_ctl);
-  if (const char* path = h->solver->sv.schur_trace ? std::getenv("RSBA_SCHUR_TRACE") : nullptr) {   // debugging aid: stamps of the last Schur launch
+  if (h->solver->sv.schur_trace && h->solver->sw.schur_trace) {   // debugging aid: stamps of the last Schur launch
     std::vector<long long> tr(8 * (size_t)h->solver->sv.nchunk);
     if (hipMemcpy(tr.data(), h->solver->sv.schur_trace, tr.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
-      if (FILE* f = std::fopen(path, "wb")) { std::fwrite(tr.data(), sizeof(long long), tr.size(), f); std::fclose(f); }
+      if (FILE* f = std::fopen(h->solver->sw.schur_trace->c_str(), "wb")) { std::fwrite(tr.data(), sizeof(long long), tr.size(), f); std::fclose(f); }
   }
   const double td1 = dbg ? now_s() : 0.0;
   if (h->stream) (void)hipStreamSynchronize(h->stream);   // (the side streams above are idle too: the blocks go back to the cache, devmem.hpp)

@@ -17,9 +17,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <functional>
 #include <vector>
+
+#include "switches.hpp"
 
 namespace rsba {
 
@@ -30,9 +31,7 @@ namespace rsba {
 // GPU idle: 0.756 -> 0.662 ms at 1k cameras on 8 ranks, 0.672 -> 0.647 on 2, 1.164 -> 1.131 at 4k cameras on 4
 // (profiles/r04/shard_leaf_sweep.txt).  Every rank — and rsba_partition_points — must use the same.
 inline int plan_leaf_size(int nparts, int nt) {
-  int k = nparts > 1 ? 12 : nt <= 64 ? 8 : nt <= 500 ? 12 : 24;
-  if (const char* e = std::getenv("RSBA_CHOL_LEAF")) k = std::max(2, std::atoi(e));
-  return k;
+  return chol_leaf_override().value_or(nparts > 1 ? 12 : nt <= 64 ? 8 : nt <= 500 ? 12 : 24);   // (read at every call: switches.hpp)
 }
 
 constexpr int kTile = 48;   // Cholesky tile: 4 rolling-shutter frames (12 unknowns) or 8 global-shutter frames
