@@ -31,8 +31,12 @@
 // Inlier rule.  Sampson distance in normalised coordinates, fp64: d^2 = (b^T E a)^2 / ((E a)_x^2 + (E a)_y^2 + (E^T b)_x^2 + (E^T b)_y^2);
 // inlier iff d^2 f^2 <= threshold_px^2 with f = (fx_a + fy_a + fx_b + fy_b) / 4.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <map>
+#include <tuple>
 #include <vector>
 
 #include "ceres_handler.hpp"
@@ -591,6 +595,171 @@ inline TwoViewResult findEssentialRansac(const float* xy_a, const float* xy_b, i
       else hyp_detail::check(rsba_epipolar_hypotheses(device, cam_a, cam_b, xy_a, xy_b, n, sub, m, tasks, opt.threshold_px, E, poses, status, inl, front));
     },
     [&](const double E[9], uint8_t* mask) { hyp_detail::check(rsba_epipolar_inliers(device, cam_a, cam_b, xy_a, xy_b, n, E, opt.threshold_px, mask)); });
+}
+
+// ---- geometric verification: the same RANSAC for many frame pairs in one device call (rsba_amd.h: rsba_epipolar_ransac_pairs) ----
+// One pair's correspondences and cameras; the arrays stay the caller's.
+struct EssentialPair {
+  const float* xy_a = nullptr;   // [n][2] pixels in frame A
+  const float* xy_b = nullptr;   // [n][2] pixels in frame B
+  int n = 0;
+  const double* cam_a = nullptr; // [NUM_CAM_PARAMS]
+  const double* cam_b = nullptr;
+};
+
+// findEssentialRansac for every pair, result p what findEssentialRansac(pairs[p]..., opt, device) returns: pair p's subsets are
+// distinct_subsets(n_p, m, opt.iterations, opt.rng_state), the draw the single call makes for that pair alone, and the loop per pair is
+// epi_detail::ransac, kept on the device by rsba_epipolar_ransac_pairs — one upload, one download, the hypothesis kernels launched over the
+// subsets of all pairs at once.  hypotheses_on_device == false: epi_detail::host_ransac per pair.  max_tasks_per_launch: the C call's (0: its default).
+inline std::vector<TwoViewResult> findEssentialRansacPairs(const std::vector<EssentialPair>& pairs, const TwoViewOptions& opt = TwoViewOptions(), int device = 0,
+                                                           int max_tasks_per_launch = 0) {
+  std::vector<TwoViewResult> out(pairs.size());
+  if (!opt.hypotheses_on_device) {
+    for (size_t p = 0; p < pairs.size(); ++p) out[p] = epi_detail::host_ransac(pairs[p].xy_a, pairs[p].xy_b, pairs[p].n, pairs[p].cam_a, pairs[p].cam_b, opt);
+    return out;
+  }
+  for (size_t p = 0; p < pairs.size(); ++p) out[p].inliers.assign((size_t)(pairs[p].n > 0 ? pairs[p].n : 0), 0);
+  if (pairs.empty() || opt.iterations <= 0) return out;
+  const int T = opt.iterations, m = opt.solver == TwoViewOptions::EssentialSolver::FivePoint ? 5 : 8;
+  const size_t P = pairs.size();
+  // the cameras by value, each once: the call normalises a run of pairs that share a camera in one launch
+  std::vector<double> cams;
+  auto cam_index = [&](const double* cam) {
+    for (size_t c = 0; c * NUM_CAM_PARAMS < cams.size(); ++c) {
+      bool same = true;
+      for (int k = 0; k < NUM_CAM_PARAMS; ++k) same = same && std::memcmp(&cams[c * NUM_CAM_PARAMS + k], &cam[k], sizeof(double)) == 0;
+      if (same) return (int32_t)c;
+    }
+    cams.insert(cams.end(), cam, cam + NUM_CAM_PARAMS);
+    return (int32_t)(cams.size() / NUM_CAM_PARAMS - 1);
+  };
+  std::vector<int32_t> ia(P), ib(P), offset(P + 1, 0), subsets(P * (size_t)T * m, 0);
+  std::vector<float> xa, xb;
+  for (size_t p = 0; p < P; ++p) {
+    const EssentialPair& q = pairs[p];
+    const int n = q.n > 0 ? q.n : 0;
+    ia[p] = cam_index(q.cam_a); ib[p] = cam_index(q.cam_b);
+    offset[p + 1] = offset[p] + n;
+    xa.insert(xa.end(), q.xy_a, q.xy_a + 2 * (size_t)n); xb.insert(xb.end(), q.xy_b, q.xy_b + 2 * (size_t)n);
+    if (n < 8) continue;   // (an empty result; the call does not read the pair's subsets)
+    const std::vector<int32_t> s = hyp_detail::distinct_subsets(n, m, T, opt.rng_state);
+    std::copy(s.begin(), s.end(), subsets.begin() + (std::ptrdiff_t)(p * (size_t)T * m));
+  }
+  if (xa.empty()) { xa.assign(2, 0.0f); xb.assign(2, 0.0f); }   // (only empty pairs: the call still wants arrays)
+  std::vector<double> E(P * 9, 0.0), poses(P * 6, 0.0);
+  std::vector<uint8_t> status(P, 0), mask((size_t)offset[P] + 1, 0);
+  std::vector<int32_t> winner(P, -1), adopted(P, 0), inl(P, 0), front(P * 4, 0);
+  hyp_detail::check(rsba_epipolar_ransac_pairs(device, cams.data(), (int32_t)(cams.size() / NUM_CAM_PARAMS), ia.data(), ib.data(), offset.data(), (int32_t)P, xa.data(), xb.data(),
+                                               subsets.data(), m, T, opt.threshold_px, opt.refits, max_tasks_per_launch, E.data(), poses.data(), status.data(), winner.data(),
+                                               adopted.data(), inl.data(), front.data(), mask.data()));
+  for (size_t p = 0; p < P; ++p) {
+    TwoViewResult& r = out[p];
+    if (!status[p]) continue;
+    for (int k = 0; k < 9; ++k) r.E[k] = E[p * 9 + k];
+    for (int k = 0; k < 6; ++k) r.pose_b[k] = poses[p * 6 + k];
+    r.winner_task = winner[p]; r.refits_adopted = adopted[p]; r.num_inliers = inl[p];
+    int cand = 0;
+    for (int c = 1; c < 4; ++c) if (front[p * 4 + c] > front[p * 4 + cand]) cand = c;
+    r.num_front = front[p * 4 + cand];
+    r.ok = r.num_front >= opt.min_inliers;
+    std::copy(mask.begin() + offset[p], mask.begin() + offset[p + 1], r.inliers.begin());
+  }
+  return out;
+}
+
+// What verifyMatches found for one frame pair.
+struct PairReport {
+  int32_t frameA = 0, frameB = 0;
+  int correspondences = 0;                 // the refs of frame B's observations into frame A
+  bool ok = false;                         // TwoViewResult::ok of the pair
+  int num_inliers = 0, num_front = 0;
+  double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double pose_b[6] = {0, 0, 0, 0, 0, 0};   // camera B in A's frame, unit baseline
+  int removed = 0;                         // refs erased from frame B's observations
+};
+struct VerifyOptions {
+  bool drop_unverified = false;   // true: a pair that is not ok (under 8 correspondences, or no accepted geometry) loses all its refs
+  int max_tasks_per_launch = 0;   // rsba_epipolar_ransac_pairs' (0: its default)
+};
+
+// Geometric verification of the matches of a session, between matchSession and createTracks / initializeTwoView: every frame B and every
+// earlier frame A that B's matches reach make a pair, whose correspondences are all refs of B's observations into A — in observation
+// order, then in the order of an observation's list; cameras f.cam if set, else sess.cam.  All pairs go through findEssentialRansacPairs
+// (one batched device call, or as many launches as its chunking needs).  Of a pair whose result is ok, the refs flagged as outliers are
+// erased from Observation::matches; a pair that is not ok is left as it is unless drop_unverified.  Nothing but `matches` is touched; refs
+// to later frames, to the frame itself or out of range are neither verified nor erased.  The rule is a global-shutter approximation of a
+// rolling-shutter pair (rsba_amd.h): widen tv.threshold_px for such sessions.  Reports in the order (frameB, frameA) ascending.
+inline std::vector<PairReport> verifyMatches(Session& sess, const TwoViewOptions& tv = TwoViewOptions(), int device = 0, const VerifyOptions& vo = VerifyOptions()) {
+  struct Ref { size_t obs, slot; };
+  struct Found { std::vector<Ref> refs; std::vector<float> xa, xb; };
+  std::vector<PairReport> reports;
+  std::vector<Found> found;
+  for (size_t fb = 0; fb < sess.frames.size(); ++fb) {
+    const Frame& B = sess.frames[fb];
+    std::map<int32_t, Found> reached;   // (ascending frame A)
+    for (size_t oi = 0; oi < B.obs.size(); ++oi)
+      for (size_t ri = 0; ri < B.obs[oi].matches.size(); ++ri) {
+        const ObservationRef& ref = B.obs[oi].matches[ri];
+        if (ref.frame < 0 || (size_t)ref.frame >= fb || ref.obs < 0 || (size_t)ref.obs >= sess.frames[(size_t)ref.frame].obs.size()) continue;
+        const Observation& oa = sess.frames[(size_t)ref.frame].obs[(size_t)ref.obs];
+        Found& f = reached[ref.frame];
+        f.refs.push_back(Ref{oi, ri});
+        f.xa.push_back((float)oa.x); f.xa.push_back((float)oa.y); f.xb.push_back((float)B.obs[oi].x); f.xb.push_back((float)B.obs[oi].y);
+      }
+    for (auto& kv : reached) {
+      PairReport r;
+      r.frameA = kv.first; r.frameB = (int32_t)fb; r.correspondences = (int)kv.second.refs.size();
+      reports.push_back(r);
+      found.push_back(std::move(kv.second));
+    }
+  }
+  std::vector<EssentialPair> pairs(reports.size());
+  for (size_t p = 0; p < reports.size(); ++p) {
+    const Frame& A = sess.frames[(size_t)reports[p].frameA];
+    const Frame& B = sess.frames[(size_t)reports[p].frameB];
+    pairs[p].xy_a = found[p].xa.data(); pairs[p].xy_b = found[p].xb.data(); pairs[p].n = reports[p].correspondences;
+    pairs[p].cam_a = A.__isset.cam ? A.cam.data() : sess.cam.data();
+    pairs[p].cam_b = B.__isset.cam ? B.cam.data() : sess.cam.data();
+  }
+  const std::vector<TwoViewResult> results = findEssentialRansacPairs(pairs, tv, device, vo.max_tasks_per_launch);
+  std::vector<std::tuple<size_t, size_t, size_t>> erase;   // (frame B, observation, slot)
+  for (size_t p = 0; p < reports.size(); ++p) {
+    PairReport& r = reports[p];
+    const TwoViewResult& res = results[p];
+    r.ok = res.ok; r.num_inliers = res.num_inliers; r.num_front = res.num_front;
+    for (int k = 0; k < 9; ++k) r.E[k] = res.E[k];
+    for (int k = 0; k < 6; ++k) r.pose_b[k] = res.pose_b[k];
+    if (!res.ok && !vo.drop_unverified) continue;
+    for (size_t i = 0; i < found[p].refs.size(); ++i) {
+      if (res.ok && res.inliers[i]) continue;
+      erase.push_back(std::make_tuple((size_t)r.frameB, found[p].refs[i].obs, found[p].refs[i].slot));
+      ++r.removed;
+    }
+  }
+  // an observation's list holds refs of several pairs: all of them erased from the back, so that the slots in front keep their numbers
+  std::sort(erase.begin(), erase.end());
+  for (size_t i = erase.size(); i-- > 0;) {
+    std::vector<ObservationRef>& list = sess.frames[std::get<0>(erase[i])].obs[std::get<1>(erase[i])].matches;
+    list.erase(list.begin() + (std::ptrdiff_t)std::get<2>(erase[i]));
+  }
+  return reports;
+}
+
+// The pair to start a reconstruction from: the ok pair with the most inliers in front of both cameras; ties go to the lowest frameB, then
+// the lowest frameA.  -1: no pair is ok.
+inline int pickBootstrapPair(const std::vector<PairReport>& reports) {
+  int best = -1;
+  for (size_t p = 0; p < reports.size(); ++p) {
+    const PairReport& r = reports[p];
+    if (!r.ok) continue;
+    if (best >= 0) {
+      const PairReport& b = reports[(size_t)best];
+      if (r.num_front < b.num_front) continue;
+      if (r.num_front == b.num_front && (r.frameB > b.frameB || (r.frameB == b.frameB && r.frameA >= b.frameA))) continue;
+    }
+    best = (int)p;
+  }
+  return best;
 }
 
 namespace epi_detail {

@@ -638,6 +638,45 @@ int32_t rsba_epipolar_hypotheses_five_point(int32_t device, const double* cam_a,
                                             double* E_out /* [num_tasks][9] */, double* poses_out /* [num_tasks][6] */, uint8_t* status,
                                             int32_t* num_inliers, int32_t* num_front /* [num_tasks][4] */, int32_t* num_solutions /* may be NULL */);
 
+/* == geometric verification: the essential-matrix RANSAC of MANY frame pairs in one call — what checks a frame pair's matches against the
+ * pair's epipolar geometry before they become tracks (include/rsba/two_view.hpp: findEssentialRansacPairs, verifyMatches).  The rules are
+ * the ones above, unchanged; this text defines the loop around them, which is epi_detail::ransac per pair (what findEssentialRansac runs for
+ * one pair with the calls above), kept on the device.
+ *   Inputs.  cams [num_cams][9]; pair p has the cameras cams[pair_cam_a[p]], cams[pair_cam_b[p]] and the correspondences
+ *     pair_offset[p] .. pair_offset[p + 1] of xy_a, xy_b [pair_offset[num_pairs]][2] (float pixels; pair_offset[0] = 0, not decreasing);
+ *     n_p their number.  subsets [num_pairs][tasks_per_pair][m] with indices local to the pair (0 .. n_p - 1); m = 8: eight-point subsets,
+ *     m = 5: five-point subsets.  Every side of every pair is undistorted and normalised once per call by the pair's own camera; the
+ *     inlier rule takes the pair's own f.
+ *   Per pair.  Hypotheses: rsba_epipolar_hypotheses (m = 8) or rsba_epipolar_hypotheses_five_point (m = 5) of the pair's subsets over the
+ *     pair's correspondences.  Winner: the accepted task with the most inliers; for m = 5 a tie goes to the task with more inliers in front
+ *     (the most over its four candidates); then the lowest task wins.  inlier_mask = rsba_epipolar_inliers of the winner's E.  Then up to
+ *     `refits` rounds: the ascending indices of the current inliers; stop if they are fewer than 8; the eight-point fit over all of them
+ *     as one task (m = their number) and its score over the pair; adopted iff the task is accepted and its count is not lower, else stop;
+ *     an adopted refit replaces E, the pose, the counts and the mask and adds one to refits_adopted.
+ *   Outputs per pair.  status 1: the pair has a winner; E_out[p], poses_out[p] (camera B in A's frame, unit baseline), winner_task[p],
+ *     refits_adopted[p], num_inliers[p], num_front[p][4] (per candidate, as rsba_epipolar_score counts them) and inlier_mask over the pair's
+ *     range are those of the final E.  status 0: n_p < 8, or no accepted hypothesis — zero counts, a zero mask, winner_task -1, E_out[p] and
+ *     poses_out[p] untouched; the subsets of a pair with n_p < 8 are not read.  A repeated index in a subset is a declined task, not an error.
+ *   Chunking.  Scratch grows with the tasks of a launch (five-point: ten slots per task), so the call works through the pairs in chunks of
+ *     whole pairs of at most max_tasks_per_launch tasks (0: the library's default, 65 536); a pair with more tasks is a chunk of its own.
+ *     One upload, a fixed sequence of launches per chunk with nothing read back between them, one download.  A pair's bytes depend neither
+ *     on the chunking nor on which other pairs share the call: the arithmetic runs in the kernels of the single-pair calls (one compiled
+ *     eight-point kernel for the subsets and the refits, one score kernel), the loop's own kernels move integers and copies, and nothing
+ *     uses an atomic.
+ *   A global-shutter rule.  E relates two central projections.  A pair of rolling-shutter frames has no single E (every scanline has its
+ *     own pose); the rule treats it as the global-shutter pair at the frames' first pose slots, as the bootstrap above does, and the
+ *     residual motion within a frame shows up as Sampson distance.  The threshold is the caller's to widen for such pairs.
+ *   Errors (RSBA_ERR_INVALID_ARGUMENT, outputs untouched): a null pointer; num_cams, num_pairs or tasks_per_pair <= 0; refits or
+ *     max_tasks_per_launch < 0; m not 5 or 8; pair_offset[0] != 0 or a decreasing pair_offset; a camera index out of range; a subset index
+ *     outside 0 .. n_p - 1 of a pair with n_p >= 8.  All pointers are host arrays. */
+int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams /* [num_cams][9] */, int32_t num_cams, const int32_t* pair_cam_a /* [num_pairs] */,
+                                   const int32_t* pair_cam_b /* [num_pairs] */, const int32_t* pair_offset /* [num_pairs + 1] */, int32_t num_pairs,
+                                   const float* xy_a, const float* xy_b, const int32_t* subsets /* [num_pairs][tasks_per_pair][m] */, int32_t m,
+                                   int32_t tasks_per_pair, double threshold_px, int32_t refits, int32_t max_tasks_per_launch,
+                                   double* E_out /* [num_pairs][9] */, double* poses_out /* [num_pairs][6] */, uint8_t* status /* [num_pairs] */,
+                                   int32_t* winner_task, int32_t* refits_adopted, int32_t* num_inliers, int32_t* num_front /* [num_pairs][4] */,
+                                   uint8_t* inlier_mask /* [pair_offset[num_pairs]] */);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

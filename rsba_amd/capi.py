@@ -24,7 +24,7 @@ EXPORTS = [
     "rsba_validate_observations", "rsba_reproject", "rsba_pose_covariance", "rsba_set_motion_priors",
     "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p",
     "rsba_epipolar_eight_point", "rsba_epipolar_score", "rsba_epipolar_hypotheses", "rsba_epipolar_inliers",
-    "rsba_epipolar_five_point", "rsba_epipolar_hypotheses_five_point", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
+    "rsba_epipolar_five_point", "rsba_epipolar_hypotheses_five_point", "rsba_epipolar_ransac_pairs", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
@@ -164,6 +164,8 @@ def lib():
         _lib.rsba_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.rsba_epipolar_five_point.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
         _lib.rsba_epipolar_hypotheses_five_point.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 6
+        _lib.rsba_epipolar_ransac_pairs.argtypes = ([C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32]
+                                                    + [C.c_void_p] * 8)
     return _lib
 
 
@@ -774,6 +776,30 @@ def epipolar_hypotheses_five_point(cam_a, cam_b, xy_a, xy_b, subsets, threshold_
     _check(lib().rsba_epipolar_hypotheses_five_point(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(sub), H, float(threshold_px), _ptr(E), _ptr(poses),
                                                      _ptr(status), _ptr(inl), _ptr(front), _ptr(count)))
     return dict(E=E, poses=poses, status=status, num_inliers=inl, num_front=front, num_solutions=count)
+
+
+def epipolar_ransac_pairs(cams, pair_cam_a, pair_cam_b, pair_offset, xy_a, xy_b, subsets, threshold_px=4.0, refits=3, max_tasks_per_launch=0,
+                          E_out=None, poses_out=None, device=0):
+    """The essential-matrix RANSAC of many frame pairs in one call (rsba_amd.h: rsba_epipolar_ransac_pairs).  cams [C,9]; pair p has the
+    correspondences pair_offset[p] .. pair_offset[p+1] of xy_a / xy_b and the subsets subsets[p] ([P,T,m], indices local to the pair, m 5 or 8).
+    -> dict(E [P,9], poses [P,6] (pairs without a winner keep what E_out / poses_out held, zeros without them), status [P], winner_task [P],
+    refits_adopted [P], num_inliers [P], num_front [P,4], mask [N] bool)"""
+    cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 9)
+    ia = np.ascontiguousarray(pair_cam_a, dtype=np.int32); ib = np.ascontiguousarray(pair_cam_b, dtype=np.int32)
+    off = np.ascontiguousarray(pair_offset, dtype=np.int32); P = len(off) - 1
+    a = np.ascontiguousarray(xy_a, dtype=np.float32).reshape(-1, 2); b = np.ascontiguousarray(xy_b, dtype=np.float32).reshape(-1, 2)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32)
+    assert len(ia) == len(ib) == P and sub.ndim == 3 and sub.shape[0] == P and len(a) == len(b) == int(off[-1])
+    E = np.zeros((P, 9)) if E_out is None else E_out
+    poses = np.zeros((P, 6)) if poses_out is None else poses_out
+    assert E.dtype == np.float64 and E.shape == (P, 9) and E.flags.c_contiguous
+    assert poses.dtype == np.float64 and poses.shape == (P, 6) and poses.flags.c_contiguous
+    status = np.zeros(P, dtype=np.uint8); winner = np.zeros(P, dtype=np.int32); adopted = np.zeros(P, dtype=np.int32)
+    inl = np.zeros(P, dtype=np.int32); front = np.zeros((P, 4), dtype=np.int32); mask = np.zeros(len(a), dtype=np.uint8)
+    _check(lib().rsba_epipolar_ransac_pairs(device, _ptr(cams), len(cams), _ptr(ia), _ptr(ib), _ptr(off), P, _ptr(a), _ptr(b), _ptr(sub), sub.shape[2], sub.shape[1],
+                                            float(threshold_px), int(refits), int(max_tasks_per_launch), _ptr(E), _ptr(poses), _ptr(status), _ptr(winner), _ptr(adopted),
+                                            _ptr(inl), _ptr(front), _ptr(mask)))
+    return dict(E=E, poses=poses, status=status, winner_task=winner, refits_adopted=adopted, num_inliers=inl, num_front=front, mask=mask.astype(bool))
 
 
 def epipolar_inliers(cam_a, cam_b, xy_a, xy_b, E, threshold_px=4.0, device=0):
