@@ -677,6 +677,79 @@ int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams /* [num_ca
                                    int32_t* winner_task, int32_t* refits_adopted, int32_t* num_inliers, int32_t* num_front /* [num_pairs][4] */,
                                    uint8_t* inlier_mask /* [pair_offset[num_pairs]] */);
 
+/* == two-view degeneracy: how well a homography explains a frame pair, and how much parallax its inliers have — the two measurements that
+ * tell a pair fit to start a reconstruction from one that only turned, has a baseline of a per cent of the depth, or looks at a wall
+ * (include/rsba/pair_geometry.hpp: findHomographyRansac, classifyPairs, classifyMatches, pickBootstrapPair with a geometry).  The reference
+ * has no such step, so this text is the definition; homo_detail (dlt, invert, transfer_inlier, score, parallax_counts) is its host form.
+ *   Inputs and conventions.  As for rsba_epipolar_*: xy_a, xy_b [n][2] float pixels, the 9 sfm intrinsics per side; both sides undistorted
+ *     and normalised once per call, a = (xa, ya, 1), b = (xb, yb, 1).  H is row-major with b ~ H a.
+ *   Four-point DLT (m >= 4 indices per subset; the minimal sample and the refit over all inliers alike).  Hartley normalisation of each
+ *     side's m points (hyp_detail::hartley_side); the 9 x 9 Gram matrix of the 2 m rows (-a', 0, xb' a') and (0, -a', yb' a'); its smallest
+ *     eigenvector by the cyclic Jacobi of the eight-point rule under the same two gap tests (hyp_detail::null_vector9: the largest eigenvalue
+ *     counts the idle unknowns, twice the trace); the normalisation undone, H = Tb^-1 Hn Ta; scaled to unit Frobenius norm.  Sign: (H a)_z > 0
+ *     for the subset's first index.
+ *     Declined (status 0, H_out[t] untouched): a repeated index; a Hartley scale that is not positive; a second null direction (three of four
+ *     points on a line, two coincident points); (H a)_z not of one sign over the subset — the orientation test; |det H| not above 1e-6 (with
+ *     the Frobenius norm at 1); a result that is not finite.
+ *   Inlier rule.  Transfer error in normalised coordinates, fp64, both ways: d_ab^2 = |b - pi(H a)|^2, d_ba^2 = |a - pi(H^-1 b)|^2, H^-1 the
+ *     adjugate over the determinant, computed once per matrix.  Inlier iff (H a)_z > 0, (H^-1 b)_z > 0 and max(d_ab^2, d_ba^2) f^2 <=
+ *     threshold_px^2, f the mean focal length of the epipolar rule.  The inverse and the deciding comparisons are evaluated with the host
+ *     form's operations in the host form's order, every product and sum rounded on its own.
+ *   Score.  num_inliers[t] of every given H.  Declined (status 0, a zero count): a determinant that is zero or not finite, an inverse that
+ *     is not finite.
+ *   Parallax rule.  Given a pair's E, its pose (camera B in A's frame, the 6-vector rsba_epipolar_score writes; R and t = -R c from it by
+ *     hyp_detail::rotate) and a threshold angle: a correspondence counts as IN FRONT when it is a Sampson inlier of E (the epipolar rule, the
+ *     same threshold_px) and in front for (R, t) (the epipolar rule's depths); as HAVING PARALLAX when, in addition, the angle between the rays
+ *     a and R^T b is at least the threshold — decided without an inverse cosine, a . (R^T b) <= c sqrt(|a|^2 |R^T b|^2), c the cosine of the
+ *     threshold, passed as a double.  Two integer counts per pair: "the median parallax reaches the angle" is 2 num_parallax > num_front.
+ * rsba_homography_dlt: one lane per subset, fp64; a subset's result does not depend on where it sits in the call.
+ * rsba_homography_score: scores the given matrices H [num_tasks][9], one wave per matrix; the counts are integer sums.
+ * rsba_homography_hypotheses: the chain — normalise, DLT, score; H never leaves the device between the two kernels.  status[t] 1: solved and
+ *   scored; 0: declined by either step (a zero count, H_out[t] untouched).
+ * rsba_homography_inliers: the inlier flags [n] of one H (all zero for an H the score declines).
+ * n >= 4, m >= 4, n >= m, num_tasks > 0; otherwise, and for a null pointer or a subset index outside 0 .. n - 1, RSBA_ERR_INVALID_ARGUMENT with
+ * the outputs untouched.  All pointers are host arrays. */
+int32_t rsba_homography_dlt(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                            const int32_t* subsets /* [num_tasks][m] */, int32_t m, int32_t num_tasks, double* H_out /* [num_tasks][9] */,
+                            uint8_t* status);
+int32_t rsba_homography_score(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                              const double* H /* [num_tasks][9] */, int32_t num_tasks, double threshold_px, int32_t* num_inliers, uint8_t* status);
+int32_t rsba_homography_hypotheses(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                   const int32_t* subsets /* [num_tasks][m] */, int32_t m, int32_t num_tasks, double threshold_px,
+                                   double* H_out /* [num_tasks][9] */, uint8_t* status, int32_t* num_inliers);
+int32_t rsba_homography_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
+                                const double* H /* [9] */, double threshold_px, uint8_t* inlier_mask /* [n] */);
+
+/* The homography RANSAC and the parallax counts of MANY frame pairs in one call (classifyPairs).  Inputs as rsba_epipolar_ransac_pairs: cams,
+ * pair_cam_a / pair_cam_b, pair_offset, xy_a / xy_b; subsets [num_pairs][tasks_per_pair][4] with indices local to the pair.  E [num_pairs][9],
+ * poses [num_pairs][6] and pair_status [num_pairs] are the pairs' essential results (rsba_epipolar_ransac_pairs' E_out, poses_out, or the
+ * caller's verdict in pair_status); where pair_status[p] is 0, E[p] and poses[p] are not used.
+ *   Per pair.  Hypotheses: rsba_homography_hypotheses of the pair's subsets over the pair's correspondences.  Winner: the accepted task with
+ *     the most inliers, then the lowest task.  h_inlier_mask = rsba_homography_inliers of the winner's H.  Then up to `refits` rounds: the
+ *     ascending indices of the current inliers; stop if they are fewer than 5; the DLT over all of them as one task (m = their number) and
+ *     its score over the pair; adopted iff the task is accepted and its count is not lower, else stop; an adopted refit replaces H, the
+ *     count and the mask and adds one to h_refits_adopted.  For a pair with pair_status[p] != 0 the parallax rule with E[p], poses[p] gives
+ *     num_front[p], num_parallax[p]; else both are 0.
+ *   Outputs per pair.  h_status 1: the pair has a winner; H_out[p], h_winner_task[p], h_refits_adopted[p], num_h_inliers[p] and h_inlier_mask
+ *     over the pair's range are those of the final H.  h_status 0: n_p < 4, or no accepted hypothesis — a zero count, a zero mask,
+ *     h_winner_task -1, H_out[p] untouched; the subsets of a pair with n_p < 4 are not read.
+ *   Chunking.  Whole pairs of at most max_tasks_per_launch tasks per launch (0: 65 536); a pair with more tasks is a chunk of its own.  One
+ *     upload, a fixed sequence of launches per chunk with nothing read back between them, the parallax kernel once over all pairs, one
+ *     download.  A pair's bytes depend neither on the chunking nor on which other pairs share the call: the arithmetic runs in the kernels of
+ *     the single-pair calls (one compiled DLT kernel for the subsets and the refits, one score kernel), the loop's own kernels move integers
+ *     and copies, and nothing uses an atomic.
+ *   Errors (RSBA_ERR_INVALID_ARGUMENT, outputs untouched): a null pointer; num_cams, num_pairs or tasks_per_pair <= 0; refits or
+ *     max_tasks_per_launch < 0; cos_min_parallax outside [-1, 1]; pair_offset[0] != 0 or a decreasing pair_offset; a camera index out of
+ *     range; a subset index outside 0 .. n_p - 1 of a pair with n_p >= 4.  All pointers are host arrays. */
+int32_t rsba_two_view_classify_pairs(int32_t device, const double* cams /* [num_cams][9] */, int32_t num_cams, const int32_t* pair_cam_a /* [num_pairs] */,
+                                     const int32_t* pair_cam_b /* [num_pairs] */, const int32_t* pair_offset /* [num_pairs + 1] */, int32_t num_pairs,
+                                     const float* xy_a, const float* xy_b, const double* E /* [num_pairs][9] */, const double* poses /* [num_pairs][6] */,
+                                     const uint8_t* pair_status /* [num_pairs] */, const int32_t* subsets /* [num_pairs][tasks_per_pair][4] */,
+                                     int32_t tasks_per_pair, double threshold_px, int32_t refits, double cos_min_parallax, int32_t max_tasks_per_launch,
+                                     double* H_out /* [num_pairs][9] */, uint8_t* h_status /* [num_pairs] */, int32_t* h_winner_task, int32_t* h_refits_adopted,
+                                     int32_t* num_h_inliers, uint8_t* h_inlier_mask /* [pair_offset[num_pairs]] */, int32_t* num_front /* [num_pairs] */,
+                                     int32_t* num_parallax /* [num_pairs] */);
+
 /* ---- multi-GPU: one process per GPU, observations partitioned BY POINT, cameras replicated ----
  * (the reference is single-process; this is the exchange step SURVEY §8e derives for the path).
  * Every rank creates a handle over its own observations (all frames / points arrays are full size, a rank

@@ -24,7 +24,9 @@ EXPORTS = [
     "rsba_validate_observations", "rsba_reproject", "rsba_pose_covariance", "rsba_set_motion_priors",
     "rsba_pnp_tasks", "rsba_pnp_inliers", "rsba_pnp_dlt", "rsba_pnp_gs_hypotheses", "rsba_pnp_p3p", "rsba_pnp_gs_hypotheses_p3p",
     "rsba_epipolar_eight_point", "rsba_epipolar_score", "rsba_epipolar_hypotheses", "rsba_epipolar_inliers",
-    "rsba_epipolar_five_point", "rsba_epipolar_hypotheses_five_point", "rsba_epipolar_ransac_pairs", "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
+    "rsba_epipolar_five_point", "rsba_epipolar_hypotheses_five_point", "rsba_epipolar_ransac_pairs",
+    "rsba_homography_dlt", "rsba_homography_score", "rsba_homography_hypotheses", "rsba_homography_inliers", "rsba_two_view_classify_pairs",
+    "rsba_set_inter_frame_ratio_free", "rsba_get_inter_frame_ratio",
     "rsba_sync_block_structure", "rsba_rccl_get_unique_id", "rsba_rccl_comm_create", "rsba_rccl_comm_destroy", "rsba_set_exchange_rccl",
     "rsba_get_phase_times", "rsba_phase_name", "rsba_get_plan_stats", "rsba_validate_frame", "rsba_reproject_frame", "rsba_set_pose_priors", "rsba_set_global_shutter_frames", "rsba_release_host_scratch",
     "rsba_partition_points", "rsba_get_exchange_stats", "rsba_exchange_name", "rsba_rccl_describe", "rsba_track_candidates",
@@ -166,6 +168,12 @@ def lib():
         _lib.rsba_epipolar_hypotheses_five_point.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 6
         _lib.rsba_epipolar_ransac_pairs.argtypes = ([C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32]
                                                     + [C.c_void_p] * 8)
+        _lib.rsba_homography_dlt.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 2
+        _lib.rsba_homography_score.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 2
+        _lib.rsba_homography_hypotheses.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 3
+        _lib.rsba_homography_inliers.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_double, C.c_void_p]
+        _lib.rsba_two_view_classify_pairs.argtypes = ([C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 6
+                                                      + [C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 8)
     return _lib
 
 
@@ -809,6 +817,73 @@ def epipolar_inliers(cam_a, cam_b, xy_a, xy_b, E, threshold_px=4.0, device=0):
     mask = np.zeros(len(a), dtype=np.uint8)
     _check(lib().rsba_epipolar_inliers(C.c_int32(device), _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), C.c_int32(len(a)), _ptr(E), C.c_double(float(threshold_px)), _ptr(mask)))
     return mask.astype(bool)
+
+
+def homography_dlt(cam_a, cam_b, xy_a, xy_b, subsets, H_out=None, device=0):
+    """The homography of every subset of m >= 4 correspondences, on the device (rsba_amd.h: rsba_homography_dlt).
+    -> dict(H [T,9] row-major, b ~ H a (declined rows keep what H_out held, zeros without it), status [T]: 0 declined, 1 solved)"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); T, m = sub.shape
+    H = np.zeros((T, 9)) if H_out is None else H_out
+    assert H.dtype == np.float64 and H.shape == (T, 9) and H.flags.c_contiguous
+    status = np.zeros(T, dtype=np.uint8)
+    _check(lib().rsba_homography_dlt(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(sub), m, T, _ptr(H), _ptr(status)))
+    return dict(H=H, status=status)
+
+
+def homography_score(cam_a, cam_b, xy_a, xy_b, H, threshold_px=4.0, device=0):
+    """The inlier count of every given H (rsba_amd.h: rsba_homography_score).  -> dict(num_inliers [T], status [T]: 0 declined, 1 scored)"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9); T = len(H)
+    inl = np.zeros(T, dtype=np.int32); status = np.zeros(T, dtype=np.uint8)
+    _check(lib().rsba_homography_score(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(H), T, float(threshold_px), _ptr(inl), _ptr(status)))
+    return dict(num_inliers=inl, status=status)
+
+
+def homography_hypotheses(cam_a, cam_b, xy_a, xy_b, subsets, threshold_px=4.0, H_out=None, device=0):
+    """DLT and score in one call, H staying on the device between them (rsba_amd.h: rsba_homography_hypotheses).
+    -> dict(H [T,9], status [T]: 0 declined by either step, 1 solved and scored; num_inliers [T])"""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32); T, m = sub.shape
+    H = np.zeros((T, 9)) if H_out is None else H_out
+    assert H.dtype == np.float64 and H.shape == (T, 9) and H.flags.c_contiguous
+    inl = np.zeros(T, dtype=np.int32); status = np.zeros(T, dtype=np.uint8)
+    _check(lib().rsba_homography_hypotheses(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(sub), m, T, float(threshold_px), _ptr(H), _ptr(status), _ptr(inl)))
+    return dict(H=H, status=status, num_inliers=inl)
+
+
+def homography_inliers(cam_a, cam_b, xy_a, xy_b, H, threshold_px=4.0, device=0):
+    """Inlier flags [n] of one homography (rsba_amd.h: rsba_homography_inliers)."""
+    ca, cb, a, b = _two_view_inputs(cam_a, cam_b, xy_a, xy_b)
+    H = np.ascontiguousarray(H, dtype=np.float64).reshape(9)
+    mask = np.zeros(len(a), dtype=np.uint8)
+    _check(lib().rsba_homography_inliers(device, _ptr(ca), _ptr(cb), _ptr(a), _ptr(b), len(a), _ptr(H), float(threshold_px), _ptr(mask)))
+    return mask.astype(bool)
+
+
+def two_view_classify_pairs(cams, pair_cam_a, pair_cam_b, pair_offset, xy_a, xy_b, E, poses, pair_status, subsets, threshold_px=4.0, refits=3,
+                            cos_min_parallax=1.0, max_tasks_per_launch=0, H_out=None, device=0):
+    """The homography RANSAC and the parallax counts of many frame pairs in one call (rsba_amd.h: rsba_two_view_classify_pairs).  cams [C,9];
+    pair p has the correspondences pair_offset[p] .. pair_offset[p+1] of xy_a / xy_b, the essential result E[p], poses[p], pair_status[p] and
+    the subsets subsets[p] ([P,T,4], indices local to the pair).
+    -> dict(H [P,9] (pairs without a winner keep what H_out held, zeros without it), status [P], winner_task [P], refits_adopted [P],
+    num_inliers [P], mask [N] bool, num_front [P], num_parallax [P])"""
+    cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 9)
+    ia = np.ascontiguousarray(pair_cam_a, dtype=np.int32); ib = np.ascontiguousarray(pair_cam_b, dtype=np.int32)
+    off = np.ascontiguousarray(pair_offset, dtype=np.int32); P = len(off) - 1
+    a = np.ascontiguousarray(xy_a, dtype=np.float32).reshape(-1, 2); b = np.ascontiguousarray(xy_b, dtype=np.float32).reshape(-1, 2)
+    E = np.ascontiguousarray(E, dtype=np.float64).reshape(-1, 9); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
+    pst = np.ascontiguousarray(pair_status, dtype=np.uint8)
+    sub = np.ascontiguousarray(subsets, dtype=np.int32)
+    assert len(ia) == len(ib) == len(E) == len(poses) == len(pst) == P and sub.ndim == 3 and sub.shape[0] == P and sub.shape[2] == 4 and len(a) == len(b) == int(off[-1])
+    H = np.zeros((P, 9)) if H_out is None else H_out
+    assert H.dtype == np.float64 and H.shape == (P, 9) and H.flags.c_contiguous
+    status = np.zeros(P, dtype=np.uint8); winner = np.zeros(P, dtype=np.int32); adopted = np.zeros(P, dtype=np.int32); inl = np.zeros(P, dtype=np.int32)
+    mask = np.zeros(len(a), dtype=np.uint8); front = np.zeros(P, dtype=np.int32); par = np.zeros(P, dtype=np.int32)
+    _check(lib().rsba_two_view_classify_pairs(device, _ptr(cams), len(cams), _ptr(ia), _ptr(ib), _ptr(off), P, _ptr(a), _ptr(b), _ptr(E), _ptr(poses), _ptr(pst), _ptr(sub),
+                                              sub.shape[1], float(threshold_px), int(refits), float(cos_min_parallax), int(max_tasks_per_launch), _ptr(H), _ptr(status),
+                                              _ptr(winner), _ptr(adopted), _ptr(inl), _ptr(mask), _ptr(front), _ptr(par)))
+    return dict(H=H, status=status, winner_task=winner, refits_adopted=adopted, num_inliers=inl, mask=mask.astype(bool), num_front=front, num_parallax=par)
 
 
 def default_options(**kw) -> SolverOptions:
