@@ -154,7 +154,7 @@ class SelectedInverse:
     nlev: int
 
 
-def selinv_fp64(prob, r, J, plan_of, frame_pairs, points=(), intrinsics=(), *, fault=None) -> SelectedInverse:
+def selinv_fp64(prob, r, J, plan_of, frame_pairs, points=(), intrinsics=(), *, fault=None, fault_frame=None) -> SelectedInverse:
     """rsba_covariance_compute and its getters step by step, every product in fp64:
       1. Schur elimination of the points and the priorPoses blocks from J^T J (block diagonal: one sparse solve) -> the reduced camera
          system S, bordered by the column of a free interFrameRatio;
@@ -168,9 +168,25 @@ def selinv_fp64(prob, r, J, plan_of, frame_pairs, points=(), intrinsics=(), *, f
       6. point blocks V^-1 + V^-1 (W^T Sigma W) V^-1 + q q^T / s, q = V^-1 W^T v, W the point's cross block (nonzero in its frames only).
     fault (the negative controls of tests/test_cov_reference.py): "tile" — one diagonal tile of Sigma, the one of frame_pairs[-1][0], is
     off by 1e-9 relative; "transpose" — an OFF item takes Sigma_ki where it needs Sigma_ik = Sigma_ki^T; "border" — the border's term is
-    left out."""
-    assert fault in (None, "tile", "transpose", "border")
+    left out; "record" (tests/test_loss_paths_reference.py: under a general loss, lm_step_reference.huber_rho substituted) — the point
+    rows of frame ``fault_frame`` come from the record of the no-loss / Huber-at-scale-1 instantiation: in step 6 the observations of
+    that frame enter W with the raw Jacobian (the problem here carries no Huber threshold of its own: rho' = 1, no corrector), V^-1 and
+    Sigma, which the solver's passes left, stay."""
+    assert fault in (None, "tile", "transpose", "border", "record")
     Jld, _, free, pos, ncam, nparam = R.assemble(prob, r, J)
+    Hrec = None
+    if fault == "record":
+        raw = prob.copy()
+        raw.huber_a = 0.0                                           # corrected() returns the blocks as they are
+        Jraw, _, free_raw, _, _, _ = R.assemble(raw, r, J)
+        assert np.array_equal(free, free_raw)
+        obs = np.flatnonzero(prob.obs_frame == int(fault_frame))
+        assert len(obs), "the frame of the fault has no observation"
+        rows = (2 * obs[:, None] + np.arange(2)[None, :]).reshape(-1)   # assemble(): the observations' rows 2 i + d come first
+        Jmix = Jld.astype(np.float64).tolil()
+        Jmix[rows] = Jraw.astype(np.float64).tocsr()[rows]
+        Jmix = Jmix.tocsr()
+        Hrec = (Jmix.T @ Jmix).tocsc()
     L = R.layout(prob)
     CD, F = L["CD"], prob.num_frames
     NIB = 0 if prob.calibrated else prob.num_intrinsics
@@ -282,7 +298,7 @@ def selinv_fp64(prob, r, J, plan_of, frame_pairs, points=(), intrinsics=(), *, f
         if np.any(pj < 0):
             pb[int(j)] = np.zeros((3, 3))
             continue
-        Wj = Hc[:, pj][camk].toarray()                              # [camera-side unknowns, 3]
+        Wj = (Hc if Hrec is None else Hrec)[:, pj][camk].toarray()   # [camera-side unknowns, 3]
         nz = np.flatnonzero(np.any(Wj != 0, axis=1))
         rows = kd[cam][nz]
         Vinv = np.linalg.inv(Hc[:, pj][pj].toarray())

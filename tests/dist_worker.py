@@ -3,6 +3,7 @@
 mode "cpu": host-side exchange logic over gloo, partial blocks from the oracle (no GPU needed)
 mode "step:...": one iteration of the sharded solve, the solved parameters written for a comparison with a host reference
 mode "cov:...": pose covariance blocks on a handle with an exchange attached, then one iteration on that handle and on a fresh one
+("step:" and "cov:" take a flag "loss=<key>", the keys of tests/test_gpu_loss.py: every rank sets that loss after rsba_create)
 mode "gpu": the sharded on-device LM solve, both ranks on GPU 0, exchange staged through gloo ("gpu_priors": with motion priors,
 "gpu_free_ratio": with a free interFrameRatio, "gpu_pose_priors": with GoodPosePrior blocks)"""
 import json
@@ -23,6 +24,22 @@ def scene():
     apply_gauge_masks(p, fix_first_n_cameras=1)
     p.pose_fixed_mask[-1, -1] |= 0b111000
     return p
+
+
+def loss_of(flags):
+    """The loss of a mode's "loss=<key>" flag (tests/test_gpu_loss.py: the_loss), None without one."""
+    key = next((f[5:] for f in flags if f.startswith("loss=")), None)
+    if key is None:
+        return None
+    from test_gpu_loss import the_loss
+    return the_loss(key)
+
+
+def set_loss_of(dp, flags):
+    """Every rank sets the mode's loss, after create and before the collective call (include/rsba_amd.h)."""
+    loss = loss_of(flags)
+    if loss is not None:
+        dp.set_loss(type=loss[0], a=loss[1], b=loss[2], scale=loss[3])
 
 
 def nd_problem(cfg, flags):
@@ -66,6 +83,8 @@ def nd_problem(cfg, flags):
     if "spherical" in flags:   # the SphericalPrior of a session that starts at the origin (CeresHandler.h:36-50,127-130): ONE 2-residual block on the first pose of frame 1 — its terms go to the rank whose part holds that pose
         full.poses[0] = 0.0; full.poses[1] = 0.0; full.poses[1, :, 3:] += 1e-4
         full.spherical_pose_block = 2
+    if any(f.startswith("loss=") for f in flags):   # the loss comes through rsba_set_loss: the problem carries no Huber threshold of its own (parent and workers build the same problem)
+        full.huber_a = 0.0
     return full
 
 
@@ -145,8 +164,12 @@ def step_mode(mode, outdir, rank, world, dist, torch):
     shard = full.shard(rank, world, owner)
     torch.cuda.set_device(0)
     dp = capi.DeviceProblem(shard, device=0)
+    set_loss_of(dp, flags)
     attach(dp)
-    s, tr = dp.solve(capi.default_options(**ONE_STEP))
+    o = capi.default_options(**ONE_STEP)
+    if loss_of(flags) is not None:   # the step is what is under test: every valid one is applied (tests/test_gpu_loss.py)
+        o.min_relative_decrease = -1e300
+    s, tr = dp.solve(o)
     st = dp.plan_stats()
     dp.close()
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), poses=shard.poses, points=shard.points, intrinsics=shard.intrinsics,
@@ -194,6 +217,7 @@ def cov_mode(mode, outdir, rank, world, dist, torch):
     for with_cov in (True, False):
         shard = full.shard(rank, world, owner)
         dp = capi.DeviceProblem(shard, device=0)
+        set_loss_of(dp, flags)
         attach(dp)
         before = dp.plan_stats()["sharded_factorisation"]
         if with_cov:

@@ -147,12 +147,35 @@ class PcgRun:
     r: list
 
 
-def pcg(red: Reduced, *, min_iterations=1, max_iterations=500, eta=0.1, r_tolerance=-1.0, drop_block=None, drop_transposed=None, stop_late=0) -> PcgRun:
+def prior_cross_entries(prob, ref: R.LMStep, red: Reduced) -> np.ndarray:
+    """[nc, nc]: the entries of the motion priors' (f, f - 1) blocks of S — both orientations — that couple DIFFERENT pose coordinates
+    (k of one pose with k' != k of another).  Without a loss, and under one with rho'' <= 0, a prior's Jacobian is kron(C, I6) times row
+    weights and these entries are zero; the corrector's rank-one term (rho'' > 0: TolerantLoss) fills them.  The points and the
+    priorPoses blocks couple no two frames through H's camera block, so what H holds there is the priors' and is S's entry too up to
+    the points' fill, which stays."""
+    F, CD = prob.num_frames, R.layout(prob)["CD"]
+    g = np.asarray(ref.free)[red.cam]
+    H = sp.csr_matrix(ref.H)[red.cam][:, red.cam].toarray().astype(red.dtype)
+    pose = g < F * CD
+    fr = np.where(pose, g // CD, -1)
+    pf = np.zeros(F + 1, dtype=bool)
+    pf[np.asarray(prob.prior_frames, dtype=np.int64)] = True
+    upper = pose[:, None] & pose[None, :] & (fr[:, None] == fr[None, :] + 1) & pf[fr][:, None]   # rows in f, columns in f - 1
+    other = (g % 6)[:, None] != (g % 6)[None, :]
+    m = upper & other
+    return np.where(m | m.T, H, 0)
+
+
+def pcg(red: Reduced, *, min_iterations=1, max_iterations=500, eta=0.1, r_tolerance=-1.0, drop_block=None, drop_transposed=None, stop_late=0,
+        drop_entries=None) -> PcgRun:
     """The recurrence and the stopping rule of include/rsba_amd.h in red.dtype.  Seeded errors: ``drop_block`` = index of a block of M
     replaced by the identity; ``drop_transposed`` = (I, J), I > J: tile (I, J) of S is not used for the rows of tile J;
-    ``stop_late`` = 1: the stopping tests look at iteration k - 1's numbers."""
+    ``stop_late`` = 1: the stopping tests look at iteration k - 1's numbers; ``drop_entries`` = [nc, nc] (prior_cross_entries): these
+    entries are missing from S in S p — the prior's (f, f - 1) block left as sparse as it is without a loss."""
     dt = red.dtype
     S, rhs = red.S, red.rhs
+    if drop_entries is not None:
+        S = S - np.asarray(drop_entries, dtype=dt)
     if drop_transposed is not None:
         I, J = drop_transposed
         S = S.copy()

@@ -618,28 +618,62 @@ def test_a_rank_that_never_arrives_is_reported_not_waited_for_forever(tmp_path):
     assert a["destroy"] == 2 and b["destroy"] == 0      # ncclSystemError on the rank that waited; nothing to report on the one that never called
 
 
+_step_refs = {}
+
+
+def sharded_step_reference(oracle, mode):
+    """(the whole problem of a "step:" mode, the host reference of its first step): computed once per mode — and so per (mode, loss) —
+    and shared by the runs on 2 and 4 ranks.  With a loss the regime conditions on the case are asserted here (no GPU needed)."""
+    import lm_step_reference as R
+    import loss_reference as L
+    from dist_worker import loss_of, nd_problem
+    if mode not in _step_refs:
+        flags = mode.split(":")[2:]
+        full = nd_problem(mode.split(":")[1], flags)
+        r, J, ok = oracle.evaluate_blocks(full)
+        assert ok.all()
+        loss = loss_of(flags)
+        if loss is None:
+            ref = R.lm_step(full, r, J)
+        else:
+            from test_loss_paths_reference import regime_conditions
+            lo, hi, curved = regime_conditions(full, r, loss)
+            print(f"{mode}: rho1 < 0.5 on {lo:.3f}, rho1 > 0.9 on {hi:.3f}, rho2 > 1e-6 on {curved:.3f} of the blocks that take the loss")
+            ref = L.lm_step(full, r, J, loss)
+        _step_refs[mode] = (full, ref)
+    return _step_refs[mode]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,world", [("step:S300:perframe:mixedintr:seed8", 2), ("step:S300:perframe:mixedintr:seed8", 4),
                                         ("step:S300:perframe:runintr5", 2), ("step:S300:perframe:runintr5", 4), ("step:C2:intr", 2), ("step:C2:intr", 4),
                                         ("step:S300:priors", 2), ("step:S300:priors", 4), ("step:S300:priors:freeratio", 2), ("step:S300:priors:freeratio", 4),
                                         ("step:S300:posepriors", 2), ("step:S300:posepriors", 4), ("step:S300:spherical", 2), ("step:S300:spherical", 4),
-                                        ("step:S300:perframe:mixedintr:seed8:priors", 2), ("step:S300:perframe:mixedintr:seed8:priors", 4)])
+                                        ("step:S300:perframe:mixedintr:seed8:priors", 2), ("step:S300:perframe:mixedintr:seed8:priors", 4),
+                                        ("step:S300:priors:loss=tol100_25", 2), ("step:S300:priors:loss=tol100_25", 4),
+                                        ("step:S300:priors:loss=cauchy10", 2), ("step:S300:priors:loss=cauchy10", 4),
+                                        ("step:S300:perframe:mixedintr:seed8:priors:loss=tol100_25", 2), ("step:S300:perframe:mixedintr:seed8:priors:loss=tol100_25", 4),
+                                        ("step:C2:intr:loss=tol100_25", 2), ("step:C2:intr:loss=tol100_25", 4)])
 def test_sharded_step_matches_the_host_reference(tmp_path, oracle, mode, world):
     """One iteration of the sharded solve against the host reference of the whole problem (tests/lm_step_reference.py), per parameter
     block with the tolerance of tests/test_gpu_lm_step.py: points seen in separator frames only (seed 8 of the mixed layout), blocks
     shared by runs of five frames whose pseudo tiles sit next to a separator, shared intrinsics with Huber; motion priors whose
     (f, f - 1) blocks cross separators (also next to pseudo tiles), a free ratio whose border column is solved part by part,
     GoodPosePrior blocks, the SphericalPrior.  A point owned by the wrong rank leaves the sharded system without its terms: its own
-    step and its frames' steps leave the reference."""
+    step and its frames' steps leave the reference.  With a flag "loss=<key>" every rank sets that loss (tests/test_gpu_loss.py) and
+    the reference is loss_reference.lm_step: under TOLERANT the priors' dense (f, f - 1) blocks cross the separators, and the
+    per-frame intrinsics blocks take the path that keeps records; the regime conditions of tests/test_loss_paths_reference.py are
+    asserted on the whole problem here, in the parent.  Measured on an MI355X under a loss (kappa 4.8e4 - 8.8e4), 2 / 4 ranks:
+    S300 priors tol100_25 0.031 / 0.026, cauchy10 0.028 / 0.053; S300 per-frame mixed intrinsics with priors tol100_25 0.124 / 0.126;
+    C2 shared intrinsics tol100_25 0.019 / 0.024 units."""
     import lm_step_reference as R
-    from dist_worker import nd_problem
+    from dist_worker import loss_of, nd_problem
     from test_lm_step_reference import C_TOL
     res = run_two_ranks(mode, tmp_path, world)
-    full = nd_problem(mode.split(":")[1], mode.split(":")[2:])
-    r, J, ok = oracle.evaluate_blocks(full)
-    assert ok.all()
-    ref = R.lm_step(full, r, J)
+    full, ref = sharded_step_reference(oracle, mode)
     assert ref.kappa <= 1e9
+    if loss_of(mode.split(":")[2:]) is not None:
+        assert full.huber_a == 0.0
     a = res[0]
     assert a["sharded"] == 1 and len(a["trace"]) == 2 and a["trace"][1]["step_is_successful"] == 1
     for o in res[1:]:
@@ -666,24 +700,38 @@ _cov_refs = {}
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 4])
-@pytest.mark.parametrize("mode", ["cov:S300:priors:freeratio", "cov:S300:posepriors", "cov:S300:perframe:mixedintr:seed8", "cov:C2:intr"])
+@pytest.mark.parametrize("mode,world", [(m, w) for m in ("cov:S300:priors:freeratio", "cov:S300:posepriors", "cov:S300:perframe:mixedintr:seed8", "cov:C2:intr") for w in (2, 4)]
+                         + [("cov:S300:priors:freeratio:loss=tol100_25", 2), ("cov:S300:priors:freeratio:loss=tol100_25", 4), ("cov:C2:intr:loss=cauchy10", 2)])
 def test_covariance_on_a_handle_with_an_exchange(tmp_path, oracle, mode, world):
     """rsba_pose_covariance on every rank of a sharded problem: the plan is the sharded one (plan_stats), the call takes its
     replicated form — the whole reduced system summed onto every rank — and puts the sharded form back: every rank's blocks are the
     same bits and within the covariance bound of the extended-precision inverse of the WHOLE problem's J^T J; the frames asked lie
     in a part, in a top separator of the 2-rank and of the 4-rank cut, and at both ends.  One LM iteration after the calls is, bit for
-    bit, the iteration of a handle that never computed a covariance."""
+    bit, the iteration of a handle that never computed a covariance.  With a flag "loss=<key>" every rank sets that loss before the
+    call and the reference is computed under loss_reference.substituted (the replicated form of the covariance under a general
+    loss; the regime conditions asserted on the whole problem).  Measured on an MI355X: S300 priors with a free ratio under
+    tol100_25 0.017 units on 2 and on 4 ranks (kappa^ 7.3e7), C2 shared intrinsics under cauchy10 0.025 on 2 ranks (kappa^ 3.4e7)."""
     import lm_step_reference as R
-    from dist_worker import nd_problem, sharded_cov_frames
+    import loss_reference as L
+    from dist_worker import loss_of, nd_problem, sharded_cov_frames
     from test_lm_step_reference import C_COV, covariance_worst
     res = run_two_ranks(mode, tmp_path, world)
     if mode not in _cov_refs:
-        full = nd_problem(mode.split(":")[1], mode.split(":")[2:])
+        flags = mode.split(":")[2:]
+        full = nd_problem(mode.split(":")[1], flags)
         r, J, ok = oracle.evaluate_blocks(full)
         assert ok.all()
         frames = sharded_cov_frames(full)
-        _cov_refs[mode] = (frames, R.covariance_blocks(full, r, J, frames))
+        loss = loss_of(flags)
+        if loss is None:
+            _cov_refs[mode] = (frames, R.covariance_blocks(full, r, J, frames))
+        else:                                                           # every rank set the loss: the reference under it, the conditions on the case asserted here
+            from test_loss_paths_reference import regime_conditions
+            assert full.huber_a == 0.0
+            lo, hi, curved = regime_conditions(full, r, loss)
+            print(f"{mode}: rho1 < 0.5 on {lo:.3f}, rho1 > 0.9 on {hi:.3f}, rho2 > 1e-6 on {curved:.3f} of the blocks that take the loss")
+            with L.substituted(loss):
+                _cov_refs[mode] = (frames, R.covariance_blocks(L._with_loss(full), r, J, frames))
     frames, ref = _cov_refs[mode]
     assert ref.ok
     got = np.load(os.path.join(tmp_path, "rank0.npz"))
