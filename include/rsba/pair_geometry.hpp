@@ -19,7 +19,6 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <map>
 #include <vector>
 
@@ -74,7 +73,7 @@ inline bool dlt(const double* na, const double* nb, const int32_t* idx, int m, d
 }
 
 // the adjugate over the determinant; false: a determinant that is zero or not finite, an inverse that is not finite.  The device evaluates
-// these operations in this order (kernels_homography.hip, contraction off): the inverse feeds the deciding comparison
+// these operations in this order (rsba_amd/csrc/two_view_rules.hpp, contraction off): the inverse feeds the deciding comparison
 inline bool invert(const double H[9], double Hi[9]) {
   const double c0 = H[4] * H[8] - H[5] * H[7], c1 = H[5] * H[6] - H[3] * H[8], c2 = H[3] * H[7] - H[4] * H[6];
   const double det = H[0] * c0 + H[1] * c1 + H[2] * c2;
@@ -291,36 +290,20 @@ inline std::vector<PairGeometry> classifyPairs(const std::vector<EssentialPair>&
     }
   } else if (P > 0 && tv.iterations > 0) {
     const int T = tv.iterations;
-    std::vector<double> cams;
-    auto cam_index = [&](const double* cam) {
-      for (size_t c = 0; c * NUM_CAM_PARAMS < cams.size(); ++c)
-        if (std::memcmp(&cams[c * NUM_CAM_PARAMS], cam, NUM_CAM_PARAMS * sizeof(double)) == 0) return (int32_t)c;
-      cams.insert(cams.end(), cam, cam + NUM_CAM_PARAMS);
-      return (int32_t)(cams.size() / NUM_CAM_PARAMS - 1);
-    };
-    std::vector<int32_t> ia(P), ib(P), offset(P + 1, 0), subsets(P * (size_t)T * 4, 0);
-    std::vector<float> xa, xb;
+    const PairArrays A = pair_arrays(pairs, 4, 4, T, tv.rng_state);
+    const std::vector<int32_t>& offset = A.offset;
     std::vector<double> E(P * 9, 0.0), poses(P * 6, 0.0);
     std::vector<uint8_t> pst(P, 0);
     for (size_t p = 0; p < P; ++p) {
-      const EssentialPair& q = pairs[p];
-      const int n = q.n > 0 ? q.n : 0;
-      ia[p] = cam_index(q.cam_a); ib[p] = cam_index(q.cam_b);
-      offset[p + 1] = offset[p] + n;
-      xa.insert(xa.end(), q.xy_a, q.xy_a + 2 * (size_t)n); xb.insert(xb.end(), q.xy_b, q.xy_b + 2 * (size_t)n);
       pst[p] = essential_results[p].ok ? 1 : 0;
       for (int k = 0; k < 9; ++k) E[p * 9 + k] = essential_results[p].E[k];
       for (int k = 0; k < 6; ++k) poses[p * 6 + k] = essential_results[p].pose_b[k];
-      if (n < 4) continue;   // (an empty result; the call does not read the pair's subsets)
-      const std::vector<int32_t> s = hyp_detail::distinct_subsets(n, 4, T, tv.rng_state);
-      std::copy(s.begin(), s.end(), subsets.begin() + (std::ptrdiff_t)(p * (size_t)T * 4));
     }
-    if (xa.empty()) { xa.assign(2, 0.0f); xb.assign(2, 0.0f); }   // (only empty pairs: the call still wants arrays)
     std::vector<double> H(P * 9, 0.0);
     std::vector<uint8_t> status(P, 0), mask((size_t)offset[P] + 1, 0);
     std::vector<int32_t> winner(P, -1), adopted(P, 0), inl(P, 0), front(P, 0), par(P, 0);
-    hyp_detail::check(rsba_two_view_classify_pairs(device, cams.data(), (int32_t)(cams.size() / NUM_CAM_PARAMS), ia.data(), ib.data(), offset.data(), (int32_t)P, xa.data(), xb.data(),
-                                                   E.data(), poses.data(), pst.data(), subsets.data(), T, tv.threshold_px, tv.refits, cos_min, co.max_tasks_per_launch, H.data(),
+    hyp_detail::check(rsba_two_view_classify_pairs(device, A.cams.data(), A.num_cams(), A.cam_a.data(), A.cam_b.data(), offset.data(), (int32_t)P, A.xy_a.data(), A.xy_b.data(),
+                                                   E.data(), poses.data(), pst.data(), A.subsets.data(), T, tv.threshold_px, tv.refits, cos_min, co.max_tasks_per_launch, H.data(),
                                                    status.data(), winner.data(), adopted.data(), inl.data(), mask.data(), front.data(), par.data()));
     for (size_t p = 0; p < P; ++p) {
       PairGeometry& g = out[p];

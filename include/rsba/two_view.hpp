@@ -143,7 +143,7 @@ inline bool decompose(const double E[9], Candidates& C) {
   return std::isfinite(C.t[0] + C.t[1] + C.t[2]);
 }
 
-// the two deciding comparisons: the device evaluates these operations in this order (kernels_epipolar.hip, contraction off)
+// the two deciding comparisons: the device evaluates these operations in this order (rsba_amd/csrc/two_view_rules.hpp, contraction off)
 inline bool sampson_inlier(const double E[9], double xa, double ya, double xb, double yb, double f2, double thr2, double* d2_out = nullptr) {
   const double l0 = E[0] * xa + E[1] * ya + E[2], l1 = E[3] * xa + E[4] * ya + E[5], l2 = E[6] * xa + E[7] * ya + E[8];
   const double m0 = E[0] * xb + E[3] * yb + E[6], m1 = E[1] * xb + E[4] * yb + E[7];
@@ -607,6 +607,42 @@ struct EssentialPair {
   const double* cam_b = nullptr;
 };
 
+// The arrays of a batched call (rsba_epipolar_ransac_pairs, rsba_two_view_classify_pairs) from the pairs: the cameras by value, each once
+// (the call normalises a run of pairs that share a camera in one launch), the offsets, the concatenated points, and for every pair of at
+// least min_n correspondences its subsets distinct_subsets(n_p, m, T, rng_state) — the draw a single-pair call makes for that pair alone; a
+// smaller pair is an empty result and the call does not read its subsets.
+struct PairArrays {
+  std::vector<double> cams;                // [num_cams][NUM_CAM_PARAMS]
+  std::vector<int32_t> cam_a, cam_b;       // [P] indices into cams
+  std::vector<int32_t> offset;             // [P + 1]
+  std::vector<float> xy_a, xy_b;           // [offset[P]][2] (two zeros where every pair is empty: the call still wants arrays)
+  std::vector<int32_t> subsets;            // [P][T][m]
+  int32_t num_cams() const { return (int32_t)(cams.size() / NUM_CAM_PARAMS); }
+};
+inline PairArrays pair_arrays(const std::vector<EssentialPair>& pairs, int min_n, int m, int T, uint64_t rng_state) {
+  const size_t P = pairs.size();
+  PairArrays A;
+  auto cam_index = [&](const double* cam) {
+    for (size_t c = 0; c * NUM_CAM_PARAMS < A.cams.size(); ++c)
+      if (std::memcmp(&A.cams[c * NUM_CAM_PARAMS], cam, NUM_CAM_PARAMS * sizeof(double)) == 0) return (int32_t)c;
+    A.cams.insert(A.cams.end(), cam, cam + NUM_CAM_PARAMS);
+    return A.num_cams() - 1;
+  };
+  A.cam_a.resize(P); A.cam_b.resize(P); A.offset.assign(P + 1, 0); A.subsets.assign(P * (size_t)T * m, 0);
+  for (size_t p = 0; p < P; ++p) {
+    const EssentialPair& q = pairs[p];
+    const int n = q.n > 0 ? q.n : 0;
+    A.cam_a[p] = cam_index(q.cam_a); A.cam_b[p] = cam_index(q.cam_b);
+    A.offset[p + 1] = A.offset[p] + n;
+    A.xy_a.insert(A.xy_a.end(), q.xy_a, q.xy_a + 2 * (size_t)n); A.xy_b.insert(A.xy_b.end(), q.xy_b, q.xy_b + 2 * (size_t)n);
+    if (n < min_n) continue;
+    const std::vector<int32_t> s = hyp_detail::distinct_subsets(n, m, T, rng_state);
+    std::copy(s.begin(), s.end(), A.subsets.begin() + (std::ptrdiff_t)(p * (size_t)T * m));
+  }
+  if (A.xy_a.empty()) { A.xy_a.assign(2, 0.0f); A.xy_b.assign(2, 0.0f); }
+  return A;
+}
+
 // findEssentialRansac for every pair, result p what findEssentialRansac(pairs[p]..., opt, device) returns: pair p's subsets are
 // distinct_subsets(n_p, m, opt.iterations, opt.rng_state), the draw the single call makes for that pair alone, and the loop per pair is
 // epi_detail::ransac, kept on the device by rsba_epipolar_ransac_pairs — one upload, one download, the hypothesis kernels launched over the
@@ -622,35 +658,13 @@ inline std::vector<TwoViewResult> findEssentialRansacPairs(const std::vector<Ess
   if (pairs.empty() || opt.iterations <= 0) return out;
   const int T = opt.iterations, m = opt.solver == TwoViewOptions::EssentialSolver::FivePoint ? 5 : 8;
   const size_t P = pairs.size();
-  // the cameras by value, each once: the call normalises a run of pairs that share a camera in one launch
-  std::vector<double> cams;
-  auto cam_index = [&](const double* cam) {
-    for (size_t c = 0; c * NUM_CAM_PARAMS < cams.size(); ++c) {
-      bool same = true;
-      for (int k = 0; k < NUM_CAM_PARAMS; ++k) same = same && std::memcmp(&cams[c * NUM_CAM_PARAMS + k], &cam[k], sizeof(double)) == 0;
-      if (same) return (int32_t)c;
-    }
-    cams.insert(cams.end(), cam, cam + NUM_CAM_PARAMS);
-    return (int32_t)(cams.size() / NUM_CAM_PARAMS - 1);
-  };
-  std::vector<int32_t> ia(P), ib(P), offset(P + 1, 0), subsets(P * (size_t)T * m, 0);
-  std::vector<float> xa, xb;
-  for (size_t p = 0; p < P; ++p) {
-    const EssentialPair& q = pairs[p];
-    const int n = q.n > 0 ? q.n : 0;
-    ia[p] = cam_index(q.cam_a); ib[p] = cam_index(q.cam_b);
-    offset[p + 1] = offset[p] + n;
-    xa.insert(xa.end(), q.xy_a, q.xy_a + 2 * (size_t)n); xb.insert(xb.end(), q.xy_b, q.xy_b + 2 * (size_t)n);
-    if (n < 8) continue;   // (an empty result; the call does not read the pair's subsets)
-    const std::vector<int32_t> s = hyp_detail::distinct_subsets(n, m, T, opt.rng_state);
-    std::copy(s.begin(), s.end(), subsets.begin() + (std::ptrdiff_t)(p * (size_t)T * m));
-  }
-  if (xa.empty()) { xa.assign(2, 0.0f); xb.assign(2, 0.0f); }   // (only empty pairs: the call still wants arrays)
+  const PairArrays A = pair_arrays(pairs, 8, m, T, opt.rng_state);
+  const std::vector<int32_t>& offset = A.offset;
   std::vector<double> E(P * 9, 0.0), poses(P * 6, 0.0);
   std::vector<uint8_t> status(P, 0), mask((size_t)offset[P] + 1, 0);
   std::vector<int32_t> winner(P, -1), adopted(P, 0), inl(P, 0), front(P * 4, 0);
-  hyp_detail::check(rsba_epipolar_ransac_pairs(device, cams.data(), (int32_t)(cams.size() / NUM_CAM_PARAMS), ia.data(), ib.data(), offset.data(), (int32_t)P, xa.data(), xb.data(),
-                                               subsets.data(), m, T, opt.threshold_px, opt.refits, max_tasks_per_launch, E.data(), poses.data(), status.data(), winner.data(),
+  hyp_detail::check(rsba_epipolar_ransac_pairs(device, A.cams.data(), A.num_cams(), A.cam_a.data(), A.cam_b.data(), offset.data(), (int32_t)P, A.xy_a.data(), A.xy_b.data(),
+                                               A.subsets.data(), m, T, opt.threshold_px, opt.refits, max_tasks_per_launch, E.data(), poses.data(), status.data(), winner.data(),
                                                adopted.data(), inl.data(), front.data(), mask.data()));
   for (size_t p = 0; p < P; ++p) {
     TwoViewResult& r = out[p];

@@ -1,5 +1,5 @@
-// What the C-ABI entry points share on the host (capi.hip, pnp_capi.hip, epipolar_capi.hip, match_capi.hip, tracks_capi.hip, filter_capi.hip
-// and, through solver.hpp, the solver's units): a HIP error turned into the library's error code and message, the check of the device
+// What the C-ABI entry points share on the host (capi.hip, pnp_capi.hip, match_capi.hip, tracks_capi.hip, filter_capi.hip, through
+// pair_capi_util.hpp epipolar_capi.hip and homography_capi.hip, and, through solver.hpp, the solver's units): a HIP error turned into the library's error code and message, the check of the device
 // ordinal, the device buffers of a stateless call and the copy of its accepted results to the caller.  Host-side glue only; private to the
 // library: nothing here is part of its surface.
 #pragma once

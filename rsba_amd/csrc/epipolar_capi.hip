@@ -1,7 +1,8 @@
 // C-ABI of the two-view bootstrap (include/rsba_amd.h: rsba_epipolar_eight_point, rsba_epipolar_score, rsba_epipolar_hypotheses,
-// rsba_epipolar_inliers, rsba_epipolar_five_point, rsba_epipolar_hypotheses_five_point, rsba_epipolar_ransac_pairs).  Host-side glue only: argument checks (the codes
-// rsba_pnp_dlt returns for the same mistakes), staging of the caller's arrays and the launches; every number comes from kernels_epipolar.hip,
-// kernels_five_point.hip and pnp_normalise_kernel (kernels_pnp_dlt.hip).
+// rsba_epipolar_inliers, rsba_epipolar_five_point, rsba_epipolar_hypotheses_five_point, rsba_epipolar_ransac_pairs).  Host-side glue only:
+// argument checks (the codes rsba_pnp_dlt returns for the same mistakes), staging of the caller's arrays and the launches; what it shares with
+// homography_capi.hip is pair_capi_util.hpp.  Every number comes from kernels_epipolar.hip, kernels_five_point.hip and pnp_normalise_kernel
+// (kernels_pnp_dlt.hip).
 #include "../../include/rsba_amd.h"
 
 #include <algorithm>
@@ -9,49 +10,16 @@
 #include <string>
 #include <vector>
 
-#include "capi_util.hpp"
 #include "epipolar_state.hpp"
-#include "pnp_state.hpp"
+#include "pair_capi_util.hpp"
 
 using namespace rsba;
 
 namespace {
 
-int32_t check_points(const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
-  if (!cam_a || !cam_b || !xy_a || !xy_b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if (n < 8) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (an essential matrix takes at least 8 correspondences)");
-  return RSBA_OK;
-}
-int32_t check_subsets(int32_t n, const int32_t* subsets, int32_t m, int32_t num_tasks) {
-  if (!subsets) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if (m < 8 || n < m || num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (an eight-point subset has at least 8 correspondences, n >= m)");
-  for (size_t k = 0; k < (size_t)num_tasks * m; ++k)
-    if (subsets[k] < 0 || subsets[k] >= n) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "subset index out of range");
-  return RSBA_OK;
-}
-
-// both frames' points uploaded, undistorted and normalised (pnp_normalise_kernel, once per side)
-struct Normalised { double* na = nullptr; double* nb = nullptr; };
-int32_t normalise_both(DeviceBuffers& B, Normalised& N, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
-  const double* cams[2] = {cam_a, cam_b};
-  const float* xy[2] = {xy_a, xy_b};
-  double** out[2] = {&N.na, &N.nb};
-  for (int side = 0; side < 2; ++side) {
-    PnpDltArgs D{};
-    for (int k = 0; k < 9; ++k) D.cam[k] = cams[side][k];
-    D.n = n;
-    RSBA_HIP_TRY(B.upload(&D.image_points, xy[side], (size_t)n * 2));
-    RSBA_HIP_TRY(B.alloc(&D.normalised, (size_t)n * 2));
-    RSBA_HIP_TRY(launch_pnp_normalise(D, nullptr));
-    *out[side] = D.normalised;
-  }
-  return RSBA_OK;
-}
-
-double mean_focal2(const double* cam_a, const double* cam_b) {
-  const double f = (cam_a[0] + cam_a[1] + cam_b[0] + cam_b[1]) / 4.0;
-  return f * f;
-}
+constexpr const char* kTooFewPoints = "bad sizes (an essential matrix takes at least 8 correspondences)";
+constexpr const char* kBadSubsets = "bad sizes (an eight-point subset has at least 8 correspondences, n >= m)";
+constexpr const char* kTooFewPointsFive = "bad sizes (the five-point solver takes at least 5 correspondences)";
 
 int32_t run_eight_point(DeviceBuffers& B, EpiEightArgs& A, const Normalised& N, int32_t n, const int32_t* subsets, int32_t m, int32_t num_tasks) {
   A.n = n; A.m = m; A.num_tasks = num_tasks; A.na = N.na; A.nb = N.nb;
@@ -87,10 +55,10 @@ int32_t download_score(const EpiScoreArgs& S, int32_t num_tasks, int32_t* num_in
 
 extern "C" int32_t rsba_epipolar_eight_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                              const int32_t* subsets, int32_t m, int32_t num_tasks, double* E_out, uint8_t* status) {
-  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 8, kTooFewPoints);
   if (rc) return rc;
   if (!E_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
+  if ((rc = check_subsets(n, subsets, m, num_tasks, 8, kBadSubsets))) return rc;
   if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
@@ -104,7 +72,7 @@ extern "C" int32_t rsba_epipolar_eight_point(int32_t device, const double* cam_a
 extern "C" int32_t rsba_epipolar_score(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                        const double* E, int32_t num_tasks, double threshold_px, int32_t* num_inliers, int32_t* num_front,
                                        double* poses_out, uint8_t* status) {
-  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 8, kTooFewPoints);
   if (rc) return rc;
   if (!E || !num_inliers || !num_front || !poses_out || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if (num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_tasks <= 0)");
@@ -122,10 +90,10 @@ extern "C" int32_t rsba_epipolar_score(int32_t device, const double* cam_a, cons
 extern "C" int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                             const int32_t* subsets, int32_t m, int32_t num_tasks, double threshold_px, double* E_out, double* poses_out,
                                             uint8_t* status, int32_t* num_inliers, int32_t* num_front) {
-  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 8, kTooFewPoints);
   if (rc) return rc;
   if (!E_out || !poses_out || !status || !num_inliers || !num_front) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = check_subsets(n, subsets, m, num_tasks))) return rc;
+  if ((rc = check_subsets(n, subsets, m, num_tasks, 8, kBadSubsets))) return rc;
   if ((rc = rsba_select_device(device))) return rc;
   DeviceBuffers B;
   Normalised N;
@@ -142,7 +110,7 @@ extern "C" int32_t rsba_epipolar_hypotheses(int32_t device, const double* cam_a,
 
 extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                          const double* E, double threshold_px, uint8_t* inlier_mask) {
-  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 8, kTooFewPoints);
   if (rc) return rc;
   if (!E || !inlier_mask) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if ((rc = rsba_select_device(device))) return rc;
@@ -162,11 +130,6 @@ extern "C" int32_t rsba_epipolar_inliers(int32_t device, const double* cam_a, co
 // ---- the five-point solver beside the eight-point: the same order of argument checks, n >= 5, exactly five indices per subset ----
 namespace {
 
-int32_t check_points_five(const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n) {
-  if (!cam_a || !cam_b || !xy_a || !xy_b) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
-  if (n < 5) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (the five-point solver takes at least 5 correspondences)");
-  return RSBA_OK;
-}
 int32_t check_subsets_five(int32_t n, const int32_t* subsets, int32_t num_tasks) {
   if (!subsets) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if (num_tasks <= 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_tasks <= 0)");
@@ -191,7 +154,7 @@ int32_t run_five_point(DeviceBuffers& B, EpiFiveArgs& F, const Normalised& N, in
 
 extern "C" int32_t rsba_epipolar_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                             const int32_t* subsets, int32_t num_tasks, double* E_out, int32_t* num_solutions, uint8_t* status) {
-  int32_t rc = check_points_five(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 5, kTooFewPointsFive);
   if (rc) return rc;
   if (!E_out || !num_solutions || !status) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if ((rc = check_subsets_five(n, subsets, num_tasks))) return rc;
@@ -216,7 +179,7 @@ extern "C" int32_t rsba_epipolar_five_point(int32_t device, const double* cam_a,
 extern "C" int32_t rsba_epipolar_hypotheses_five_point(int32_t device, const double* cam_a, const double* cam_b, const float* xy_a, const float* xy_b, int32_t n,
                                                        const int32_t* subsets, int32_t num_tasks, double threshold_px, double* E_out, double* poses_out,
                                                        uint8_t* status, int32_t* num_inliers, int32_t* num_front, int32_t* num_solutions) {
-  int32_t rc = check_points_five(cam_a, cam_b, xy_a, xy_b, n);
+  int32_t rc = check_points(cam_a, cam_b, xy_a, xy_b, n, 5, kTooFewPointsFive);
   if (rc) return rc;
   if (!E_out || !poses_out || !status || !num_inliers || !num_front) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "null argument");
   if ((rc = check_subsets_five(n, subsets, num_tasks))) return rc;
@@ -248,31 +211,8 @@ extern "C" int32_t rsba_epipolar_hypotheses_five_point(int32_t device, const dou
 }
 
 // ---- the RANSAC of many frame pairs in one call: the hypothesis kernels above over the concatenated points, the loop of
-// epi_detail::ransac per pair kept on the device (kernels_epipolar.hip: winner, masks, ordered compaction, adopt) ----
-namespace {
-
-constexpr int32_t kDefaultTasksPerLaunch = 65536;   // five-point scratch is about 1.5 KB per task: 100 MB at this budget
-
-// one side of every pair normalised by its own camera: pnp_normalise_kernel itself (the kernel the single-pair calls run, so the same
-// bytes), once per run of consecutive pairs that share the camera — a session with one camera takes one launch per side
-int32_t normalise_pairs(const double* cams, const int32_t* pair_cam, const int32_t* pair_offset, int32_t num_pairs, const float* d_xy, double* d_out) {
-  for (int32_t p = 0; p < num_pairs;) {
-    int32_t q = p + 1;
-    while (q < num_pairs && pair_cam[q] == pair_cam[p]) ++q;
-    const int32_t first = pair_offset[p], count = pair_offset[q] - first;
-    if (count > 0) {
-      PnpDltArgs D{};
-      for (int k = 0; k < 9; ++k) D.cam[k] = cams[(size_t)pair_cam[p] * 9 + k];
-      D.n = count; D.image_points = d_xy + 2 * (size_t)first; D.normalised = d_out + 2 * (size_t)first;
-      RSBA_HIP_TRY(launch_pnp_normalise(D, nullptr));
-    }
-    p = q;
-  }
-  return RSBA_OK;
-}
-
-}  // namespace
-
+// epi_detail::ransac per pair kept on the device.  The staging and the loop are pair_capi_util.hpp's and kernels_pair_loop.hip's, shared with
+// the homography; here, what is the essential matrix's own: the two hypothesis stages, the pose and the front counts ----
 extern "C" int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams, int32_t num_cams, const int32_t* pair_cam_a, const int32_t* pair_cam_b,
                                               const int32_t* pair_offset, int32_t num_pairs, const float* xy_a, const float* xy_b, const int32_t* subsets, int32_t m,
                                               int32_t tasks_per_pair, double threshold_px, int32_t refits, int32_t max_tasks_per_launch, double* E_out, double* poses_out,
@@ -283,69 +223,14 @@ extern "C" int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams
   if (num_cams <= 0 || num_pairs <= 0 || tasks_per_pair <= 0 || refits < 0 || max_tasks_per_launch < 0)
     return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (num_cams, num_pairs, tasks_per_pair > 0; refits, max_tasks_per_launch >= 0)");
   if (m != 5 && m != 8) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (m is 5, five-point subsets, or 8, eight-point subsets)");
-  if (pair_offset[0] != 0) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "pair_offset[0] is not 0");
-  for (int32_t p = 0; p < num_pairs; ++p) {
-    if (pair_offset[p + 1] < pair_offset[p]) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "pair_offset decreases");
-    if (pair_cam_a[p] < 0 || pair_cam_a[p] >= num_cams || pair_cam_b[p] < 0 || pair_cam_b[p] >= num_cams)
-      return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "camera index out of range");
-  }
-  const int32_t budget = max_tasks_per_launch ? max_tasks_per_launch : kDefaultTasksPerLaunch;
-  const int32_t chunk_pairs = std::min<int64_t>(num_pairs, std::max<int64_t>(1, budget / tasks_per_pair));   // whole pairs; a pair above the budget is a chunk of its own
-  if ((int64_t)chunk_pairs * tasks_per_pair * 10 > INT32_MAX) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (tasks per launch)");
-  const size_t per_pair = (size_t)tasks_per_pair * m, points = (size_t)pair_offset[num_pairs];
-  // pair-local indices to indices of the concatenated points; a pair under 8 correspondences gets the repeated index 0, which every
-  // hypothesis kernel declines before it reads a point, and its part of the caller's array is not read
-  std::vector<int32_t> global((size_t)num_pairs * per_pair, 0);
-  std::vector<EpiPair> table((size_t)num_pairs);
-  std::vector<int32_t> starts((size_t)num_pairs), point_pair(points);
-  for (int32_t p = 0; p < num_pairs; ++p) {
-    const int32_t first = pair_offset[p], n = pair_offset[p + 1] - first;
-    table[(size_t)p] = EpiPair{first, n, mean_focal2(cams + 9 * (size_t)pair_cam_a[p], cams + 9 * (size_t)pair_cam_b[p])};
-    starts[(size_t)p] = first;
-    for (int32_t i = 0; i < n; ++i) point_pair[(size_t)first + i] = p % chunk_pairs;   // the pair's index within its chunk
-    if (n < 8) continue;
-    for (size_t k = 0; k < per_pair; ++k) {
-      const int32_t s = subsets[(size_t)p * per_pair + k];
-      if (s < 0 || s >= n) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "subset index out of range");
-      global[(size_t)p * per_pair + k] = first + s;
-    }
-  }
-  int32_t rc = rsba_select_device(device);
+  int32_t rc = check_pair_table(num_cams, pair_cam_a, pair_cam_b, pair_offset, num_pairs);
   if (rc) return rc;
-
-  // ---- one upload ----
-  DeviceBuffers B;
-  const float* d_xy[2] = {nullptr, nullptr};
-  double* d_n[2] = {nullptr, nullptr};
-  const int32_t* d_subsets = nullptr; const int32_t* d_starts = nullptr; const int32_t* d_point_pair = nullptr;
-  const EpiPair* d_table = nullptr;
-  RSBA_HIP_TRY(B.upload(&d_xy[0], xy_a, points * 2));
-  RSBA_HIP_TRY(B.upload(&d_xy[1], xy_b, points * 2));
-  RSBA_HIP_TRY(B.alloc(&d_n[0], points * 2));
-  RSBA_HIP_TRY(B.alloc(&d_n[1], points * 2));
-  RSBA_HIP_TRY(B.upload(&d_subsets, global.data(), global.size()));
-  RSBA_HIP_TRY(B.upload(&d_starts, starts.data(), starts.size()));
-  RSBA_HIP_TRY(B.upload(&d_point_pair, point_pair.data(), point_pair.size()));
-  RSBA_HIP_TRY(B.upload(&d_table, table.data(), table.size()));
-  if ((rc = normalise_pairs(cams, pair_cam_a, pair_offset, num_pairs, d_xy[0], d_n[0]))) return rc;
-  if ((rc = normalise_pairs(cams, pair_cam_b, pair_offset, num_pairs, d_xy[1], d_n[1]))) return rc;
-
-  // the state of the loop, every pair's; a chunk works on its slice
-  EpiPairState all{};
-  RSBA_HIP_TRY(B.alloc(&all.E, (size_t)num_pairs * 9));
-  RSBA_HIP_TRY(B.alloc(&all.pose, (size_t)num_pairs * 6));
-  RSBA_HIP_TRY(B.alloc(&all.num_inliers, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.num_front, (size_t)num_pairs * 4));
-  RSBA_HIP_TRY(B.alloc(&all.winner_task, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.refits_adopted, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.status, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.done, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.inlier_count, (size_t)num_pairs));
-  RSBA_HIP_TRY(B.alloc(&all.mask, points));
-  RSBA_HIP_TRY(B.alloc(&all.inlier_idx, points));
-  RSBA_HIP_TRY(hipMemset(all.E, 0, (size_t)num_pairs * 9 * sizeof(double)));
-  RSBA_HIP_TRY(hipMemset(all.pose, 0, (size_t)num_pairs * 6 * sizeof(double)));
-  RSBA_HIP_TRY(hipMemset(all.mask, 0, points ? points : 1));
+  const int32_t chunk_pairs = pairs_per_launch(num_pairs, tasks_per_pair, max_tasks_per_launch);
+  if ((int64_t)chunk_pairs * tasks_per_pair * 10 > INT32_MAX) return rsba_set_error(RSBA_ERR_INVALID_ARGUMENT, "bad sizes (tasks per launch)");
+  PairStaging G;
+  if ((rc = stage_pairs(G, device, cams, pair_cam_a, pair_cam_b, pair_offset, num_pairs, xy_a, xy_b, subsets, m, tasks_per_pair, chunk_pairs, 8))) return rc;
+  if ((rc = alloc_pair_loop(G, true))) return rc;
+  DeviceBuffers& B = G.B;
 
   // scratch of the largest chunk: the hypotheses of its tasks (five-point: ten slots per task), the refit of its pairs
   const size_t T = (size_t)chunk_pairs * tasks_per_pair, slots = m == 5 ? T * 10 : T;
@@ -355,9 +240,9 @@ extern "C" int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams
   EpiPickArgs K{};
   EpiEightArgs RA{};
   EpiScoreArgs RS{};
-  A.na = F.na = S.na = RA.na = RS.na = d_n[0];
-  A.nb = F.nb = S.nb = RA.nb = RS.nb = d_n[1];
-  A.n = F.n = RA.n = (int)points;
+  A.na = F.na = S.na = RA.na = RS.na = G.na;
+  A.nb = F.nb = S.nb = RA.nb = RS.nb = G.nb;
+  A.n = F.n = RA.n = (int)G.points;
   S.thr2 = RS.thr2 = threshold_px * threshold_px;
   if (m == 5) {
     RSBA_HIP_TRY(B.alloc(&F.E_out, T * 90));
@@ -389,65 +274,48 @@ extern "C" int32_t rsba_epipolar_ransac_pairs(int32_t device, const double* cams
   RSBA_HIP_TRY(B.alloc(&RS.poses_out, (size_t)chunk_pairs * 6));
   RSBA_HIP_TRY(B.alloc(&RS.status, (size_t)chunk_pairs));
 
-  // ---- per chunk a fixed sequence of launches, nothing read back between them ----
   for (int32_t p0 = 0; p0 < num_pairs; p0 += chunk_pairs) {
-    const int32_t np = std::min(chunk_pairs, num_pairs - p0), tasks = np * tasks_per_pair;
-    const int32_t first_point = pair_offset[p0], num_points = pair_offset[p0 + np] - first_point;
-    EpiPairState C = all;
-    C.num_pairs = np; C.pairs = d_table + p0;
-    C.E += (size_t)p0 * 9; C.pose += (size_t)p0 * 6; C.num_inliers += p0; C.num_front += (size_t)p0 * 4; C.winner_task += p0; C.refits_adopted += p0;
-    C.status += p0; C.done += p0; C.inlier_count += p0;
-    S.pairs = RS.pairs = C.pairs;
-    EpiWinnerArgs W{};
-    W.S = C; W.tasks_per_pair = tasks_per_pair; W.front_breaks_ties = m == 5 ? 1 : 0;
+    const PairChunk C = pair_chunk(G, p0);
+    const int32_t tasks = C.np * tasks_per_pair;
+    S.pairs = RS.pairs = C.S.pairs;
+    WinnerArgs W{};
+    W.tasks_per_pair = tasks_per_pair; W.front_breaks_ties = m == 5 ? 1 : 0;
     if (m == 5) {
-      F.num_tasks = tasks; F.subsets = d_subsets + (size_t)p0 * per_pair;
+      F.num_tasks = tasks; F.subsets = G.subsets + (size_t)p0 * G.per_pair;
       RSBA_HIP_TRY(launch_epipolar_five_point(F, nullptr));
       S.num_tasks = tasks * 10;
       RSBA_HIP_TRY(launch_epipolar_score(S, nullptr));
       K.num_tasks = tasks;
       RSBA_HIP_TRY(launch_epipolar_pick(K, nullptr));
-      W.status = K.status; W.num_inliers = K.num_inliers; W.num_front = K.num_front; W.E = K.E_out; W.poses = K.poses_out;
+      W.status = K.status; W.num_inliers = K.num_inliers; W.num_front = K.num_front; W.models = K.E_out; W.poses = K.poses_out;
     } else {
-      A.num_tasks = tasks; A.subsets = d_subsets + (size_t)p0 * per_pair;
+      A.num_tasks = tasks; A.subsets = G.subsets + (size_t)p0 * G.per_pair;
       RSBA_HIP_TRY(launch_epipolar_eight_point(A, nullptr));
       S.num_tasks = tasks;
       RSBA_HIP_TRY(launch_epipolar_score(S, nullptr));
-      W.status = S.status; W.num_inliers = S.num_inliers; W.num_front = S.num_front; W.E = A.E_out; W.poses = S.poses_out;
+      W.status = S.status; W.num_inliers = S.num_inliers; W.num_front = S.num_front; W.models = A.E_out; W.poses = S.poses_out;
     }
-    RSBA_HIP_TRY(launch_epipolar_winner(W, nullptr));
-    RSBA_HIP_TRY(launch_epipolar_pair_masks(C, d_point_pair, first_point, num_points, S.thr2, d_n[0], d_n[1], nullptr));
-    RA.num_tasks = RS.num_tasks = np; RA.subsets = C.inlier_idx; RA.sub_start = d_starts + p0; RA.sub_count = C.inlier_count;
-    EpiAdoptArgs D{};
-    D.S = C; D.status = RS.status; D.num_inliers = RS.num_inliers; D.num_front = RS.num_front; D.E = RA.E_out; D.poses = RS.poses_out;
-    for (int32_t round = 0; round < refits; ++round) {   // every round is launched: a pair that is done is skipped by the kernels
-      RSBA_HIP_TRY(launch_epipolar_compact(C, nullptr));
+    RA.num_tasks = RS.num_tasks = C.np; RA.subsets = C.S.inlier_idx; RA.sub_start = G.starts + p0; RA.sub_count = C.S.inlier_count;
+    AdoptArgs D{};
+    D.status = RS.status; D.num_inliers = RS.num_inliers; D.num_front = RS.num_front; D.models = RA.E_out; D.poses = RS.poses_out;
+    rc = run_pair_loop(G, C, W, D, PairRule::Sampson, 8, refits, S.thr2, [&]() -> int32_t {
       RSBA_HIP_TRY(launch_epipolar_eight_point(RA, nullptr));
       RSBA_HIP_TRY(launch_epipolar_score(RS, nullptr));
-      RSBA_HIP_TRY(launch_epipolar_adopt(D, nullptr));
-      RSBA_HIP_TRY(launch_epipolar_pair_masks(C, d_point_pair, first_point, num_points, S.thr2, d_n[0], d_n[1], nullptr));
-    }
+      return RSBA_OK;
+    });
+    if (rc) return rc;
   }
 
   // ---- one download; E and the pose of a pair without a winner stay the caller's ----
-  std::vector<double> e((size_t)num_pairs * 9), ps((size_t)num_pairs * 6);
-  std::vector<uint8_t> st((size_t)num_pairs), mask(points);
-  std::vector<int32_t> win((size_t)num_pairs), adopted((size_t)num_pairs), inl((size_t)num_pairs), front((size_t)num_pairs * 4);
-  RSBA_HIP_TRY(hipMemcpy(e.data(), all.E, e.size() * sizeof(double), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(ps.data(), all.pose, ps.size() * sizeof(double), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(st.data(), all.status, st.size(), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(win.data(), all.winner_task, win.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(adopted.data(), all.refits_adopted, adopted.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(inl.data(), all.num_inliers, inl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  RSBA_HIP_TRY(hipMemcpy(front.data(), all.num_front, front.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (points) RSBA_HIP_TRY(hipMemcpy(mask.data(), all.mask, points, hipMemcpyDeviceToHost));
+  std::vector<double> ps((size_t)num_pairs * 6);
+  std::vector<int32_t> front((size_t)num_pairs * 4);
+  std::vector<uint8_t> st;
+  RSBA_HIP_TRY(hipMemcpy(ps.data(), G.all.pose, ps.size() * sizeof(double), hipMemcpyDeviceToHost));
+  RSBA_HIP_TRY(hipMemcpy(front.data(), G.all.num_front, front.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if ((rc = download_pairs(G, status, winner_task, refits_adopted, num_inliers, inlier_mask, E_out, st))) return rc;
   for (size_t p = 0; p < (size_t)num_pairs; ++p) {
-    status[p] = st[p]; winner_task[p] = win[p]; refits_adopted[p] = adopted[p]; num_inliers[p] = inl[p];
     for (int c = 0; c < 4; ++c) num_front[p * 4 + c] = front[p * 4 + c];
-    if (!st[p]) continue;
-    for (int k = 0; k < 9; ++k) E_out[p * 9 + k] = e[p * 9 + k];
-    for (int k = 0; k < 6; ++k) poses_out[p * 6 + k] = ps[p * 6 + k];
+    if (st[p]) for (int k = 0; k < 6; ++k) poses_out[p * 6 + k] = ps[p * 6 + k];
   }
-  for (size_t i = 0; i < points; ++i) inlier_mask[i] = mask[i];
   return RSBA_OK;
 }

@@ -1,7 +1,10 @@
-// Arguments of the two-view kernels (kernels_epipolar.hip, kernels_five_point.hip); all pointers are device pointers.
+// Arguments of the two-view kernels (kernels_epipolar.hip, kernels_five_point.hip); all pointers are device pointers.  The loop of the batched
+// call around them is pair_loop_state.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+
+#include "pair_loop_state.hpp"   // PairRange
 
 namespace rsba {
 
@@ -18,11 +21,10 @@ struct EpiEightArgs {
 };
 
 // epipolar_score_kernel
-struct EpiPair { int32_t start, n; double f2; };   // one frame pair of a batched call: its range of the concatenated points, its (mean focal length)^2
 struct EpiScoreArgs {
   int n, num_tasks;
   double f2, thr2;               // (mean focal length)^2, threshold_px^2
-  const EpiPair* pairs;          // null: every task counts over [0, n) with f2.  Else task t belongs to pairs[t / tasks_per_pair] and counts over
+  const PairRange* pairs;        // null: every task counts over [0, n) with f2.  Else task t belongs to pairs[t / tasks_per_pair] and counts over
   int tasks_per_pair;            //   that pair's range with that pair's f2 (n and f2 above are not read)
   const double* na;              // [n][2]
   const double* nb;              // [n][2]
@@ -60,51 +62,6 @@ struct EpiPickArgs {
   int32_t* num_front;            // [num_tasks][4]
   uint8_t* status;               // [num_tasks] 0: no slot that the score accepted
 };
-
-// ---- the batched RANSAC of many frame pairs (rsba_epipolar_ransac_pairs): the state of the loop per pair, and the kernels around the
-// hypothesis kernels above that keep the loop on the device
-struct EpiPairState {
-  int num_pairs;                 // of this launch (a chunk); every array below is indexed by the chunk's pair, every range by EpiPair::start
-  const EpiPair* pairs;          // [num_pairs]
-  double* E;                     // [num_pairs][9] the current matrix
-  double* pose;                  // [num_pairs][6]
-  int32_t* num_inliers;          // [num_pairs]
-  int32_t* num_front;            // [num_pairs][4]
-  int32_t* winner_task;          // [num_pairs] -1: no accepted hypothesis
-  int32_t* refits_adopted;       // [num_pairs]
-  uint8_t* status;               // [num_pairs] 1: the pair has a winner
-  uint8_t* done;                 // [num_pairs] 1: no (further) refit — no winner, fewer than 8 inliers, or a refit that was not adopted
-  uint8_t* mask;                 // [points] inlier flags of the current matrix (zero for a pair without a winner)
-  int32_t* inlier_idx;           // [points] per pair, from its start: the ascending (global) indices of its inliers
-  int32_t* inlier_count;         // [num_pairs] their number; 0 for a pair that is done
-};
-// epipolar_winner_kernel: per pair the best of its tasks_per_pair scored hypotheses — most inliers, with front_breaks_ties the most in front
-// (over the four candidates) next, then the lowest task
-struct EpiWinnerArgs {
-  EpiPairState S;
-  int tasks_per_pair, front_breaks_ties;
-  const uint8_t* status;         // [num_pairs][tasks_per_pair]
-  const int32_t* num_inliers;    // [num_pairs][tasks_per_pair]
-  const int32_t* num_front;      // [num_pairs][tasks_per_pair][4]
-  const double* E;               // [num_pairs][tasks_per_pair][9]
-  const double* poses;           // [num_pairs][tasks_per_pair][6]
-};
-// epipolar_adopt_kernel: the refit of each pair (one task per pair), adopted iff accepted and its count is not lower
-struct EpiAdoptArgs {
-  EpiPairState S;
-  const uint8_t* status;         // [num_pairs] the score kernel's
-  const int32_t* num_inliers;    // [num_pairs]
-  const int32_t* num_front;      // [num_pairs][4]
-  const double* E;               // [num_pairs][9]
-  const double* poses;           // [num_pairs][6]
-};
-hipError_t launch_epipolar_winner(const EpiWinnerArgs& args, hipStream_t st);
-// mask[i] of every correspondence of the pairs that are not done, from its pair's current E; first_point / num_points: the chunk's range,
-// point_pair [points]: the chunk's pair of each correspondence
-hipError_t launch_epipolar_pair_masks(const EpiPairState& S, const int32_t* point_pair, int first_point, int num_points, double thr2, const double* na, const double* nb, hipStream_t st);
-// inlier_idx / inlier_count from mask, in ascending order; a pair with fewer than 8 inliers becomes done
-hipError_t launch_epipolar_compact(const EpiPairState& S, hipStream_t st);
-hipError_t launch_epipolar_adopt(const EpiAdoptArgs& args, hipStream_t st);
 
 hipError_t launch_epipolar_five_point(const EpiFiveArgs& args, hipStream_t st);
 hipError_t launch_epipolar_pick(const EpiPickArgs& args, hipStream_t st);

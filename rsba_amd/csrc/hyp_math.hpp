@@ -1,4 +1,4 @@
-// The small algebra the hypothesis kernels share (kernels_pnp_dlt.hip, kernels_pnp_p3p.hip, kernels_epipolar.hip): the device restatement of
+// The small algebra the hypothesis kernels share (kernels_pnp_dlt.hip, kernels_pnp_p3p.hip, kernels_epipolar.hip, kernels_homography.hip): the device restatement of
 // include/rsba/hyp_host.hpp's hyp_detail::rotate, pose_from_rt, eigen3 and smallest_eigenvector12, which solve_rs_pnp.hpp and two_view.hpp call
 // alike.  The host functions are the definition; fp64 throughout, every loop with the host's fixed bound (40 / 60 Jacobi sweeps).  No anonymous
 // namespace: a tool that includes two kernel files into one translation unit sees one definition.

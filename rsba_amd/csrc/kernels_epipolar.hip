@@ -16,17 +16,12 @@
 // The RANSAC of many frame pairs in one call (rsba_epipolar_ransac_pairs) runs the two kernels above over the concatenated points of all
 // pairs — the eight-point kernel with an optional list per task (the refits, one lane per pair), the score kernel with an optional pair
 // table (a task counts over its pair's range with its pair's focal length) — so that a pair's numbers are rounded by the code that rounds
-// them in the single-pair calls.  Around them, integers and copies only:
-//   epipolar_winner_kernel       one wave per pair over its tasks: the key (inliers, most in front) as one integer, its maximum and then
-//                                the lowest task that reaches it, each by a butterfly over the wave
-//   epipolar_pair_masks_kernel   one lane per correspondence: the inlier flag by its pair's current E
-//   epipolar_compact_kernel      one wave per pair: the ascending inlier indices by ballot and the popcount of the lower lanes
-//   epipolar_adopt_kernel        one lane per pair: a refit adopted iff accepted and its count is not lower; else the pair is done
+// them in the single-pair calls.  The loop around them (winner, masks, compaction, adopt) is kernels_pair_loop.hip, shared with the
+// homography; the two deciding comparisons, sampson_inlier and in_front, are two_view_rules.hpp's.
 // An eight-point lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
-#include <climits>
-
 #include "epipolar_state.hpp"
 #include "hyp_math.hpp"
+#include "two_view_rules.hpp"
 
 namespace rsba {
 
@@ -150,27 +145,6 @@ __global__ __launch_bounds__(kEpiBlock) void epipolar_eight_point_kernel(const E
   A.status[t] = 1;
 }
 
-// the two deciding comparisons: the operations of epi_detail::sampson_inlier / in_front in their order, each rounded on its own
-__device__ __forceinline__ bool sampson_inlier(const double E[9], double xa, double ya, double xb, double yb, double f2, double thr2) {
-#pragma clang fp contract(off)
-  const double l0 = E[0] * xa + E[1] * ya + E[2], l1 = E[3] * xa + E[4] * ya + E[5], l2 = E[6] * xa + E[7] * ya + E[8];
-  const double m0 = E[0] * xb + E[3] * yb + E[6], m1 = E[1] * xb + E[4] * yb + E[7];
-  const double r = xb * l0 + yb * l1 + l2;
-  const double den = l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1;
-  const double d2 = (r * r) / den;
-  return d2 * f2 <= thr2;
-}
-__device__ __forceinline__ bool in_front(const double R[9], const double t[3], double sign, double xa, double ya, double xb, double yb) {
-#pragma clang fp contract(off)
-  const double p0 = R[0] * xa + R[1] * ya + R[2], p1 = R[3] * xa + R[4] * ya + R[5], p2 = R[6] * xa + R[7] * ya + R[8];
-  const double t0 = sign * t[0], t1 = sign * t[1], t2 = sign * t[2];
-  const double pp = p0 * p0 + p1 * p1 + p2 * p2, qq = xb * xb + yb * yb + 1.0, pq = p0 * xb + p1 * yb + p2;
-  const double pt = p0 * t0 + p1 * t1 + p2 * t2, qt = xb * t0 + yb * t1 + t2;
-  const double det = pp * qq - pq * pq;
-  const double za = (pq * qt - qq * pt) / det, zb = (pp * qt - pq * pt) / det;
-  return za > 0.0 && zb > 0.0;
-}
-
 __global__ __launch_bounds__(kEpiBlock) void epipolar_score_kernel(const EpiScoreArgs A) {
   const int lane = threadIdx.x, t = blockIdx.x;   // (one workgroup per task: every branch on t is uniform across the wave)
   const bool skip = A.status_in && A.status_in[t] == 0;
@@ -203,7 +177,7 @@ __global__ __launch_bounds__(kEpiBlock) void epipolar_score_kernel(const EpiScor
   // the correspondences the task counts over: all of them, or (a batched call) the range of the task's pair, with the pair's focal length
   int start = 0, n = A.n;
   double f2 = A.f2;
-  if (A.pairs) { const EpiPair P = A.pairs[t / A.tasks_per_pair]; start = P.start; n = P.n; f2 = P.f2; }
+  if (A.pairs) { const PairRange P = A.pairs[t / A.tasks_per_pair]; start = P.start; n = P.n; f2 = P.f2; }
   int inl = 0, front[4] = {0, 0, 0, 0};
   if (ok) {
     for (int base = 0; base < n; base += kEpiBlock) {   // (uniform trip count: every lane reaches every ballot)
@@ -255,111 +229,7 @@ __global__ __launch_bounds__(256) void epipolar_inliers_kernel(const EpiScoreArg
   mask[i] = sampson_inlier(E, A.na[2 * (size_t)i], A.na[2 * (size_t)i + 1], A.nb[2 * (size_t)i], A.nb[2 * (size_t)i + 1], A.f2, A.thr2) ? 1 : 0;
 }
 
-// ---- the loop of rsba_epipolar_ransac_pairs around the kernels above: integers and copies only, so nothing here can round differently ----
-
-// what the winner is chosen by: most inliers, then most in front (zero where that does not break ties) — one integer per task, 0 for a
-// declined one — then the lowest task.  Two reductions of one value each (a maximum, then a minimum over the tasks that reach it), both
-// by a butterfly over the wave: integers, so every lane ends with the value a serial scan ends with.
-__device__ __forceinline__ unsigned long long winner_key(const EpiWinnerArgs& A, size_t g) {
-  if (!A.status[g]) return 0ull;
-  int front = 0;
-  if (A.front_breaks_ties) {
-    front = A.num_front[g * 4];
-    for (int k = 1; k < 4; ++k) front = max(front, A.num_front[g * 4 + k]);
-  }
-  return ((unsigned long long)((unsigned)A.num_inliers[g] + 1u) << 32) | (unsigned)front;
-}
-
-__global__ __launch_bounds__(kEpiBlock) void epipolar_winner_kernel(const EpiWinnerArgs A) {
-  const int lane = threadIdx.x, p = blockIdx.x, T = A.tasks_per_pair;
-  unsigned long long best = 0ull;
-  for (int t = lane; t < T; t += kEpiBlock) best = max(best, winner_key(A, (size_t)p * T + t));
-#pragma unroll
-  for (int off = kEpiBlock / 2; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor((long long)best, off));
-  int first = INT_MAX;   // the lowest task with that key
-  for (int t = lane; t < T; t += kEpiBlock) first = min(first, best != 0ull && winner_key(A, (size_t)p * T + t) == best ? t : INT_MAX);
-#pragma unroll
-  for (int off = kEpiBlock / 2; off >= 1; off >>= 1) first = min(first, __shfl_xor(first, off));
-  if (lane != 0) return;
-  const EpiPairState& S = A.S;
-  const bool has = best != 0ull;
-  const int winner = has ? first : -1;
-  S.status[p] = has ? 1 : 0;
-  S.done[p] = has ? 0 : 1;
-  S.winner_task[p] = winner;
-  S.refits_adopted[p] = 0;
-  S.inlier_count[p] = 0;
-  const size_t g = (size_t)p * T + (has ? winner : 0);
-  S.num_inliers[p] = has ? A.num_inliers[g] : 0;
-  for (int c = 0; c < 4; ++c) S.num_front[(size_t)p * 4 + c] = has ? A.num_front[g * 4 + c] : 0;
-  if (!has) return;
-  for (int k = 0; k < 9; ++k) S.E[(size_t)p * 9 + k] = A.E[g * 9 + k];
-  for (int k = 0; k < 6; ++k) S.pose[(size_t)p * 6 + k] = A.poses[g * 6 + k];
-}
-
-__global__ __launch_bounds__(256) void epipolar_pair_masks_kernel(const EpiPairState S, const int32_t* __restrict__ point_pair, int first_point, int num_points,
-                                                                  double thr2, const double* __restrict__ na, const double* __restrict__ nb) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= num_points) return;
-  const size_t g = (size_t)first_point + i;
-  const int p = point_pair[g];
-  if (S.done[p]) return;   // (no winner: the flags stay zero; no adopted refit: they stay the last matrix's)
-  double E[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) E[k] = S.E[(size_t)p * 9 + k];
-  S.mask[g] = sampson_inlier(E, na[2 * g], na[2 * g + 1], nb[2 * g], nb[2 * g + 1], S.pairs[p].f2, thr2) ? 1 : 0;
-}
-
-// one wave per pair: lane l of a ballot writes at the running base plus the number of set lanes below it — the order of a serial push_back
-__global__ __launch_bounds__(kEpiBlock) void epipolar_compact_kernel(const EpiPairState S) {
-  const int lane = threadIdx.x, p = blockIdx.x;
-  if (S.done[p]) { if (lane == 0) S.inlier_count[p] = 0; return; }   // (uniform across the wave)
-  const EpiPair P = S.pairs[p];
-  int count = 0;
-  for (int base = 0; base < P.n; base += kEpiBlock) {   // (uniform trip count)
-    const int i = base + lane;
-    const bool in = i < P.n && S.mask[(size_t)P.start + i] != 0;
-    const unsigned long long ballot = __ballot(in);
-    if (in) S.inlier_idx[(size_t)P.start + count + __popcll(ballot & ((1ull << lane) - 1ull))] = P.start + i;
-    count += __popcll(ballot);
-  }
-  if (lane != 0) return;
-  S.inlier_count[p] = count;
-  if (count < 8) S.done[p] = 1;   // (the eight-point kernel declines a list under 8 on its own; later rounds skip the pair)
-}
-
-__global__ __launch_bounds__(256) void epipolar_adopt_kernel(const EpiAdoptArgs A) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const EpiPairState& S = A.S;
-  if (p >= S.num_pairs || S.done[p]) return;
-  if (!A.status[p] || A.num_inliers[p] < S.num_inliers[p]) { S.done[p] = 1; return; }   // not adopted: the next round would refit the same set
-  S.num_inliers[p] = A.num_inliers[p];
-  for (int c = 0; c < 4; ++c) S.num_front[(size_t)p * 4 + c] = A.num_front[(size_t)p * 4 + c];
-  for (int k = 0; k < 9; ++k) S.E[(size_t)p * 9 + k] = A.E[(size_t)p * 9 + k];
-  for (int k = 0; k < 6; ++k) S.pose[(size_t)p * 6 + k] = A.poses[(size_t)p * 6 + k];
-  S.refits_adopted[p] += 1;
-}
-
 }  // namespace
-
-hipError_t launch_epipolar_winner(const EpiWinnerArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(epipolar_winner_kernel, dim3(A.S.num_pairs), dim3(kEpiBlock), 0, st, A);
-  return hipGetLastError();
-}
-hipError_t launch_epipolar_pair_masks(const EpiPairState& S, const int32_t* point_pair, int first_point, int num_points, double thr2, const double* na, const double* nb,
-                                      hipStream_t st) {
-  if (num_points <= 0) return hipSuccess;
-  hipLaunchKernelGGL(epipolar_pair_masks_kernel, dim3((num_points + 255) / 256), dim3(256), 0, st, S, point_pair, first_point, num_points, thr2, na, nb);
-  return hipGetLastError();
-}
-hipError_t launch_epipolar_compact(const EpiPairState& S, hipStream_t st) {
-  hipLaunchKernelGGL(epipolar_compact_kernel, dim3(S.num_pairs), dim3(kEpiBlock), 0, st, S);
-  return hipGetLastError();
-}
-hipError_t launch_epipolar_adopt(const EpiAdoptArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(epipolar_adopt_kernel, dim3((A.S.num_pairs + 255) / 256), dim3(256), 0, st, A);
-  return hipGetLastError();
-}
 
 hipError_t launch_epipolar_eight_point(const EpiEightArgs& A, hipStream_t st) {
   const size_t lds = (size_t)(kTri + kVec) * kEpiBlock * sizeof(double);   // 64 512 bytes

@@ -12,17 +12,12 @@
 //   homography_inliers_kernel   one lane per correspondence: the inlier flags of one H
 //   two_view_parallax_kernel    one wave per pair: every lane holds (R, t) of the pair's pose, the lanes stride over the pair's correspondences,
 //                               num_front and num_parallax are sums of ballot popcounts.
-// The loop of rsba_two_view_classify_pairs around them, integers and copies only:
-//   homography_winner_kernel      one wave per pair over its tasks: the key (inliers + 1, 0 for a declined task) and then the lowest task that
-//                                 reaches it, each by a butterfly over the wave
-//   homography_pair_masks_kernel  one lane per correspondence: the inlier flag by its pair's current H
-//   homography_compact_kernel     one wave per pair: the ascending inlier indices by ballot and the popcount of the lower lanes
-//   homography_adopt_kernel       one lane per pair: a refit adopted iff accepted and its count is not lower; else the pair is done
+// The loop of rsba_two_view_classify_pairs around them (winner, masks, compaction, adopt) is kernels_pair_loop.hip, shared with the essential
+// matrix; the deciding comparisons (invert, transfer_inlier, sampson_inlier, in_front) are two_view_rules.hpp's.
 // A DLT lane's result depends on its own subset only: no cross-lane operation, no atomics, no dependence on the launch geometry.
-#include <climits>
-
 #include "homography_state.hpp"
 #include "hyp_math.hpp"
+#include "two_view_rules.hpp"
 
 namespace rsba {
 
@@ -136,39 +131,6 @@ __global__ __launch_bounds__(kHomoBlock) void homography_dlt_kernel(const HomoDl
   A.status[t] = 1;
 }
 
-// homo_detail::invert: the adjugate over the determinant; the operations of the host form in their order, each rounded on its own (the
-// inverse feeds a deciding comparison)
-__device__ __forceinline__ bool invert(const double H[9], double Hi[9]) {
-#pragma clang fp contract(off)
-  const double c0 = H[4] * H[8] - H[5] * H[7], c1 = H[5] * H[6] - H[3] * H[8], c2 = H[3] * H[7] - H[4] * H[6];
-  const double det = H[0] * c0 + H[1] * c1 + H[2] * c2;
-  if (!(fabs(det) > 0.0)) return false;
-  Hi[0] = c0 / det; Hi[1] = (H[2] * H[7] - H[1] * H[8]) / det; Hi[2] = (H[1] * H[5] - H[2] * H[4]) / det;
-  Hi[3] = c1 / det; Hi[4] = (H[0] * H[8] - H[2] * H[6]) / det; Hi[5] = (H[2] * H[3] - H[0] * H[5]) / det;
-  Hi[6] = c2 / det; Hi[7] = (H[1] * H[6] - H[0] * H[7]) / det; Hi[8] = (H[0] * H[4] - H[1] * H[3]) / det;
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) finite = finite && isfinite(Hi[k]);
-  return finite;
-}
-
-// the deciding comparison: the operations of homo_detail::transfer_inlier in their order, each rounded on its own
-__device__ __forceinline__ bool transfer_inlier(const double H[9], const double Hi[9], double xa, double ya, double xb, double yb, double f2, double thr2) {
-#pragma clang fp contract(off)
-  const double w = H[6] * xa + H[7] * ya + H[8];
-  if (!(w > 0.0)) return false;
-  const double u = (H[0] * xa + H[1] * ya + H[2]) / w, v = (H[3] * xa + H[4] * ya + H[5]) / w;
-  const double eu = xb - u, ev = yb - v;
-  const double dab = eu * eu + ev * ev;
-  const double w2 = Hi[6] * xb + Hi[7] * yb + Hi[8];
-  if (!(w2 > 0.0)) return false;
-  const double u2 = (Hi[0] * xb + Hi[1] * yb + Hi[2]) / w2, v2 = (Hi[3] * xb + Hi[4] * yb + Hi[5]) / w2;
-  const double fu = xa - u2, fv = ya - v2;
-  const double dba = fu * fu + fv * fv;
-  const double d2 = dab > dba ? dab : dba;
-  return d2 * f2 <= thr2;
-}
-
 __global__ __launch_bounds__(kHomoBlock) void homography_score_kernel(const HomoScoreArgs A) {
   const int lane = threadIdx.x, t = blockIdx.x;   // (one workgroup per task: every branch on t is uniform across the wave)
   double H[9], Hi[9];
@@ -180,7 +142,7 @@ __global__ __launch_bounds__(kHomoBlock) void homography_score_kernel(const Homo
   }
   int start = 0, n = A.n;
   double f2 = A.f2;
-  if (A.pairs) { const HomoPair P = A.pairs[t / A.tasks_per_pair]; start = P.start; n = P.n; f2 = P.f2; }
+  if (A.pairs) { const PairRange P = A.pairs[t / A.tasks_per_pair]; start = P.start; n = P.n; f2 = P.f2; }
   int inl = 0;
   if (ok) {
     for (int base = 0; base < n; base += kHomoBlock) {   // (uniform trip count: every lane reaches every ballot)
@@ -208,98 +170,7 @@ __global__ __launch_bounds__(256) void homography_inliers_kernel(const HomoScore
   mask[i] = ok && transfer_inlier(H, Hi, A.na[2 * (size_t)i], A.na[2 * (size_t)i + 1], A.nb[2 * (size_t)i], A.nb[2 * (size_t)i + 1], A.f2, A.thr2) ? 1 : 0;
 }
 
-// ---- the loop of rsba_two_view_classify_pairs around the kernels above: integers and copies only, so nothing here can round differently ----
-
-__device__ __forceinline__ unsigned winner_key(const HomoWinnerArgs& A, size_t g) { return A.status[g] ? (unsigned)A.num_inliers[g] + 1u : 0u; }
-
-__global__ __launch_bounds__(kHomoBlock) void homography_winner_kernel(const HomoWinnerArgs A) {
-  const int lane = threadIdx.x, p = blockIdx.x, T = A.tasks_per_pair;
-  unsigned best = 0u;
-  for (int t = lane; t < T; t += kHomoBlock) best = max(best, winner_key(A, (size_t)p * T + t));
-#pragma unroll
-  for (int off = kHomoBlock / 2; off >= 1; off >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, off));
-  int first = INT_MAX;   // the lowest task with that key
-  for (int t = lane; t < T; t += kHomoBlock) first = min(first, best != 0u && winner_key(A, (size_t)p * T + t) == best ? t : INT_MAX);
-#pragma unroll
-  for (int off = kHomoBlock / 2; off >= 1; off >>= 1) first = min(first, __shfl_xor(first, off));
-  if (lane != 0) return;
-  const HomoPairState& S = A.S;
-  const bool has = best != 0u;
-  const int winner = has ? first : -1;
-  S.status[p] = has ? 1 : 0;
-  S.done[p] = has ? 0 : 1;
-  S.winner_task[p] = winner;
-  S.refits_adopted[p] = 0;
-  S.inlier_count[p] = 0;
-  const size_t g = (size_t)p * T + (has ? winner : 0);
-  S.num_inliers[p] = has ? A.num_inliers[g] : 0;
-  if (!has) return;
-  for (int k = 0; k < 9; ++k) S.H[(size_t)p * 9 + k] = A.H[g * 9 + k];
-}
-
-__global__ __launch_bounds__(256) void homography_pair_masks_kernel(const HomoPairState S, const int32_t* __restrict__ point_pair, int first_point, int num_points,
-                                                                    double thr2, const double* __restrict__ na, const double* __restrict__ nb) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= num_points) return;
-  const size_t g = (size_t)first_point + i;
-  const int p = point_pair[g];
-  if (S.done[p]) return;   // (no winner: the flags stay zero; no adopted refit: they stay the last matrix's)
-  double H[9], Hi[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) H[k] = S.H[(size_t)p * 9 + k];
-  const bool ok = invert(H, Hi);
-  S.mask[g] = ok && transfer_inlier(H, Hi, na[2 * g], na[2 * g + 1], nb[2 * g], nb[2 * g + 1], S.pairs[p].f2, thr2) ? 1 : 0;
-}
-
-// one wave per pair: lane l of a ballot writes at the running base plus the number of set lanes below it — the order of a serial push_back
-__global__ __launch_bounds__(kHomoBlock) void homography_compact_kernel(const HomoPairState S) {
-  const int lane = threadIdx.x, p = blockIdx.x;
-  if (S.done[p]) { if (lane == 0) S.inlier_count[p] = 0; return; }   // (uniform across the wave)
-  const HomoPair P = S.pairs[p];
-  int count = 0;
-  for (int base = 0; base < P.n; base += kHomoBlock) {   // (uniform trip count)
-    const int i = base + lane;
-    const bool in = i < P.n && S.mask[(size_t)P.start + i] != 0;
-    const unsigned long long ballot = __ballot(in);
-    if (in) S.inlier_idx[(size_t)P.start + count + __popcll(ballot & ((1ull << lane) - 1ull))] = P.start + i;
-    count += __popcll(ballot);
-  }
-  if (lane != 0) return;
-  if (count < 5) { S.done[p] = 1; count = 0; }   // (a refit takes at least five inliers; later rounds skip the pair)
-  S.inlier_count[p] = count;
-}
-
-__global__ __launch_bounds__(256) void homography_adopt_kernel(const HomoAdoptArgs A) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const HomoPairState& S = A.S;
-  if (p >= S.num_pairs || S.done[p]) return;
-  if (!A.status[p] || A.num_inliers[p] < S.num_inliers[p]) { S.done[p] = 1; return; }   // not adopted: the next round would refit the same set
-  S.num_inliers[p] = A.num_inliers[p];
-  for (int k = 0; k < 9; ++k) S.H[(size_t)p * 9 + k] = A.H[(size_t)p * 9 + k];
-  S.refits_adopted[p] += 1;
-}
-
 // ---- the parallax rule ----
-// epi_detail::sampson_inlier / in_front, restated as kernels_epipolar.hip restates them: the host form's operations in its order
-__device__ __forceinline__ bool sampson_inlier(const double E[9], double xa, double ya, double xb, double yb, double f2, double thr2) {
-#pragma clang fp contract(off)
-  const double l0 = E[0] * xa + E[1] * ya + E[2], l1 = E[3] * xa + E[4] * ya + E[5], l2 = E[6] * xa + E[7] * ya + E[8];
-  const double m0 = E[0] * xb + E[3] * yb + E[6], m1 = E[1] * xb + E[4] * yb + E[7];
-  const double r = xb * l0 + yb * l1 + l2;
-  const double den = l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1;
-  const double d2 = (r * r) / den;
-  return d2 * f2 <= thr2;
-}
-__device__ __forceinline__ bool in_front(const double R[9], const double t[3], double xa, double ya, double xb, double yb) {
-#pragma clang fp contract(off)
-  const double p0 = R[0] * xa + R[1] * ya + R[2], p1 = R[3] * xa + R[4] * ya + R[5], p2 = R[6] * xa + R[7] * ya + R[8];
-  const double t0 = 1.0 * t[0], t1 = 1.0 * t[1], t2 = 1.0 * t[2];
-  const double pp = p0 * p0 + p1 * p1 + p2 * p2, qq = xb * xb + yb * yb + 1.0, pq = p0 * xb + p1 * yb + p2;
-  const double pt = p0 * t0 + p1 * t1 + p2 * t2, qt = xb * t0 + yb * t1 + t2;
-  const double det = pp * qq - pq * pq;
-  const double za = (pq * qt - qq * pt) / det, zb = (pp * qt - pq * pt) / det;
-  return za > 0.0 && zb > 0.0;
-}
 // the angle between the rays a and R^T b is at least the threshold: a . (R^T b) <= c sqrt(|a|^2 |R^T b|^2)
 __device__ __forceinline__ bool has_parallax(const double R[9], double xa, double ya, double xb, double yb, double c) {
 #pragma clang fp contract(off)
@@ -313,7 +184,7 @@ __global__ __launch_bounds__(kHomoBlock) void two_view_parallax_kernel(const Par
   const int lane = threadIdx.x, p = blockIdx.x;   // (one workgroup per pair: every branch on p is uniform across the wave)
   int front = 0, par = 0;
   if (A.pair_status[p]) {
-    const HomoPair P = A.pairs[p];
+    const PairRange P = A.pairs[p];
     double E[9], R[9], tv[3], pose[6];
 #pragma unroll
     for (int k = 0; k < 9; ++k) E[k] = A.E[(size_t)p * 9 + k];
@@ -338,7 +209,7 @@ __global__ __launch_bounds__(kHomoBlock) void two_view_parallax_kernel(const Par
       if (i < P.n) {
         const size_t j = 2 * ((size_t)P.start + i);
         const double xa = A.na[j], ya = A.na[j + 1], xb = A.nb[j], yb = A.nb[j + 1];
-        fr = sampson_inlier(E, xa, ya, xb, yb, P.f2, A.thr2) && in_front(R, tv, xa, ya, xb, yb);
+        fr = sampson_inlier(E, xa, ya, xb, yb, P.f2, A.thr2) && in_front(R, tv, 1.0, xa, ya, xb, yb);
         pa = fr && has_parallax(R, xa, ya, xb, yb, A.cos_min);
       }
       front += __popcll(__ballot(fr));
@@ -363,24 +234,6 @@ hipError_t launch_homography_score(const HomoScoreArgs& A, hipStream_t st) {
 }
 hipError_t launch_homography_inliers(const HomoScoreArgs& A, uint8_t* mask, hipStream_t st) {
   hipLaunchKernelGGL(homography_inliers_kernel, dim3((A.n + 255) / 256), dim3(256), 0, st, A, mask);
-  return hipGetLastError();
-}
-hipError_t launch_homography_winner(const HomoWinnerArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(homography_winner_kernel, dim3(A.S.num_pairs), dim3(kHomoBlock), 0, st, A);
-  return hipGetLastError();
-}
-hipError_t launch_homography_pair_masks(const HomoPairState& S, const int32_t* point_pair, int first_point, int num_points, double thr2, const double* na, const double* nb,
-                                        hipStream_t st) {
-  if (num_points <= 0) return hipSuccess;
-  hipLaunchKernelGGL(homography_pair_masks_kernel, dim3((num_points + 255) / 256), dim3(256), 0, st, S, point_pair, first_point, num_points, thr2, na, nb);
-  return hipGetLastError();
-}
-hipError_t launch_homography_compact(const HomoPairState& S, hipStream_t st) {
-  hipLaunchKernelGGL(homography_compact_kernel, dim3(S.num_pairs), dim3(kHomoBlock), 0, st, S);
-  return hipGetLastError();
-}
-hipError_t launch_homography_adopt(const HomoAdoptArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(homography_adopt_kernel, dim3((A.S.num_pairs + 255) / 256), dim3(256), 0, st, A);
   return hipGetLastError();
 }
 hipError_t launch_two_view_parallax(const ParallaxArgs& A, hipStream_t st) {

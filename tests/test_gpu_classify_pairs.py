@@ -99,12 +99,17 @@ def essential(capi, c):
 
 
 def classify(capi, c, order=None, max_tasks=0):
+    """the C call over the pairs in `order` (None: an empty pair, n = 0, whose subsets are never read; it is given pair 0's essential result)"""
     order = list(range(c["P"])) if order is None else order
-    sizes = [c["offset"][p + 1] - c["offset"][p] for p in order]
-    points = np.concatenate([np.arange(c["offset"][p], c["offset"][p + 1]) for p in order]).astype(np.int64)
+    empty = [k for k, p in enumerate(order) if p is None]
+    known = [0 if p is None else p for p in order]
+    sizes = [0 if p is None else c["offset"][p + 1] - c["offset"][p] for p in order]
+    points = np.concatenate([np.zeros(0)] + [np.arange(c["offset"][p], c["offset"][p + 1]) for p in order if p is not None]).astype(np.int64)
+    subsets = c["sub4"][known]
+    subsets[empty] = 10 ** 6
     e = c["essential"]
-    out = capi.two_view_classify_pairs(c["cams"], c["cam_a"][order], c["cam_b"][order], np.concatenate([[0], np.cumsum(sizes)]), c["xy_a"][points], c["xy_b"][points],
-                                       e["E"][order], e["poses"][order], c["pair_status"][order], c["sub4"][order], threshold_px=H.THRESHOLD_PX, refits=3,
+    out = capi.two_view_classify_pairs(c["cams"], c["cam_a"][known], c["cam_b"][known], np.concatenate([[0], np.cumsum(sizes)]), c["xy_a"][points], c["xy_b"][points],
+                                       e["E"][known], e["poses"][known], c["pair_status"][known], subsets, threshold_px=H.THRESHOLD_PX, refits=3,
                                        cos_min_parallax=COS_MIN, max_tasks_per_launch=max_tasks, H_out=np.full((len(order), 9), SENTINEL))
     out["offset"] = np.concatenate([[0], np.cumsum(sizes)])
     return out
@@ -115,8 +120,8 @@ def pair_bytes(out, k):
     return b"".join(np.ascontiguousarray(out[key][k]).tobytes() for key in ("H", "status", "winner_task", "refits_adopted", "num_inliers", "num_front", "num_parallax")) + out["mask"][lo:hi].tobytes()
 
 
-def run_example(example, c, mode, max_tasks=0):
-    r = subprocess.run([example, "pairs", str(c["path"]), mode, str(TASKS), str(H.THRESHOLD_PX), "3", str(MIN_INLIERS), str(H.RNG_STATE), "0", "five_point", str(DEG), str(max_tasks)],
+def run_example(example, c, mode, max_tasks=0, tasks=TASKS):
+    r = subprocess.run([example, "pairs", str(c["path"]), mode, str(tasks), str(H.THRESHOLD_PX), "3", str(MIN_INLIERS), str(H.RNG_STATE), "0", "five_point", str(DEG), str(max_tasks)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.split("\n")
@@ -182,6 +187,60 @@ def test_the_bytes_depend_neither_on_the_chunking_nor_on_the_order(capi, call):
         assert pair_bytes(rev, k) == pair_bytes(base, p), p
     one = classify(capi, c, order=[1])
     assert pair_bytes(one, 0) == pair_bytes(base, 1)
+
+
+def is_untouched_empty(out, k):
+    return (out["status"][k] == 0 and out["winner_task"][k] == -1 and out["refits_adopted"][k] == 0 and out["num_inliers"][k] == 0 and out["num_front"][k] == 0
+            and out["num_parallax"][k] == 0 and np.all(out["H"][k] == SENTINEL) and out["offset"][k] == out["offset"][k + 1])
+
+
+def test_empty_pairs_are_declined_and_change_nothing_around_them(capi, call):
+    """pairs of n = 0 (with pair_status 1) between three of the pairs: in the middle of a chunk and first in one (three pairs per launch),
+    last in a chunk (two per launch), all in one launch; then a call of empty pairs only (no correspondences at all)"""
+    c = call
+    order = [0, 5, 11]
+    assert [c["pairs"][p]["name"] for p in order[1:]] == ["short_4", "two_cameras"] and c["pair_status"][0] == 1
+    base = classify(capi, c, order=order)
+    assert base["status"].all()
+    mixed = [0, None, 5, None, 11]
+    for max_tasks in (3 * TASKS, 2 * TASKS, 0):
+        out = classify(capi, c, order=mixed, max_tasks=max_tasks)
+        assert is_untouched_empty(out, 1) and is_untouched_empty(out, 3), max_tasks
+        assert [pair_bytes(out, k) for k in (0, 2, 4)] == [pair_bytes(base, k) for k in range(3)], max_tasks
+    for max_tasks in (0, TASKS):
+        none = classify(capi, c, order=[None, None, None], max_tasks=max_tasks)
+        assert len(none["mask"]) == 0 and all(is_untouched_empty(none, k) for k in range(3))
+
+
+def test_a_second_stride_of_the_winner_kernel(capi, example, call, tmp_path):
+    """65 subsets per pair — one stride of the wave over a pair's tasks and a single lane of the next, in the winner kernel the homography shares
+    with the essential matrix (which the other tests run at 100 tasks) — for three of the pairs, against the pair-by-pair path as above"""
+    c = call
+    tasks, order = 65, [0, 5, 11]
+    pairs = [c["pairs"][p] for p in order]
+    sizes = [len(p["xy_a"]) for p in pairs]
+
+    def subsets(n, m):
+        out = subprocess.run([c["host"], "subsets", str(n), str(m), str(tasks), str(H.RNG_STATE)], check=True, capture_output=True, text=True).stdout
+        return np.array([[int(x) for x in line.split()] for line in out.strip().split("\n")], dtype=np.int32)
+    offset = np.concatenate([[0], np.cumsum(sizes)])
+    xy_a, xy_b = np.concatenate([p["xy_a"] for p in pairs]), np.concatenate([p["xy_b"] for p in pairs])
+    sub5 = np.stack([subsets(n, 5) if n >= 8 else np.full((tasks, 5), 10 ** 6, dtype=np.int32) for n in sizes])
+    e = capi.epipolar_ransac_pairs(c["cams"], c["cam_a"][order], c["cam_b"][order], offset, xy_a, xy_b, sub5, threshold_px=H.THRESHOLD_PX, refits=3)
+    pair_status = ((e["status"] == 1) & (e["num_front"].max(axis=1) >= MIN_INLIERS)).astype(np.uint8)
+    out = capi.two_view_classify_pairs(c["cams"], c["cam_a"][order], c["cam_b"][order], offset, xy_a, xy_b, e["E"], e["poses"], pair_status,
+                                       np.stack([subsets(n, 4) for n in sizes]), threshold_px=H.THRESHOLD_PX, refits=3, cos_min_parallax=COS_MIN,
+                                       H_out=np.full((3, 9), SENTINEL))
+    path = tmp_path / "three.bin"
+    H.write_pairs_file(path, pairs)
+    _, ref = run_example(example, dict(path=path, P=3), "sequential", tasks=tasks)
+    for k, r in enumerate(ref):
+        lo, hi = offset[k], offset[k + 1]
+        assert out["status"][k] == r["h_ok"] == 1 and r["essential_ok"] == pair_status[k], k
+        assert out["winner_task"][k] == r["winner_task"] and out["refits_adopted"][k] == r["refits_adopted"] and out["num_inliers"][k] == r["num_inliers"], k
+        assert np.array_equal(out["mask"][lo:hi], r["mask"]) and np.array_equal(out["H"][k], r["H"]), k
+        assert (out["num_front"][k], out["num_parallax"][k]) == (r["num_front"], r["num_parallax"]), k
+    print("winner tasks of 65:", out["winner_task"].tolist())
 
 
 def test_the_new_call_leaves_the_essential_path_alone(capi, call):

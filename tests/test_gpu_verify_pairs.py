@@ -3,7 +3,9 @@ existing path: findEssentialRansac on each pair alone, run pair by pair by the s
 
 One call of 67 pairs, assembled by repetition from the scenes the two-view tests use (verify_pairs_common.py): the four outlier scenes
 (n = 436 .. 449, no multiple of 64; they take refits), the case list (n = 8, 12, 24, 48), the planar scene (60), the pure-rotation and
-coincident-point pairs (n = 8, every hypothesis declined), two pairs with a distorted and a pinhole camera, and a pair of 7 in the middle.
+coincident-point pairs (n = 8, every hypothesis declined), two pairs with a distorted and a pinhole camera, a pair of 7 in the middle and
+next to it the sparse pair (n = 10, six correspondences and four gross outliers: a winner under the refit size, so the compaction of the
+first round ends the pair with a non-zero count — test_verify_pairs_host.py checks that on the host).
 67 pairs: the refit runs one lane per pair, so the call crosses a 64-lane workgroup.  100 subsets per pair, both solvers.
 
 Everything is compared for equality — the counts, the masks, and E and the pose bit for bit: the batched call runs the single-pair calls'
@@ -23,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = -12345.678
-P, TASKS, MIDDLE = 67, 100, 33
+P, TASKS, MIDDLE, SPARSE = 67, 100, 33, 34
 
 
 @pytest.fixture(scope="module")
@@ -50,6 +52,7 @@ def call(tmp_path_factory):
     base = V.outlier_pairs() + V.small_pairs()
     pairs = [base[i % len(base)] for i in range(P)]
     pairs[MIDDLE] = V.short_pair()
+    pairs[SPARSE] = V.sparse_pair()
     cams, index = [], {}
     for p in pairs:
         for side in ("cam_a", "cam_b"):
@@ -98,13 +101,18 @@ def reference(exe, call, m):
 
 
 def batched(capi, call, m, order=None, max_tasks=0):
-    """the C call over the pairs in `order`, the outputs that a pair without a winner must not touch filled with a sentinel"""
+    """the C call over the pairs in `order` (None: an empty pair, n = 0, whose subsets are never read), the outputs that a pair without a
+    winner must not touch filled with a sentinel"""
     order = list(range(P)) if order is None else order
-    sizes = [call["offset"][p + 1] - call["offset"][p] for p in order]
-    points = np.concatenate([np.arange(call["offset"][p], call["offset"][p + 1]) for p in order]).astype(np.int64)
+    empty = [k for k, p in enumerate(order) if p is None]
+    known = [0 if p is None else p for p in order]
+    sizes = [0 if p is None else call["offset"][p + 1] - call["offset"][p] for p in order]
+    points = np.concatenate([np.zeros(0)] + [np.arange(call["offset"][p], call["offset"][p + 1]) for p in order if p is not None]).astype(np.int64)
+    subsets = call["subsets"][m][known]
+    subsets[empty] = 10 ** 6
     E = np.full((len(order), 9), SENTINEL); poses = np.full((len(order), 6), SENTINEL)
-    out = capi.epipolar_ransac_pairs(call["cams"], call["cam_a"][order], call["cam_b"][order], np.concatenate([[0], np.cumsum(sizes)]), call["xy_a"][points], call["xy_b"][points],
-                                     call["subsets"][m][order], threshold_px=V.OPTIONS["threshold_px"], refits=V.OPTIONS["refits"], max_tasks_per_launch=max_tasks,
+    out = capi.epipolar_ransac_pairs(call["cams"], call["cam_a"][known], call["cam_b"][known], np.concatenate([[0], np.cumsum(sizes)]), call["xy_a"][points], call["xy_b"][points],
+                                     subsets, threshold_px=V.OPTIONS["threshold_px"], refits=V.OPTIONS["refits"], max_tasks_per_launch=max_tasks,
                                      E_out=E, poses_out=poses)
     out["offset"] = np.concatenate([[0], np.cumsum(sizes)])
     return out
@@ -170,6 +178,28 @@ def test_find_essential_ransac_pairs_prints_what_the_sequential_calls_print(exe,
     text, _ = reference(exe, call, m)
     assert run_example(exe, call["path"], "batched", m, P)[0] == text
     assert run_example(exe, call["path"], "batched", m, P, max_tasks=900)[0] == text
+
+
+def is_untouched_empty(out, k):
+    return (out["status"][k] == 0 and out["winner_task"][k] == -1 and out["refits_adopted"][k] == 0 and out["num_inliers"][k] == 0 and not out["num_front"][k].any()
+            and np.all(out["E"][k] == SENTINEL) and np.all(out["poses"][k] == SENTINEL) and out["offset"][k] == out["offset"][k + 1])
+
+
+@pytest.mark.parametrize("m", [8, 5])
+def test_empty_pairs_are_declined_and_change_nothing_around_them(capi, call, m):
+    """pairs of n = 0 between main_pinhole, main_distorted and single: in the middle of a chunk and first in one (three pairs per launch), last
+    in a chunk (two per launch), all in one launch; then a call of empty pairs only (no correspondences at all)"""
+    order = [4, 5, 6]
+    base = batched(capi, call, m, order=order)
+    assert base["status"].all()
+    mixed = [4, None, 5, None, 6]
+    for max_tasks in (3 * TASKS, 2 * TASKS, 0):
+        out = batched(capi, call, m, order=mixed, max_tasks=max_tasks)
+        assert is_untouched_empty(out, 1) and is_untouched_empty(out, 3), max_tasks
+        assert [pair_bytes(out, k) for k in (0, 2, 4)] == [pair_bytes(base, k) for k in range(3)], max_tasks
+    for max_tasks in (0, TASKS):
+        none = batched(capi, call, m, order=[None, None, None], max_tasks=max_tasks)
+        assert len(none["mask"]) == 0 and all(is_untouched_empty(none, k) for k in range(3))
 
 
 def test_bad_arguments_are_errors_and_leave_the_outputs_untouched(capi, call):

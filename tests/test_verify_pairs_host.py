@@ -45,6 +45,20 @@ def test_pairs_from_the_host_definitions_equal_host_ransac_per_pair(host, pairs,
     assert len({r["winner_task"] for r in res}) > 3
 
 
+def test_the_sparse_pair_keeps_a_winner_below_the_refit_size(host):
+    """the pair the device tests use for the compaction of a pair under the refit size with a non-zero count: with five-point subsets the
+    host loop's winner keeps 5, 6 or 7 inliers, so no refit is tried (seed V.SPARSE_SEED; checked here, not assumed)"""
+    exe, d = host
+    path = d / "sparse.bin"
+    sparse = V.sparse_pair()
+    assert 8 <= len(sparse["xy_a"]) <= 12
+    V.write_pairs_file(path, [sparse])
+    r = V.parse_results(run(exe, "pairs", path, "single", *V.option_args(V.OPTIONS, 5)), 1)[0]
+    print(f"sparse pair, m = 5: winner {r['winner_task']}, {r['num_inliers']} inliers, {r['refits_adopted']} refits adopted")
+    assert r["winner_task"] >= 0 and 5 <= r["num_inliers"] <= 7 and r["refits_adopted"] == 0
+    assert int(r["mask"].sum()) == r["num_inliers"]
+
+
 @pytest.fixture(scope="module")
 def session():
     return V.SmallSession()

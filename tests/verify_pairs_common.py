@@ -41,6 +41,23 @@ def short_pair():
     return pair(c["cam_a"], c["cam_b"], c["xy_a"][:7], c["xy_b"][:7], "seven")
 
 
+SPARSE_SEED = 6   # of seeds 0 .. 11, the one whose m = 5 winner keeps exactly the six (the others: seven or eight inliers)
+
+
+def sparse_pair(seed=SPARSE_SEED):
+    """n = 10, mostly gross outliers: six noise-free correspondences of a cloud and four pairs of unrelated pixels, shuffled.  A five-point
+    hypothesis from five of the six collects the six (and, by chance, perhaps a seventh) and nothing more, so the winner of m = 5 has fewer
+    inliers than a refit takes: the loop ends at the compaction of the first round with a non-zero count.  test_verify_pairs_host.py checks on
+    the host that this seed does so."""
+    rng = np.random.default_rng(seed)
+    X = R._cloud(rng, 6)
+    pose = R._unit_centre(R.POSE_B)
+    xy_a = np.concatenate([project(CAM_PLAIN, np.zeros(6), X), rng.uniform([40.0, 40.0], [1240.0, 680.0], (4, 2))])
+    xy_b = np.concatenate([project(CAM_PLAIN, pose, X), rng.uniform([40.0, 40.0], [1240.0, 680.0], (4, 2))])
+    order = rng.permutation(10)
+    return pair(CAM_PLAIN, CAM_PLAIN, xy_a[order], xy_b[order], "sparse")
+
+
 def outlier_pairs():
     out = []
     for fb, rolling in R.OUTLIER_SCENES:
